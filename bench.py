@@ -7,10 +7,11 @@ step is generate_poa() (H2D of the packed reads + the POA kernel) followed by
 get_consensus() (D2H + the per-window result vectors) on a batch of 1024
 windows x 32 reads x ~1 kb (std::minstd_rand(seed w) generators,
 BatchSize(1100, 32), full alignment, -8/-6/8, int16 scores); windows are added
-outside the timed region, as the reference's PauseTiming does.  The same line
-carries `secondary` objects for config D (cudaaligner global alignment,
-align_all() + sync_alignments() on 100k pairs x 5 kb) and config E (the
-multi-batch streaming driver on one GPU's share of the 1M-window job).
+outside the timed region, as the reference's PauseTiming does.  With `--full`
+the same line carries `secondary` objects for config D (cudaaligner global
+alignment, align_all() + sync_alignments() on 100k pairs x 5 kb), config C and
+config E (the multi-batch streaming driver on one GPU's share of the 1M-window
+job).
 
 Config E (`--config E`, and the default when WORLD_SIZE > 1): the reference's
 multi-batch benchmark unit (multi_batch.hpp:64-171, BM_MultiBatchTest): windows
@@ -21,9 +22,16 @@ by one process_batches call (K = 20: 125k windows per GPU, the 1M-window job
 on 8 GPUs).  Weak scaling; one process per GPU; no collective inside the timed
 region; after it, rank 0 gathers every rank's consensus over RCCL.
 
-Prints one JSON line (rank 0) with roofline and cpu_baseline objects.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+the K steps of its one config and prints one JSON line (rank 0) with the
+headline figure, `ms_per_step` and the roofline of the timed kernels.  `--full`
+adds everything that takes work of its own: the `secondary` objects of the
+default run, the CPU baselines (`cpu_baseline`) and the checks against the
+oracle (`parity`).  `--dump-outputs DIR` writes what the last timed step
+returned to its caller as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -39,9 +47,9 @@ import torch.distributed as dist  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 E_STEP_WINDOWS = 6250   # config E: windows per step (20 steps = 125k windows per GPU)
 # The N > 1 default workload is config E; its like-for-like N = 1 point is
-# `bench.py --config E` (also the secondary.E object of the default N = 1 line,
-# whose headline is config B, the reference's single-batch benchmark).
-E_ANCHOR = "N=1 like-for-like point: `python bench.py --config E` (= secondary.E of the default --gpus 1 line)"
+# `bench.py --config E` (also the secondary.E object of the default N = 1 line
+# with --full, whose headline is config B, the reference's single-batch benchmark).
+E_ANCHOR = "N=1 like-for-like point: `python bench.py --config E` (= secondary.E of the default --gpus 1 --full line)"
 
 ALIGNER_CONFIGS = {
     # 100k pairs x 5 kb, ~10% difference; Hirschberg-Myers
@@ -143,20 +151,27 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the default run's secondary objects "
+                        "(D, C, E), the CPU baselines and the parity checks against the oracle")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32")
     p.add_argument("--config", default=None,
                    choices=sorted(CONFIGS) + sorted(ALIGNER_CONFIGS) + sorted(STREAM_CONFIGS),
                    help="default: B on one GPU (with D and E as secondary objects), E when WORLD_SIZE > 1")
     p.add_argument("--pairs", type=int, default=None, help="override aligner pairs per GPU")
     p.add_argument("--windows", type=int, default=None, help="override windows per GPU (B, C)")
     p.add_argument("--cpu-sample", type=int, default=None, help="windows / pairs in the CPU baseline sample")
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--no-secondary", action="store_true", help="default run: skip the D and E objects")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
+    p.add_argument("--no-secondary", action="store_true", help="--full default run: skip the D, C and E objects")
     p.add_argument("--secondary-steps", type=int, default=3, help="timed steps of the D object")
     p.add_argument("--stream-batches", type=int, default=2, help="E: concurrent batches (streams + host threads)")
     p.add_argument("--stream-batch-windows", type=int, default=4096, help="E: windows per batch")
     p.add_argument("--stream-step-windows", type=int, default=None,
                    help="E: windows per step (default %d; 20 steps = 125k windows per GPU)" % E_STEP_WINDOWS)
     p.add_argument("--secondary-c-steps", type=int, default=3, help="timed steps of the default run's C object")
+    p.add_argument("--secondary-e-steps", type=int, default=20,
+                   help="most timed steps of the default run's E object (it runs --steps of them up to this)")
     p.add_argument("--cpus", type=int, default=None,
                    help="pin each rank to K host CPUs (rank r: the r-th K of its affinity set) before any GPU "
                         "call, to predict a host-bound multi-GPU run on one GPU")
@@ -258,6 +273,40 @@ def summary_of(line):
     return s
 
 
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(dirname, arrays, lengths=None, fill=0):
+    """--dump-outputs DIR: the arrays the timed path handed its caller in the
+    last timed step, one row per window / pair, as DIR/<name>.npy in float32
+    (every value is a small integer: bases, coverage counts, lengths, states,
+    status codes).  Outputs over DUMP_BYTES are cut to a fixed sample of rows
+    (RandomState(0), the same rows in every array); DIR/rows.npy holds the
+    rows' indices.  lengths: name -> per-row live length; cells past it are
+    buffer padding and are written as `fill`."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = 8 + sum(4 * int(np.prod(a.shape[1:], dtype=np.int64)) for a in arrays.values())
+    k = int(max(1, min(n, DUMP_BYTES // row_bytes)))
+    rows = np.arange(n) if k == n else np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+    np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        a = np.asarray(a)[rows]
+        if lengths and name in lengths:
+            live = np.arange(a.shape[1])[None, :] < np.asarray(lengths[name])[rows][:, None]
+            a = np.where(live.reshape(live.shape + (1,) * (a.ndim - 2)), a, fill)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def strings_to_rows(strings, width=None):
+    """Equal-width uint8 rows (zero padded) of a list of str."""
+    width = width or max([len(s) for s in strings] + [1])
+    out = np.zeros((len(strings), width), np.uint8)
+    for i, s in enumerate(strings):
+        out[i, :len(s)] = np.frombuffer(s.encode(), np.uint8)
+    return out
+
+
 class Ctx:
     """One process per GPU (torch.distributed.run sets RANK / LOCAL_RANK /
     WORLD_SIZE); RCCL ("nccl") between the ranks.  dry: gloo on CPU, no GPU."""
@@ -328,6 +377,52 @@ def roofline(alg_bytes, kernel_ms, traffic, kernel, source=None, sq=None):
     return r
 
 
+def aligner_parity(cfg, recipe, qs, ts, paths, plen, mq):
+    """--full: the batch's paths against the oracle and the size-independent checks."""
+    from oracle import oracle
+    n, L = len(qs), cfg["length"]
+    k = min(8 if L <= 20000 else 1, n)
+    algo = ALIGNER_ALGOS[cfg["algorithm"]][0]
+    gold = golden_long(recipe, L, cfg["algorithm"]) if recipe else None
+    if gold is not None:
+        # the first pair against tests/golden/aligner_long.json (oracle output,
+        # make_aligner_long.py): a 100 kb oracle run takes ~40 s
+        import hashlib
+        p0 = paths[0, :plen[0]][::-1].tobytes()
+        ok = int(plen[0]) == gold["path_length"] and hashlib.sha256(p0).hexdigest() == gold["path_sha256"]
+        parity = {"pairs_checked": 1, "bit_exact_vs_oracle": bool(ok),
+                  "pinned_by": "tests/golden/aligner_long.json: " + gold["name"]}
+    else:
+        ok = all(paths[i, :plen[i]][::-1].tolist() == oracle.align(qs[i], ts[i], algo, mq) for i in range(k))
+        parity = {"pairs_checked": k, "bit_exact_vs_oracle": bool(ok)}
+    # size-independent check over every pair: a global alignment consumes the
+    # whole query (match/mismatch + deletion) and the whole target (match/
+    # mismatch + insertion; cudaaligner.hpp:46-52)
+    R = paths.shape[1]
+    live = np.arange(R)[None, :] < plen[:, None]
+    mm = (((paths == 0) | (paths == 1)) & live).sum(1)
+    parity["all_pairs_consume_query_and_target"] = bool(
+        np.all(mm + ((paths == 3) & live).sum(1) == np.array([len(q) for q in qs])) and
+        np.all(mm + ((paths == 2) & live).sum(1) == np.array([len(t) for t in ts])))
+    kb = min(1000, n)
+    bases_ok = True
+    for i in range(kb):
+        p = paths[i, :plen[i]][::-1]
+        qi = np.cumsum((p == 0) | (p == 1) | (p == 3)) - 1
+        ti = np.cumsum((p == 0) | (p == 1) | (p == 2)) - 1
+        qb = np.frombuffer(qs[i], np.uint8)
+        tb = np.frombuffer(ts[i], np.uint8)
+        m, x = p == 0, p == 1
+        bases_ok = bases_ok and bool(np.all(qb[qi[m]] == tb[ti[m]]) and np.all(qb[qi[x]] != tb[ti[x]]))
+    parity["pairs_match_states_on_equal_bases"] = {"pairs": kb, "ok": bases_ok}
+    if cfg["algorithm"] == "myers_banded":
+        # not an invariant of the reference's banded backtrace: its neighbour
+        # scores at the band edges (myers_gpu.cu:377-494) can label unequal
+        # bases as a match on long pairs; the oracle restatement does the same
+        parity["pairs_match_states_on_equal_bases"]["invariant"] = False
+    return parity
+
+
 # ---------------------------------------------------------------------------
 # config D (and D_*): global alignments/s, step = align_all() + sync_alignments()
 # ---------------------------------------------------------------------------
@@ -382,52 +477,18 @@ def bench_aligner(ctx, key, steps, warmup, args, with_cpu):
     paths, plen = b.raw_paths()
     if ctx.rank != 0:
         return None
-    from oracle import oracle
+    if args.dump_outputs:
+        # the alignments' states as sync_alignments left them (emitted end -> start)
+        dump_outputs(args.dump_outputs, {"paths": paths, "path_lengths": plen}, {"paths": plen}, fill=-1)
     cells = sum(len(q) * len(t) for q, t in zip(qs, ts))
     alg_bytes = sum(aligner_alg_bytes(cfg["algorithm"], q, t) for q, t in zip(qs, ts))
-    k = min(8 if L <= 20000 else 1, n)
+    parity = aligner_parity(cfg, recipe, qs, ts, paths, plen, mq) if args.full else None
     algo = ALIGNER_ALGOS[cfg["algorithm"]][0]
-    gold = golden_long(recipe, L, cfg["algorithm"]) if recipe else None
-    if gold is not None:
-        # the first pair against tests/golden/aligner_long.json (oracle output,
-        # make_aligner_long.py): a 100 kb oracle run takes ~40 s
-        import hashlib
-        p0 = paths[0, :plen[0]][::-1].tobytes()
-        ok = int(plen[0]) == gold["path_length"] and hashlib.sha256(p0).hexdigest() == gold["path_sha256"]
-        parity = {"pairs_checked": 1, "bit_exact_vs_oracle": bool(ok),
-                  "pinned_by": "tests/golden/aligner_long.json: " + gold["name"]}
-    else:
-        ok = all(paths[i, :plen[i]][::-1].tolist() == oracle.align(qs[i], ts[i], algo, mq) for i in range(k))
-        parity = {"pairs_checked": k, "bit_exact_vs_oracle": bool(ok)}
-    # size-independent check over every pair: a global alignment consumes the
-    # whole query (match/mismatch + deletion) and the whole target (match/
-    # mismatch + insertion; cudaaligner.hpp:46-52)
-    R = paths.shape[1]
-    live = np.arange(R)[None, :] < plen[:, None]
-    mm = (((paths == 0) | (paths == 1)) & live).sum(1)
-    parity["all_pairs_consume_query_and_target"] = bool(
-        np.all(mm + ((paths == 3) & live).sum(1) == np.array([len(q) for q in qs])) and
-        np.all(mm + ((paths == 2) & live).sum(1) == np.array([len(t) for t in ts])))
-    kb = min(1000, n)
-    bases_ok = True
-    for i in range(kb):
-        p = paths[i, :plen[i]][::-1]
-        qi = np.cumsum((p == 0) | (p == 1) | (p == 3)) - 1
-        ti = np.cumsum((p == 0) | (p == 1) | (p == 2)) - 1
-        qb = np.frombuffer(qs[i], np.uint8)
-        tb = np.frombuffer(ts[i], np.uint8)
-        m, x = p == 0, p == 1
-        bases_ok = bases_ok and bool(np.all(qb[qi[m]] == tb[ti[m]]) and np.all(qb[qi[x]] != tb[ti[x]]))
-    parity["pairs_match_states_on_equal_bases"] = {"pairs": kb, "ok": bases_ok}
-    if cfg["algorithm"] == "myers_banded":
-        # not an invariant of the reference's banded backtrace: its neighbour
-        # scores at the band edges (myers_gpu.cu:377-494) can label unequal
-        # bases as a match on long pairs; the oracle restatement does the same
-        parity["pairs_match_states_on_equal_bases"]["invariant"] = False
     cpu = None
     if with_cpu:  # rank 0, after the timed region, at every GPU count
         th = cpu_threads()
         ns = args.cpu_sample or min(n, max(th * 12, 64) if L <= 20000 else th)
+        from oracle import oracle
         tc = time.perf_counter()
         cres, used = oracle.align_batch(list(zip(qs[:ns], ts[:ns])), algo, mq, th)
         cpu_s = time.perf_counter() - tc
@@ -525,12 +586,28 @@ def bench_poa(ctx, key, steps, warmup, args, with_cpu):
         evs[k][0].record(stream)
         batch.launch()
         evs[k][1].record(stream)
-        fetch()  # get_consensus(): blocks, D2H, result vectors
+        last = fetch()  # get_consensus(): blocks, D2H, result vectors
     torch.cuda.synchronize()
     ctx.barrier()
     wall = time.perf_counter() - t_start
     kernel_ms = float(np.mean([a.elapsed_time(e) for a, e in evs]))
     wall_max = ctx.max_over_ranks(wall)
+    if args.dump_outputs and ctx.rank == 0:
+        # what the last timed get_msa() / get_consensus() returned
+        if msa:
+            rows = [strings_to_rows(r) for r in last[0]]
+            width = max(r.shape[1] for r in rows)
+            arr = np.zeros((nwin, cfg["reads"], width), np.uint8)
+            for w, r in enumerate(rows):
+                arr[w, :r.shape[0], :r.shape[1]] = r
+            dump_outputs(args.dump_outputs, {"msa": arr, "status": np.array(last[1], np.int32)})
+        else:
+            st, ln, cbase, vbase, stride = last
+            raw_c = np.ctypeslib.as_array((ctypes.c_uint8 * (nwin * stride)).from_address(cbase))
+            raw_v = np.ctypeslib.as_array((ctypes.c_uint16 * (nwin * stride)).from_address(vbase))
+            dump_outputs(args.dump_outputs, {"consensus": raw_c.reshape(nwin, stride),
+                                             "coverage": raw_v.reshape(nwin, stride), "lengths": ln, "status": st},
+                         {"consensus": ln, "coverage": ln})
 
     # outputs + work counters (outside the timed region)
     if msa:
@@ -558,31 +635,34 @@ def bench_poa(ctx, key, steps, warmup, args, with_cpu):
     if ctx.rank != 0:
         return None
 
-    from oracle import oracle
+    if args.full or with_cpu:
+        from oracle import oracle
     mn = ((4 if cfg["banded"] else 3) * cfg["max_seq"] + 3) // 4 * 4
-    k = min(4, nwin)
-    ok = True
-    for i in range(k):
-        r = oracle.poa_window(windows[i], banded=cfg["banded"], band_width=cfg["bw"], score_bits=score_bits,
-                              max_nodes=mn, max_consensus=2 * cfg["max_seq"], max_seqs=cfg["reads"], msa=msa)
+    parity = {"all_windows_status_ok": n_ok == nwin}
+    if args.full:
+        k = min(4, nwin)
+        ok = True
+        for i in range(k):
+            r = oracle.poa_window(windows[i], banded=cfg["banded"], band_width=cfg["bw"], score_bits=score_bits,
+                                  max_nodes=mn, max_consensus=2 * cfg["max_seq"], max_seqs=cfg["reads"], msa=msa)
+            if msa:
+                ok = ok and (r.status == status[i] and (r.msa or []) == msa_rows[i])
+            else:
+                ok = ok and (r.status == status[i] and r.consensus == cons[i] and r.coverage == cov[i])
+        parity.update({"windows_checked": k, "bit_exact_vs_oracle": bool(ok)})
         if msa:
-            ok = ok and (r.status == status[i] and (r.msa or []) == msa_rows[i])
+            # MSA rows de-gapped are the window's reads (Test_CudapoaGenerateMSA2.cu:125-140)
+            parity["all_msa_rows_degap_to_reads"] = bool(all(
+                [row.replace("-", "") for row in msa_rows[i]] == [r.decode() for r in windows[i]] for i in range(nwin)))
+            parity["pinned_by"] = ("banded + MSA: the reference holds no banded or MSA known-answer vector; parity is "
+                                   "HIP == IEEE-division oracle restatement (SURVEY 8(c) gap (i)), plus the de-gap "
+                                   "property above")
         else:
-            ok = ok and (r.status == status[i] and r.consensus == cons[i] and r.coverage == cov[i])
-    parity = {"windows_checked": k, "bit_exact_vs_oracle": bool(ok), "all_windows_status_ok": n_ok == nwin}
-    if msa:
-        # MSA rows de-gapped are the window's reads (Test_CudapoaGenerateMSA2.cu:125-140)
-        parity["all_msa_rows_degap_to_reads"] = bool(all(
-            [row.replace("-", "") for row in msa_rows[i]] == [r.decode() for r in windows[i]] for i in range(nwin)))
-        parity["pinned_by"] = ("banded + MSA: the reference holds no banded or MSA known-answer vector; parity is "
-                               "HIP == IEEE-division oracle restatement (SURVEY 8(c) gap (i)), plus the de-gap "
-                               "property above")
-    else:
-        parity["all_coverage_lengths_match"] = bool(all(len(cov[i]) == len(cons[i]) and len(cons[i]) > 0
-                                                        for i in range(nwin)))
-        if cfg["banded"]:
-            parity["pinned_by"] = ("banded: no reference banded known-answer vector; parity is HIP == IEEE-division "
-                                   "oracle restatement (SURVEY 8(c) gap (i))")
+            parity["all_coverage_lengths_match"] = bool(all(len(cov[i]) == len(cons[i]) and len(cons[i]) > 0
+                                                            for i in range(nwin)))
+            if cfg["banded"]:
+                parity["pinned_by"] = ("banded: no reference banded known-answer vector; parity is HIP == "
+                                       "IEEE-division oracle restatement (SURVEY 8(c) gap (i))")
     cpu = None
     if with_cpu:  # rank 0, after the timed region, at every GPU count
         th = cpu_threads()
@@ -784,6 +864,10 @@ def bench_stream(ctx, key, steps, warmup, args, with_cpu):
         gather_ms = (time.perf_counter() - tg) * 1e3
     if ctx.rank != 0:
         return None
+    if args.dump_outputs:
+        # the rows process_packed filled for this rank's windows (the stream is one timed call)
+        dump_outputs(args.dump_outputs, {"consensus": cons, "coverage": cov, "lengths": clen, "status": status},
+                     {"consensus": clen, "coverage": clen})
     parity = {"all_windows_status_ok": n_ok == nwin}
     if gathered is not None:
         glen = gathered[:, :4].copy().view(np.int32).ravel()
@@ -812,37 +896,38 @@ def bench_stream(ctx, key, steps, warmup, args, with_cpu):
                            "parallelism": "dp%d (windows sharded, gloo gather)" % ctx.world},
                 "roofline": None, "cpu_baseline": cpu, "parity": parity}
 
-    # oracle check of a sample spread over the rank's stream (windows from every
-    # batch round) and, at N > 1, of windows the other ranks computed
-    from oracle import oracle
-    starts = np.concatenate([[0], np.cumsum(read_lens)])
+    if args.full:
+        # oracle check of a sample spread over the rank's stream (windows from every
+        # batch round) and, at N > 1, of windows the other ranks computed
+        from oracle import oracle
+        starts = np.concatenate([[0], np.cumsum(read_lens)])
 
-    def window_reads(i):
-        r0 = i * cfg["reads"]
-        return [bases[starts[r]:starts[r + 1]].tobytes() for r in range(r0, r0 + cfg["reads"])]
+        def window_reads(i):
+            r0 = i * cfg["reads"]
+            return [bases[starts[r]:starts[r + 1]].tobytes() for r in range(r0, r0 + cfg["reads"])]
 
-    idx = sorted(set(np.linspace(0, nwin - 1, 12).astype(int).tolist()))
-    mn = 3 * cfg["max_seq"]
-    rcons, rst, rcov, _, used = oracle.poa_batch([window_reads(i) for i in idx], nthreads=cpu_threads(),
-                                                 max_nodes=mn, max_consensus=2 * cfg["max_seq"],
-                                                 max_seqs=cfg["reads"], coverage=True)
-    ok = all(rst[j] == status[i] and rcons[j] == cons[i, :clen[i]].tobytes().decode() and
-             list(rcov[j]) == cov[i, :clen[i]].tolist() for j, i in enumerate(idx))
-    parity.update({"windows_checked": len(idx), "bit_exact_vs_oracle": bool(ok)})
-    if gathered is not None:
-        # two windows of every other rank, regenerated here from their seeds
-        gidx = [r * nwin + k for r in range(1, ctx.world) for k in (0, nwin - 1)]
-        wins = []
-        for g in gidx:
-            b1, l1 = synth.poa_windows_packed(1 + g, 1, cfg["backbone"], cfg["reads"], cfg["err"], cfg["err"],
-                                              cfg["err"])
-            wins.append(windows_from_packed(b1, l1)[0])
-        gc, gs, gv, _, _ = oracle.poa_batch(wins, nthreads=cpu_threads(), max_nodes=mn,
-                                            max_consensus=2 * cfg["max_seq"], max_seqs=cfg["reads"], coverage=True)
-        parity["gathered_other_ranks_checked"] = len(gidx)
-        parity["gathered_other_ranks_bit_exact_vs_oracle"] = bool(all(
-            gs[j] == gst[g] and gc[j] == gcons[g, :glen[g]].tobytes().decode() and
-            list(gv[j]) == gcov[g, :glen[g]].tolist() for j, g in enumerate(gidx)))
+        idx = sorted(set(np.linspace(0, nwin - 1, 12).astype(int).tolist()))
+        mn = 3 * cfg["max_seq"]
+        rcons, rst, rcov, _, used = oracle.poa_batch([window_reads(i) for i in idx], nthreads=cpu_threads(),
+                                                     max_nodes=mn, max_consensus=2 * cfg["max_seq"],
+                                                     max_seqs=cfg["reads"], coverage=True)
+        ok = all(rst[j] == status[i] and rcons[j] == cons[i, :clen[i]].tobytes().decode() and
+                 list(rcov[j]) == cov[i, :clen[i]].tolist() for j, i in enumerate(idx))
+        parity.update({"windows_checked": len(idx), "bit_exact_vs_oracle": bool(ok)})
+        if gathered is not None:
+            # two windows of every other rank, regenerated here from their seeds
+            gidx = [r * nwin + k for r in range(1, ctx.world) for k in (0, nwin - 1)]
+            wins = []
+            for g in gidx:
+                b1, l1 = synth.poa_windows_packed(1 + g, 1, cfg["backbone"], cfg["reads"], cfg["err"], cfg["err"],
+                                                  cfg["err"])
+                wins.append(windows_from_packed(b1, l1)[0])
+            gc, gs, gv, _, _ = oracle.poa_batch(wins, nthreads=cpu_threads(), max_nodes=mn,
+                                                max_consensus=2 * cfg["max_seq"], max_seqs=cfg["reads"], coverage=True)
+            parity["gathered_other_ranks_checked"] = len(gidx)
+            parity["gathered_other_ranks_bit_exact_vs_oracle"] = bool(all(
+                gs[j] == gst[g] and gc[j] == gcons[g, :glen[g]].tobytes().decode() and
+                list(gv[j]) == gcov[g, :glen[g]].tolist() for j, g in enumerate(gidx)))
 
     # roofline of the streamed kernels: SURVEY 8(d) priced bytes of every launch
     # (4 B per int16 DP cell + inputs + outputs) over the time the GPU ran at
@@ -953,13 +1038,19 @@ def main():
     key = args.config or ("B" if ctx.world == 1 else "E")
     if ctx.dry and key != "E":
         raise SystemExit("--dry-run rehearses config E only")
-    line = RUNNERS[key](ctx, key, args.steps, args.warmup, args, not args.no_cpu)
-    if default and ctx.world == 1 and not args.no_secondary and not ctx.dry:
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    with_cpu = args.full and not args.no_cpu
+    line = RUNNERS[key](ctx, key, args.steps, args.warmup, args, with_cpu)
+    if args.full and default and ctx.world == 1 and not args.no_secondary and not ctx.dry:
         # the metric's second half, the MSA config and the streaming driver, in the same run
+        args.dump_outputs = None  # the dump is the headline config's
         sec = {}
-        sec["D"] = bench_aligner(ctx, "D", max(1, args.secondary_steps), 1, args, not args.no_cpu)
-        sec["C"] = bench_poa(ctx, "C", max(1, args.secondary_c_steps), 1, args, not args.no_cpu)
-        sec["E"] = bench_stream(ctx, "E", args.steps, min(args.warmup, 1), args, not args.no_cpu)
+        sec["D"] = bench_aligner(ctx, "D", max(1, args.secondary_steps), 1, args, with_cpu)
+        sec["C"] = bench_poa(ctx, "C", max(1, args.secondary_c_steps), 1, args, with_cpu)
+        # E streams steps x 6,250 windows in one call: capped, so that a long headline run keeps E's job size
+        sec["E"] = bench_stream(ctx, "E", min(args.steps, args.secondary_e_steps), min(args.warmup, 1), args,
+                                with_cpu)
         if line is not None:
             line["secondary"] = sec
     if ctx.rank == 0 and line is not None:

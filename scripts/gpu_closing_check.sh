@@ -19,12 +19,12 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 if [ -z "$SKIP_BENCH" ]; then
   step "bench default"
-  timeout -k 10 500 python bench.py > $OUT/bench_default.log 2>&1 || { tail -20 $OUT/bench_default.log; exit 1; }
+  timeout -k 10 500 python bench.py --full > $OUT/bench_default.log 2>&1 || { tail -20 $OUT/bench_default.log; exit 1; }
   tail -c 600 $OUT/bench_default.log
 fi
 for C in $EXTRA; do
   step "bench $C"
-  timeout -k 10 400 python bench.py --config $C --steps 3 --warmup 1 > $OUT/bench_$C.log 2>&1 || { tail -20 $OUT/bench_$C.log; exit 1; }
+  timeout -k 10 400 python bench.py --full --config $C --steps 3 --warmup 1 > $OUT/bench_$C.log 2>&1 || { tail -20 $OUT/bench_$C.log; exit 1; }
 done
 for C in ${PROFILE-B C D}; do
   step "profile $C"

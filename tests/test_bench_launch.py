@@ -29,7 +29,7 @@ def _run(args, timeout=300):
 
 def test_gpus_2_launches_two_ranks_and_gathers_both():
     steps, per_step = 2, 5
-    line = _run(["--gpus", "2", "--dry-run", "--steps", str(steps), "--warmup", "0",
+    line = _run(["--gpus", "2", "--dry-run", "--full", "--steps", str(steps), "--warmup", "0",
                  "--stream-step-windows", str(per_step)])
     per_rank = steps * per_step
     assert line["dry_run"] is True and line["value"] is None
@@ -40,8 +40,8 @@ def test_gpus_2_launches_two_ranks_and_gathers_both():
     assert par["gathered_rows_equal_expected"] is True
     assert par["gathered_rank0_rows_equal_local"] is True
     assert par["gathered_all_status_ok"] is True
-    # the N > 1 line carries the CPU leg (rank 0, after the GPU region) with a
-    # per-core rate, and names its like-for-like N = 1 point
+    # with --full the N > 1 line carries the CPU leg (rank 0, after the GPU
+    # region) with a per-core rate, and names its like-for-like N = 1 point
     cpu = line["cpu_baseline"]
     assert cpu is not None and cpu["value"] > 0 and cpu["unit"] == "windows/s"
     assert cpu["value_per_core"] > 0 and cpu["cores"] >= 1
@@ -53,6 +53,8 @@ def test_gpus_3_uneven_world():
     assert line["n_gpus"] == 3
     assert line["parity"]["gathered_windows"] == 12
     assert line["parity"]["gathered_rows_equal_expected"] is True
+    # a plain run leaves the CPU leg to --full
+    assert line["cpu_baseline"] is None
 
 
 def test_dry_run_rejects_other_configs():
@@ -77,3 +79,34 @@ def test_dry_rows_are_seed_functions():
     b = bench.dry_rows(6, 5, 64)
     for x, y in zip(a, b):
         assert np.array_equal(x[5:], y)
+
+
+def test_dump_outputs_small(tmp_path):
+    # under the size limit: every row, float32, cells past a row's length zeroed
+    import bench
+    cons = np.arange(1, 13, dtype=np.uint8).reshape(3, 4)
+    lens = np.array([4, 2, 0], np.int32)
+    bench.dump_outputs(str(tmp_path), {"consensus": cons, "lengths": lens}, {"consensus": lens})
+    got = np.load(tmp_path / "consensus.npy")
+    assert got.dtype == np.float32
+    assert got.tolist() == [[1, 2, 3, 4], [5, 6, 0, 0], [0, 0, 0, 0]]
+    assert np.load(tmp_path / "lengths.npy").tolist() == [4, 2, 0]
+    assert np.load(tmp_path / "rows.npy").tolist() == [0, 1, 2]
+
+
+def test_dump_outputs_samples_large(tmp_path, monkeypatch):
+    # over the limit: the same seeded rows in every array and in every run
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    a = np.arange(200 * 16, dtype=np.int32).reshape(200, 16)
+    b = np.arange(200, dtype=np.int32)
+    d1, d2 = tmp_path / "one", tmp_path / "two"
+    bench.dump_outputs(str(d1), {"a": a, "b": b})
+    bench.dump_outputs(str(d2), {"a": a, "b": b})
+    rows = np.load(d1 / "rows.npy").astype(int)
+    assert 0 < len(rows) < 200 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(d1 / "a.npy"), a[rows]) and np.array_equal(np.load(d1 / "b.npy"), b[rows])
+    total = sum(f.stat().st_size for f in d1.iterdir())
+    assert total <= 4096 + 3 * 128
+    for name in ("rows", "a", "b"):
+        assert np.array_equal(np.load(d1 / (name + ".npy")), np.load(d2 / (name + ".npy")))

@@ -742,15 +742,23 @@ public:
     // kernel on the round-3 forward pass (GWAMD_POA_FWD=v1, A/B runs); bit 2
     // keeps the LDS and banded kernels on the FIFO Kahn sort instead of the
     // level-keyed one (GWAMD_TOPSORT=fifo, cross-check tests and A/B runs);
-    // bit 3 keeps the MSA's racon sort on the round-5 DFS step (GWAMD_RACON=v1)
+    // bit 3 keeps the MSA's racon sort on the round-5 DFS step (GWAMD_RACON=v1);
+    // bit 4 keeps the consensus on lane 0 in HBM (GWAMD_CONSENSUS=hbm, parity
+    // tests and A/B runs); bits 16-31 cap the LDS bytes offered to the
+    // wave-wide consensus (GWAMD_CONSENSUS_LDS_BYTES, 1..65535: tests push
+    // small graphs over the fit limit)
     static int diag_bits()
     {
         const char* r = gwamd::host::diag_env("GWAMD_TOPSORT_RING");
         const char* f = gwamd::host::diag_env("GWAMD_POA_FWD");
         const char* t = gwamd::host::diag_env("GWAMD_TOPSORT");
         const char* d = gwamd::host::diag_env("GWAMD_RACON");
+        const char* c = gwamd::host::diag_env("GWAMD_CONSENSUS");
+        const char* b = gwamd::host::diag_env("GWAMD_CONSENSUS_LDS_BYTES");
+        const int cap = b ? std::min(std::max(std::atoi(b), 1), 65535) : 0;
         return ((r && std::atoi(r) != 0) ? 1 : 0) | ((f && std::string(f) == "v1") ? 2 : 0) |
-               ((t && std::string(t) == "fifo") ? 4 : 0) | ((d && std::string(d) == "v1") ? 8 : 0);
+               ((t && std::string(t) == "fifo") ? 4 : 0) | ((d && std::string(d) == "v1") ? 8 : 0) |
+               ((c && std::string(c) == "hbm") ? 16 : 0) | int(uint32_t(cap) << 16);
     }
     static int tb_walk_bits()
     {

@@ -101,7 +101,8 @@ struct Dims
     int32_t tb_rank;        // traceback move windows (TbWin): bit 0 pointer-doubling walk, bit 1 strips, bit 2 32 x 4 strips
     int32_t diag;           // diagnostic switches (GWAMD_DIAG=1 only): bit 0 Kahn sort queued words in a ring,
                             // bit 1 LDS kernel on the round-3 forward pass, bit 2 FIFO Kahn sort,
-                            // bit 3 round-5 racon DFS step for the MSA
+                            // bit 3 round-5 racon DFS step for the MSA, bit 4 consensus by lane 0 in HBM,
+                            // bits 16-31 cap on the LDS bytes offered to the consensus (0: none)
 };
 
 // LDS bytes of the pointer-doubling traceback walk (walk_window_ranked)

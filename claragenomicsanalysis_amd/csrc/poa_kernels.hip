@@ -1402,8 +1402,8 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
     }
     if (wave == 0)
     {
-        finish_window<SizeT, MSA>(b, d, w, lane, g, status, nseq, node_count, cscore, cpred, ecov, ecovc, seq_begin,
-                                  sh_len, sh_status, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off);
+        finish_window<SizeT, MSA, NW>(b, d, w, lane, g, status, nseq, node_count, cscore, cpred, ecov, ecovc,
+                                      seq_begin, sh_len, sh_status, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off);
         ph.lap<kPhOutput>();
         if (lane == 0)
         {
@@ -1692,8 +1692,159 @@ int topsort_racon_test(int n, const uint16_t* in_cnt, const int32_t* in_e, const
     return fin(out[0]);
 }
 
+// Test hook: the consensus of one graph by one wave, as finish_window runs it
+// (consensus_window: the LDS path when the graph fits `scratch` bytes, else
+// consensus_raw on lane 0).
+template <typename SizeT>
+__global__ void __launch_bounds__(64) consensus_test_kernel(WinGraph<SizeT> g, int n, int scratch, int force_hbm,
+                                                           int32_t* cscore, SizeT* cpred, uint8_t* cons,
+                                                           uint16_t* cov, int max_cons, int* out)
+{
+    extern __shared__ __align__(16) uint8_t lds[];
+    __shared__ int sh[2];
+    int len = 0, st = kSuccess;
+    const int path = consensus_window<SizeT>(g, n, cscore, cpred, cons, cov, max_cons, (GWAMD_LDS uint8_t*)(lds),
+                                             scratch, force_hbm != 0, int(threadIdx.x), sh[0], sh[1], len, st);
+    if (threadIdx.x == 0)
+    {
+        if (len < max_cons)
+            cons[len] = 0;
+        out[0] = st;
+        out[1] = len;
+        out[2] = path;
+    }
+}
+
+template <typename SizeT>
+int consensus_test(int n, const uint8_t* base, const int32_t* sorted, const int32_t* pos, const uint16_t* in_cnt,
+                   const int32_t* in_e, const uint16_t* in_w, const uint16_t* out_cnt, const int32_t* out_e,
+                   const uint16_t* aln_cnt, const int32_t* aln, const uint16_t* cov, int max_cons, int force_hbm,
+                   int scratch, int* status, int* len, uint8_t* cons_out, uint16_t* cov_out)
+{
+    if (n <= 0 || n > 32767 || max_cons <= 0 || scratch < 0 || scratch > 163840 - 64)
+        return -2;
+    const size_t ne = size_t(n) * kMaxEdges, na = size_t(n) * kMaxAlignments;
+    std::vector<SizeT> ie(ne), oe(ne), al(na), so(n), po(n);
+    for (size_t i = 0; i < ne; i++)
+    {
+        ie[i] = SizeT(in_e[i]);
+        oe[i] = SizeT(out_e[i]);
+    }
+    for (size_t i = 0; i < na; i++)
+        al[i] = SizeT(aln[i]);
+    for (int q = 0; q < n; q++)
+    {
+        so[q] = SizeT(sorted[q]);
+        po[q] = SizeT(pos[q]);
+    }
+    uint8_t *d_base = nullptr, *d_cons = nullptr;
+    uint16_t *d_ic = nullptr, *d_oc = nullptr, *d_ac = nullptr, *d_cv = nullptr, *d_iw = nullptr, *d_ccov = nullptr;
+    SizeT *d_ie = nullptr, *d_oe = nullptr, *d_al = nullptr, *d_sorted = nullptr, *d_pos = nullptr, *d_cpred = nullptr;
+    int32_t* d_cscore = nullptr;
+    int* d_out        = nullptr;
+    auto fin          = [&](int r) {
+        (void)hipFree(d_base);
+        (void)hipFree(d_cons);
+        (void)hipFree(d_ic);
+        (void)hipFree(d_oc);
+        (void)hipFree(d_ac);
+        (void)hipFree(d_cv);
+        (void)hipFree(d_iw);
+        (void)hipFree(d_ccov);
+        (void)hipFree(d_ie);
+        (void)hipFree(d_oe);
+        (void)hipFree(d_al);
+        (void)hipFree(d_sorted);
+        (void)hipFree(d_pos);
+        (void)hipFree(d_cpred);
+        (void)hipFree(d_cscore);
+        (void)hipFree(d_out);
+        return r;
+    };
+    const size_t mc = size_t(max_cons);
+    if (hipMalloc(&d_base, n) || hipMalloc(&d_cons, mc + 1) || hipMalloc(&d_ic, n * 2) || hipMalloc(&d_oc, n * 2) ||
+        hipMalloc(&d_ac, n * 2) || hipMalloc(&d_cv, n * 2) || hipMalloc(&d_iw, ne * 2) ||
+        hipMalloc(&d_ccov, (mc + 1) * 2) || hipMalloc(&d_ie, ne * sizeof(SizeT)) ||
+        hipMalloc(&d_oe, ne * sizeof(SizeT)) || hipMalloc(&d_al, na * sizeof(SizeT)) ||
+        hipMalloc(&d_sorted, n * sizeof(SizeT)) || hipMalloc(&d_pos, n * sizeof(SizeT)) ||
+        hipMalloc(&d_cpred, n * sizeof(SizeT)) || hipMalloc(&d_cscore, n * 4) || hipMalloc(&d_out, 3 * sizeof(int)))
+        return fin(-1);
+    if (hipMemcpy(d_base, base, n, hipMemcpyHostToDevice) || hipMemcpy(d_ic, in_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oc, out_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ac, aln_cnt, n * 2, hipMemcpyHostToDevice) || hipMemcpy(d_cv, cov, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_iw, in_w, ne * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ie, ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oe, oe.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_al, al.data(), na * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_sorted, so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_pos, po.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) || hipMemset(d_cons, 0, mc + 1) ||
+        hipMemset(d_ccov, 0, (mc + 1) * 2))
+        return fin(-1);
+    WinGraph<SizeT> g{};
+    g.base      = d_base;
+    g.in_cnt    = d_ic;
+    g.out_cnt   = d_oc;
+    g.aln_cnt   = d_ac;
+    g.cov       = d_cv;
+    g.in_w      = d_iw;
+    g.in_e      = d_ie;
+    g.out_e     = d_oe;
+    g.aln       = d_al;
+    g.sorted    = d_sorted;
+    g.pos       = d_pos;
+    g.max_nodes = n;
+    // (at least one LDS word, so the kernel's dynamic array exists)
+    const int lds_bytes = std::max(scratch, 16);
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&consensus_test_kernel<SizeT>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes))
+        return fin(-1);
+    hipLaunchKernelGGL(consensus_test_kernel<SizeT>, dim3(1), dim3(64), size_t(lds_bytes), 0, g, n, scratch, force_hbm,
+                       d_cscore, d_cpred, d_cons, d_ccov, max_cons, d_out);
+    int out[3] = {0, 0, 0};
+    if (hipGetLastError() || hipDeviceSynchronize() || hipMemcpy(out, d_out, sizeof(out), hipMemcpyDeviceToHost) ||
+        hipMemcpy(cons_out, d_cons, mc, hipMemcpyDeviceToHost) ||
+        hipMemcpy(cov_out, d_ccov, mc * 2, hipMemcpyDeviceToHost))
+        return fin(-1);
+    *status = out[0];
+    *len    = out[1];
+    return fin(out[2]);
+}
+
 } // namespace poa
 } // namespace gwamd
+
+// Test hook (tests/test_poa_consensus.py): the consensus of one graph given as
+// the reference's fixed-slot arrays (kMaxEdges / kMaxAlignments slots per
+// node), by one wave with `scratch` bytes of LDS offered to the wave-wide path
+// (consensus_lds); force_hbm keeps consensus_raw.  cons_out / cov_out hold
+// max_cons entries and receive the consensus in host order.  Returns 1 when
+// the LDS path ran, 0 for the HBM path, negative on a HIP error or bad
+// arguments.
+extern "C" int gwamd_internal_consensus(int size_bits, int n, const uint8_t* base, const int32_t* sorted,
+                                        const int32_t* pos, const uint16_t* in_cnt, const int32_t* in_e,
+                                        const uint16_t* in_w, const uint16_t* out_cnt, const int32_t* out_e,
+                                        const uint16_t* aln_cnt, const int32_t* aln, const uint16_t* cov, int max_cons,
+                                        int force_hbm, int scratch, int* status, int* len, uint8_t* cons_out,
+                                        uint16_t* cov_out)
+{
+    if (size_bits == 16)
+        return gwamd::poa::consensus_test<int16_t>(n, base, sorted, pos, in_cnt, in_e, in_w, out_cnt, out_e, aln_cnt,
+                                                   aln, cov, max_cons, force_hbm, scratch, status, len, cons_out,
+                                                   cov_out);
+    return gwamd::poa::consensus_test<int32_t>(n, base, sorted, pos, in_cnt, in_e, in_w, out_cnt, out_e, aln_cnt, aln,
+                                               cov, max_cons, force_hbm, scratch, status, len, cons_out, cov_out);
+}
+
+// The fit rule of the wave-wide consensus: LDS bytes of the compact graph of
+// n nodes and m in-edges, and whether it runs with `scratch` bytes offered.
+extern "C" long long gwamd_internal_consensus_lds_bytes(int n, int m)
+{
+    return gwamd::poa::consensus_lds_bytes(n, m);
+}
+extern "C" int gwamd_internal_consensus_lds_fits(int n, int m, int scratch)
+{
+    return gwamd::poa::consensus_lds_fits(n, m, scratch) ? 1 : 0;
+}
 
 // Test hook (tests/test_poa_topsort.py, scripts/racon_bench.py): the racon
 // DFS sort (cudapoa_topsort.cuh:94-189) of one graph given as fixed-slot

@@ -15,6 +15,8 @@
 #define GWAMD_LDS __attribute__((address_space(3)))
 #define GWAMD_GLB __attribute__((address_space(1)))
 
+#include "poa_consensus.hpp"
+
 namespace gwamd
 {
 namespace poa
@@ -75,8 +77,10 @@ __device__ __forceinline__ bool topsort_racon_lds(WinGraph<SizeT> g, int n, GWAM
 
 // Consensus and/or MSA of one finished window (cudapoa_generate_consensus.cuh:
 // 279-347, cudapoa_generate_msa.cuh:121-224).  scratch: free LDS of the
-// workgroup for the MSA's racon sort (nullptr: the lane-0 sort in HBM).
-template <typename SizeT, bool MSA>
+// workgroup for the consensus (poa_consensus.hpp; scratch_bytes 0: lane 0 in
+// HBM) and the MSA's racon sort (nullptr: the lane-0 sort in HBM).  kInst:
+// the instantiation of the out-of-line consensus_lds.
+template <typename SizeT, bool MSA, int kInst = 0>
 __device__ __forceinline__ void finish_window(const Buffers& b, const Dims& d, int w, int lane, WinGraph<SizeT> g, int status,
                               int nseq, int node_count, int32_t* cscore, SizeT* cpred, uint16_t* ecov,
                               uint16_t* ecovc, SizeT* seq_begin, int& sh_len, int& sh_status,
@@ -95,37 +99,23 @@ __device__ __forceinline__ void finish_window(const Buffers& b, const Dims& d, i
     if (!MSA || d.want_consensus)
     {
         uint16_t* cov_out = b.cov + size_t(w) * d.max_consensus;
-        if (lane == 0)
+        // by the wave on a compact copy of the graph in the free LDS when it
+        // fits (poa_consensus.hpp), else by lane 0 in HBM.  Dims::diag bit 4
+        // (GWAMD_CONSENSUS=hbm) keeps the HBM path, bits 16-31
+        // (GWAMD_CONSENSUS_LDS_BYTES) cap the LDS bytes offered
+        int len = 0;
+        int cst = graph_status;
+        if (cst == kSuccess && nseq > 0)
         {
-            int len = 0;
-            int cst = graph_status;
-            if (cst == kSuccess && nseq > 0)
-            {
-                int r = consensus_raw<SizeT>(g, node_count, cscore, cpred, cons_out, cov_out, d.max_consensus);
-                if (r < 0)
-                    cst = -r;
-                else
-                    len = r;
-            }
-            sh_len    = len;
-            sh_status = cst;
-        }
-        wave_sync();
-        const int len = sh_len;
-        // reverse in place to host order (cudapoa_batch.cuh:241-246 does this on the host)
-        for (int k = lane; k < len / 2; k += kWave)
-        {
-            uint8_t c0  = cons_out[k];
-            uint8_t c1  = cons_out[len - 1 - k];
-            uint16_t v0 = cov_out[k];
-            uint16_t v1 = cov_out[len - 1 - k];
-            cons_out[k] = c1, cons_out[len - 1 - k] = c0;
-            cov_out[k] = v1, cov_out[len - 1 - k] = v0;
+            const int cap = (d.diag >> 16) & 0xffff;
+            consensus_window<SizeT, kInst>(g, node_count, cscore, cpred, cons_out, cov_out, d.max_consensus, scratch,
+                                    cap ? min(cap, scratch_bytes) : scratch_bytes, (d.diag & 16) != 0, lane, sh_len,
+                                    sh_status, len, cst);
         }
         if (lane == 0)
         {
             b.cons_len[w] = len;
-            b.status[w]   = uint8_t(sh_status);
+            b.status[w]   = uint8_t(cst);
             if (len < d.max_consensus)
                 cons_out[len] = 0;
         }

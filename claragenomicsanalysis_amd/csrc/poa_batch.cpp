@@ -611,26 +611,32 @@ private:
     // predecessor lists | shared words; the topological sort reuses everything
     // below the shared words.  Span carries of multi-sweep reads live in HBM
     // next to the traceback codes.
-    void plan_lds_kernel()
+    void plan_lds_kernel() { plan_lds_layout(dims_, banded_, size_bits_, score_bits_); }
+
+public:
+    // ... as a function of the capacities in `dims` alone (and the diagnostic
+    // environment), so that the plan can be examined without a device
+    // (gwamd_internal_poa_lds_add_plan)
+    static void plan_lds_layout(gwamd::poa::Dims& dims, bool banded, int size_bits, int score_bits)
     {
-        dims_.lds_kernel = 0;
+        dims.lds_kernel = 0;
         const char* env  = gwamd::host::diag_env("GWAMD_POA_KERNEL");
         if (env && std::string(env) == "v1")
             return;
         // 16-bit node ids; 16-bit scores, or 32-bit ones (the reference's
         // use32bitScore batches: nw_forward_lds_w)
-        if (banded_ || size_bits_ != 16 || (score_bits_ != 16 && score_bits_ != 32))
+        if (banded || size_bits != 16 || (score_bits != 16 && score_bits != 32))
             return;
-        const bool wide      = score_bits_ == 32;
+        const bool wide      = score_bits == 32;
         auto a16             = [](int64_t v) { return (v + 15) & ~int64_t(15); };
         int ring_rows        = 8;
-        const int64_t read_b = a16(int64_t(dims_.max_seq_len) + 48);
+        const int64_t read_b = gwamd::poa::lds_read_bytes(dims.max_seq_len);
         // forward pass shape: CPL columns per lane on NW waves; a sweep covers
         // NW*64*CPL read columns, longer reads take several sweeps
         // (GWAMD_POA_LDS_SHAPE="cpl,waves").  32-bit scores: one sweep up to
         // 4,096 columns (8 waves), 8,192 with 16 columns per lane
         int cpl = 8, nw = 1;
-        const int ms = dims_.max_seq_len;
+        const int ms = dims.max_seq_len;
         if (!wide && ms > 512)
             nw = 2;
         if (wide)
@@ -653,12 +659,16 @@ private:
             }
         }
         const int ebytes     = wide ? 4 : 2;
-        const int64_t add_b  = 5 * a16(dims_.max_seq_len + 16) + 2 * (int64_t(dims_.max_nodes) + dims_.max_seq_len);
+        // the one-wave graph update's scratch always fits the ring region
+        // (this is lds_add_wave0_bytes rounded up); the every-wave update's
+        // larger one is not planned for: the kernel runs it where
+        // lds_add_fits(max_seq_len, max_nodes, lds_rec_off - lds_ring_off)
+        const int64_t add_b  = 5 * a16(dims.max_seq_len + 16) + 2 * (int64_t(dims.max_nodes) + dims.max_seq_len);
         const int64_t tile_b = int64_t(gwamd::poa::kTileRows) * gwamd::poa::kTileCols + gwamd::poa::kTbRankBytes;
-        const int64_t rec_b  = a16(int64_t(dims_.max_nodes + 2) * 4);
+        const int64_t rec_b  = a16(int64_t(dims.max_nodes + 2) * 4);
         const int64_t sh_b   = a16(wide ? gwamd::poa::kShBytesW(nw) : gwamd::poa::kShBytes(nw));
         auto ring_bytes      = [&](int rows) {
-            return a16(std::max<int64_t>({int64_t(rows) * dims_.score_stride * ebytes, tile_b, add_b}));
+            return a16(std::max<int64_t>({int64_t(rows) * dims.score_stride * ebytes, tile_b, add_b}));
         };
         int64_t ring_b       = ring_bytes(ring_rows);
         int64_t fixed        = read_b + ring_b + rec_b + sh_b;
@@ -696,23 +706,23 @@ private:
             total += a16(std::atoi(pad));
         if (total > (wide ? 163840 - 64 : 65536))
             return;
-        dims_.lds_kernel    = 1;
-        dims_.tb_rank       = tb_rank_default();
-        dims_.lds_ring_off  = int32_t(read_b);
-        dims_.lds_ring_rows = ring_rows;
-        dims_.lds_rec_off   = int32_t(read_b + ring_b);
-        dims_.lds_xl_off    = int32_t(read_b + ring_b + rec_b);
-        dims_.lds_xl_cap    = int32_t(xl_cap);
-        dims_.lds_sh_off    = int32_t(read_b + ring_b + rec_b + a16(xl_cap * 2));
-        dims_.lds_bytes     = int32_t(total);
-        dims_.lds_cpl       = cpl;
-        dims_.lds_waves     = nw;
-        dims_.code_stride   = int32_t(a16(int64_t(dims_.max_seq_len) + 48));
+        dims.lds_kernel    = 1;
+        dims.tb_rank       = tb_rank_default();
+        dims.lds_ring_off  = int32_t(read_b);
+        dims.lds_ring_rows = ring_rows;
+        dims.lds_rec_off   = int32_t(read_b + ring_b);
+        dims.lds_xl_off    = int32_t(read_b + ring_b + rec_b);
+        dims.lds_xl_cap    = int32_t(xl_cap);
+        dims.lds_sh_off    = int32_t(read_b + ring_b + rec_b + a16(xl_cap * 2));
+        dims.lds_bytes     = int32_t(total);
+        dims.lds_cpl       = cpl;
+        dims.lds_waves     = nw;
+        dims.code_stride   = int32_t(a16(int64_t(dims.max_seq_len) + 48));
         // HBM side buffer per window: traceback codes, span carries
-        const int64_t code_b = int64_t(dims_.score_rows) * dims_.code_stride;
-        const int64_t cr_b   = a16(int64_t(dims_.max_nodes + 2) * ebytes);
-        dims_.aux_carry_off  = int32_t(code_b);
-        dims_.aux_stride     = code_b + cr_b;
+        const int64_t code_b = int64_t(dims.score_rows) * dims.code_stride;
+        const int64_t cr_b   = a16(int64_t(dims.max_nodes + 2) * ebytes);
+        dims.aux_carry_off  = int32_t(code_b);
+        dims.aux_stride     = code_b + cr_b;
     }
 
     // Banded kernel (poa_window_kernel_band, poa_band.hip): band widths 128 to
@@ -746,7 +756,10 @@ public:
     // bit 4 keeps the consensus on lane 0 in HBM (GWAMD_CONSENSUS=hbm, parity
     // tests and A/B runs); bits 16-31 cap the LDS bytes offered to the
     // wave-wide consensus (GWAMD_CONSENSUS_LDS_BYTES, 1..65535: tests push
-    // small graphs over the fit limit)
+    // small graphs over the fit limit); bit 5 keeps the LDS kernel's graph
+    // update on wave 0 with one read position per lane (GWAMD_POA_ADD=wave0),
+    // bit 6 runs the sequential restatement on lane 0 for every read
+    // (GWAMD_POA_ADD=serial): parity tests and A/B runs
     static int diag_bits()
     {
         const char* r = gwamd::host::diag_env("GWAMD_TOPSORT_RING");
@@ -755,8 +768,10 @@ public:
         const char* d = gwamd::host::diag_env("GWAMD_RACON");
         const char* c = gwamd::host::diag_env("GWAMD_CONSENSUS");
         const char* b = gwamd::host::diag_env("GWAMD_CONSENSUS_LDS_BYTES");
+        const char* a = gwamd::host::diag_env("GWAMD_POA_ADD");
         const int cap = b ? std::min(std::max(std::atoi(b), 1), 65535) : 0;
-        return ((r && std::atoi(r) != 0) ? 1 : 0) | ((f && std::string(f) == "v1") ? 2 : 0) |
+        const int add = (a && std::string(a) == "wave0") ? 32 : ((a && std::string(a) == "serial") ? 64 : 0);
+        return add | ((r && std::atoi(r) != 0) ? 1 : 0) | ((f && std::string(f) == "v1") ? 2 : 0) |
                ((t && std::string(t) == "fifo") ? 4 : 0) | ((d && std::string(d) == "v1") ? 8 : 0) |
                ((c && std::string(c) == "hbm") ? 16 : 0) | int(uint32_t(cap) << 16);
     }
@@ -1520,6 +1535,50 @@ int32_t gwamd_poa_get_grid(const gwamd_poa_batch* batch, int32_t* slots, int32_t
     *slots    = batch->impl->slots();
     *resident = batch->impl->resident_slots();
     return 0;
+}
+
+// Test hooks (tests/test_poa_add_waves.py): the fit rule of the LDS kernel's
+// every-wave graph update (lds_add_bytes / lds_add_fits, poa_common.hpp), and
+// what the host's plan makes of it for a full-alignment batch of these
+// capacities without a device: returns the rule applied to the planned ring
+// region, as the kernel applies it (-1 when no LDS kernel is planned), and the
+// plan's ring region bytes, waves and LDS bytes.
+long long gwamd_internal_poa_lds_add_bytes(int32_t max_seq_len, int32_t max_nodes)
+{
+    return gwamd::poa::lds_add_bytes(max_seq_len, max_nodes);
+}
+
+int32_t gwamd_internal_poa_lds_add_fits(int32_t max_seq_len, int32_t max_nodes, int32_t ring_bytes)
+{
+    return gwamd::poa::lds_add_fits(max_seq_len, max_nodes, ring_bytes) ? 1 : 0;
+}
+
+int32_t gwamd_internal_poa_lds_add_plan(int32_t max_seq_len, int32_t max_nodes, int32_t score_bits,
+                                        int32_t* ring_bytes, int32_t* waves, int32_t* lds_bytes)
+{
+    gwamd::poa::Dims d{};
+    d.max_nodes    = max_nodes;
+    d.max_seq_len  = max_seq_len;
+    d.score_stride = int32_t((int64_t(max_seq_len) + 48 + 7) & ~int64_t(7));
+    d.score_rows   = max_nodes + 2;
+    try
+    {
+        claraparabricks::genomeworks::cudapoa::PoaBatch::plan_lds_layout(d, false, 16, score_bits);
+    }
+    catch (const std::exception& e)
+    {
+        gwamd::host::last_error() = e.what();
+        return -2;
+    }
+    if (!d.lds_kernel)
+        return -1;
+    if (ring_bytes)
+        *ring_bytes = d.lds_rec_off - d.lds_ring_off;
+    if (waves)
+        *waves = d.lds_waves;
+    if (lds_bytes)
+        *lds_bytes = d.lds_bytes;
+    return gwamd::poa::lds_add_fits(d.max_seq_len, d.max_nodes, d.lds_rec_off - d.lds_ring_off) ? 1 : 0;
 }
 
 static size_t query_free_memory(uint64_t given)

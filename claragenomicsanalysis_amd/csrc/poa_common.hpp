@@ -102,8 +102,43 @@ struct Dims
     int32_t diag;           // diagnostic switches (GWAMD_DIAG=1 only): bit 0 Kahn sort queued words in a ring,
                             // bit 1 LDS kernel on the round-3 forward pass, bit 2 FIFO Kahn sort,
                             // bit 3 round-5 racon DFS step for the MSA, bit 4 consensus by lane 0 in HBM,
-                            // bits 16-31 cap on the LDS bytes offered to the consensus (0: none)
+                            // bits 16-31 cap on the LDS bytes offered to the consensus (0: none),
+                            // bit 5 graph update on wave 0, one position per lane (GWAMD_POA_ADD=wave0),
+                            // bit 6 graph update by the sequential restatement on lane 0 (GWAMD_POA_ADD=serial)
 };
+
+// LDS kernel: bytes of the staged read at the start of the LDS image (the ring
+// region follows it).
+constexpr int64_t lds_read_bytes(int64_t max_seq_len) { return (max_seq_len + 48 + 15) & ~int64_t(15); }
+
+// Scratch of the LDS kernel's graph update (AddScratch) in the ring region,
+// which is free between a read's traceback and the next read's row program:
+// gid, curr (u16) and kind (u8) per read position, owner (u16) per node and
+// new node; the every-wave update (add_alignment_waves) also keeps hit and
+// ohit (u8 per read position) and kAddShBytes of control words behind them.
+// One layout for the host's plan (poa_batch.cpp) and the kernel.
+constexpr int kAddShBytes = 64; // conflict word, one error word per wave (up to 8)
+constexpr int64_t lds_add_ms(int64_t max_seq_len) { return (max_seq_len + 16) & ~int64_t(15); }
+constexpr int64_t lds_add_wave0_bytes(int64_t max_seq_len, int64_t max_nodes)
+{
+    return 5 * lds_add_ms(max_seq_len) + 2 * (max_nodes + max_seq_len);
+}
+constexpr int64_t lds_add_hit_off(int64_t max_seq_len, int64_t max_nodes)
+{
+    return (lds_add_wave0_bytes(max_seq_len, max_nodes) + 15) & ~int64_t(15);
+}
+constexpr int64_t lds_add_bytes(int64_t max_seq_len, int64_t max_nodes)
+{
+    return lds_add_hit_off(max_seq_len, max_nodes) + 2 * lds_add_ms(max_seq_len) + kAddShBytes;
+}
+// the every-wave update runs when its scratch fits the ring region of this
+// LDS shape (ring_bytes: Dims::lds_rec_off - Dims::lds_ring_off); node ids
+// and read positions are 16-bit fields
+constexpr bool lds_add_fits(int64_t max_seq_len, int64_t max_nodes, int64_t ring_bytes)
+{
+    return max_seq_len > 0 && max_nodes > 0 && max_nodes + max_seq_len < 65535 &&
+           lds_add_bytes(max_seq_len, max_nodes) <= ring_bytes;
+}
 
 // LDS bytes of the pointer-doubling traceback walk (walk_window_ranked)
 constexpr int kTbRankBytes = 7 * 144 + 128 * 4;

@@ -1169,10 +1169,11 @@ __device__ int traceback_codes(WinGraph<SizeT> g, const RowProg& P, int V, int L
 #include "poa_fwd_w.hpp"
 
 // LDS-resident POA kernel: one workgroup of NW waves per window.  The forward
-// pass, the traceback tile loads and the level-keyed topological sort use
-// every wave; the serial phases (graph update, consensus, MSA) run on wave 0
-// while the other waves wait at the next barrier.  W: 32-bit scores (nw_forward_lds_w, the
-// reference's use32bitScore batches), else 16-bit.  Two waves per window
+// pass, the graph update (add_alignment_waves) and the level-keyed
+// topological sort use every wave; the serial phases (row program, traceback,
+// consensus, MSA) run on wave 0 while the other waves wait at the next
+// barrier.  W: 32-bit scores (nw_forward_lds_w, the reference's
+// use32bitScore batches), else 16-bit.  Two waves per window
 // (config B: four windows per CU, two waves per SIMD) need the kernel within
 // 256 registers; it is (252 with the per-kernel level sort instance), and a
 // second launch bound of 2 to force it costs config B 4% (the traceback
@@ -1201,17 +1202,14 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
     uint8_t* tile    = lds + d.lds_ring_off; // traceback tiles reuse the ring
     const int rstride = d.score_stride;      // ring / spill row stride (elements)
     GWAMD_LDS uint8_t* shb = (GWAMD_LDS uint8_t*)(lds) + d.lds_sh_off;
-    AddScratch AX;
-    {
-        // add-alignment scratch lives in the ring region (free between reads)
-        GWAMD_LDS uint8_t* a = (GWAMD_LDS uint8_t*)(lds) + d.lds_ring_off;
-        const int ms         = (d.max_seq_len + 16) & ~15;
-        AX.gid               = (GWAMD_LDS uint16_t*)(a);
-        AX.curr              = (GWAMD_LDS uint16_t*)(a + 2 * ms);
-        AX.kind              = a + 4 * ms;
-        AX.owner             = (GWAMD_LDS uint16_t*)(a + 5 * ms);
-        AX.sh                = (GWAMD_LDS int*)(shb);
-    }
+    // add-alignment scratch lives in the ring region (free between reads)
+    const AddScratch AX = lds_add_scratch((GWAMD_LDS uint8_t*)(lds) + d.lds_ring_off, d.max_seq_len, d.max_nodes,
+                                          false, (GWAMD_LDS int*)(shb));
+    // graph update: 0 every wave (add_alignment_waves; when its scratch fits
+    // the ring region), 1 wave 0 with one position per lane, 2 the sequential
+    // restatement on lane 0 (Dims::diag bits 5 and 6, GWAMD_POA_ADD)
+    const bool add_fits = lds_add_fits(d.max_seq_len, d.max_nodes, d.lds_rec_off - d.lds_ring_off);
+    const int add_mode  = (d.diag & 64) ? 2 : (((d.diag & 32) || !add_fits) ? 1 : 0);
 
     for (int idx = blockIdx.x; idx < b.num_windows;)
     {
@@ -1332,11 +1330,38 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
                 status = kLoopCountExceeded;
                 break;
             }
+            // Graph update.  Workgroup barriers of this step, the same on every
+            // wave whatever the outcome (alen == -1 left the loop above on a
+            // value every wave read after a barrier, before any of them):
+            //   every-wave update: the barriers inside add_alignment_waves (8
+            //     when positions conflict, 9 on a node or edge limit, 12 on
+            //     success; each count is taken by the whole workgroup, see
+            //     there), then the two below;
+            //   conflict (0xff): lane 0 of wave 0 then runs the sequential
+            //     restatement inside the wave-0 block, which holds no barrier;
+            //     the other waves wait at the first of the two below;
+            //   one-wave and serial modes: the two below only.
+            // The status and node count go to the other waves through
+            // sh_status / sh_len between those two barriers; an error status
+            // (node limit included) leaves the read loop after the sort step's
+            // own two barriers, again on every wave.
+            int add_r = -1;
+            if (add_mode == 0)
+                add_r = add_alignment_waves<MSA, NW, NW + (W ? 16 : 0)>(lds_kernel_args(), w, int(slot), s, off,
+                                                                        node_count, alen, L,
+                                                                        (GWAMD_LDS uint8_t*)(lds));
             if (wave == 0)
             {
                 int nc = node_count;
-                int rc = add_alignment_parallel<SizeT, MSA>(g, nc, ag, ar, alen, L, lread, wts_g, s, ecov, ecovc,
-                                                             seq_begin, d.max_seqs, AX, lane);
+                int rc = -1;
+                if (add_mode == 0)
+                {
+                    nc = add_r >> 8;
+                    rc = (add_r & 0xff) == 0xff ? -1 : (add_r & 0xff);
+                }
+                else if (add_mode == 1)
+                    rc = add_alignment_parallel<SizeT, MSA>(g, nc, ag, ar, alen, L, lread, wts_g, s, ecov, ecovc,
+                                                            seq_begin, d.max_seqs, AX, lane);
                 if (rc < 0)
                 {
                     if (lane == 0)

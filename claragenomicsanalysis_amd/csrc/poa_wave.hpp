@@ -552,9 +552,10 @@ __device__ __forceinline__ int add_alignment_parallel(WinGraph<SizeT> g, int& no
 // The same add with kAU read positions per lane and pass and their graph
 // loads issued together (one HBM round trip per dependent level instead of one
 // per position): used by the banded kernel, whose windows are long (config C:
-// 10 kb reads, 21 ms of adds per window before); the LDS full-alignment kernel
-// keeps the one-position form (the batched one raises its register count and
-// slows its forward pass).  nwv > 1: the nwv waves of the workgroup run it
+// 10 kb reads, 21 ms of adds per window before), and by the LDS
+// full-alignment kernel through add_alignment_waves below, which keeps it out
+// of line (inlined there, it raised the kernel's register count and slowed its
+// forward pass).  nwv > 1: the nwv waves of the workgroup run it
 // together (wave wv; every wave calls it with the same arguments): the
 // order-free passes split the read positions among the waves and meet at
 // workgroup barriers; the new-node numbering and the new nodes' writes stay
@@ -939,6 +940,118 @@ __device__ __forceinline__ int add_alignment_parallel_batched(WinGraph<SizeT> g,
     bar();
     lap(7);
     return kSuccess;
+}
+
+// The add scratch of the LDS kernel in its ring region `a` (layout:
+// lds_add_* in poa_common.hpp).  waves: the every-wave update's arrays and
+// control words too (the one-wave update keeps its conflict word in `sh`).
+__device__ __forceinline__ AddScratch lds_add_scratch(GWAMD_LDS uint8_t* a, int max_seq_len, int max_nodes, bool waves,
+                                                      GWAMD_LDS int* sh)
+{
+    AddScratch X;
+    const int ms = int(lds_add_ms(max_seq_len));
+    X.gid        = (GWAMD_LDS uint16_t*)(a);
+    X.curr       = (GWAMD_LDS uint16_t*)(a + 2 * ms);
+    X.kind       = a + 4 * ms;
+    X.owner      = (GWAMD_LDS uint16_t*)(a + 5 * ms);
+    X.sh         = sh;
+    if (waves)
+    {
+        const int ho = int(lds_add_hit_off(max_seq_len, max_nodes));
+        X.hit        = a + ho;
+        X.ohit       = a + ho + ms;
+        X.sh         = (GWAMD_LDS int*)(a + ho + 2 * ms);
+    }
+    return X;
+}
+
+// The parameters of poa_window_kernel_lds as they lie in its kernarg segment
+// (by-value structs, each at its natural alignment: the layout of this
+// struct).  The kernel takes the segment's address itself
+// (lds_kernel_args(); the builtin gives a null pointer anywhere but in a
+// kernel) and hands it to routines kept out of line.
+struct LdsKernelArgs
+{
+    Buffers b;
+    Dims d;
+    Scores sc;
+};
+static_assert(alignof(Buffers) == 8 && sizeof(Buffers) % 8 == 0 && alignof(Dims) == 8 && sizeof(Dims) % 8 == 0 &&
+                  alignof(Scores) <= 8,
+              "LdsKernelArgs: the kernel's three by-value parameters follow each other without padding");
+typedef const __attribute__((address_space(4))) LdsKernelArgs* LdsKernelArgsPtr;
+__device__ __forceinline__ LdsKernelArgsPtr lds_kernel_args()
+{
+    return (LdsKernelArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
+// The graph update of the LDS kernel on every wave of its workgroup:
+// add_alignment_parallel_batched with wv = this wave, nwv = NW, on the scratch
+// of lds_add_scratch (the caller has checked the fit, lds_add_fits).  Every
+// thread of the workgroup calls it with the same arguments: window w, read s
+// of it (its weights at b.wts + wts_off), the alignment in the scratch slot's
+// ag / ar; `lds` is the start of the LDS image (the staged read).  Returns
+// (node count << 8) | status, status 0xff for the batched routine's -1
+// (conflicting positions: nothing was written, the caller runs the sequential
+// restatement); the status is the same on every wave, the node count is
+// wave 0's.
+// Workgroup barriers (NW > 1), the same sequence on every wave for a given
+// outcome, as every branch that leaves early is taken on LDS words read after
+// a barrier: conflict 8, node or edge limit 9, success 12.
+// Out of line, so that its registers are allocated apart from the calling
+// kernel's.  Only called from poa_window_kernel_lds: the batch's pointers and
+// capacities are read from that kernel's own kernarg segment `ka_` (scalar
+// loads) instead of being passed, so the call keeps nine values live, not the
+// graph's nine pointers and the rest (passed, they changed the register
+// allocation of the 32-bit forward pass: config F's forward phase 112 -> 118
+// ms per window).  kInst: one instantiation per calling kernel, as
+// topsort_levels.
+template <bool MSA, int NW, int kInst = 0>
+__device__ __noinline__ int add_alignment_waves(LdsKernelArgsPtr ka_, int w_, int slot_, int s_, int64_t wts_off,
+                                                int node_count, int alen, int L, GWAMD_LDS uint8_t* lds)
+{
+    using SizeT = int16_t;
+    // (arguments arrive in vector registers; the address is the same in every lane)
+    const uint64_t kav        = uint64_t(uintptr_t(ka_));
+    const LdsKernelArgsPtr ka = (LdsKernelArgsPtr)(uintptr_t(
+        (uint64_t(uint32_t(uniform(int(uint32_t(kav >> 32))))) << 32) | uint32_t(uniform(int(uint32_t(kav))))));
+    const int tid     = int(threadIdx.x);
+    const int lane    = tid & (kWave - 1);
+    const int wv      = NW > 1 ? uniform(tid / kWave) : 0;
+    const size_t w    = size_t(uniform(w_));
+    const size_t slot = size_t(uniform(slot_));
+    const int s       = uniform(s_);
+    const size_t mn   = size_t(ka->d.max_nodes);
+    const int max_seq_len = ka->d.max_seq_len;
+    const int max_seqs    = ka->d.max_seqs;
+    const int64_t woff    = (int64_t(uniform(int(wts_off >> 32))) << 32) | uint32_t(uniform(int(uint32_t(wts_off))));
+    WinGraph<SizeT> g;
+    g.base      = ka->b.base + w * mn;
+    g.in_cnt    = ka->b.in_cnt + w * mn;
+    g.out_cnt   = ka->b.out_cnt + w * mn;
+    g.aln_cnt   = ka->b.aln_cnt + w * mn;
+    g.cov       = ka->b.node_cov + w * mn;
+    g.in_w      = ka->b.in_w + w * mn * kMaxEdges;
+    g.in_e      = static_cast<SizeT*>(ka->b.in_e) + w * mn * kMaxEdges;
+    g.out_e     = static_cast<SizeT*>(ka->b.out_e) + w * mn * kMaxEdges;
+    g.aln       = static_cast<SizeT*>(ka->b.aln) + w * mn * kMaxAlignments;
+    g.sorted    = nullptr;
+    g.pos       = nullptr;
+    g.max_nodes = int(mn);
+    const SizeT* ag  = glb(static_cast<const SizeT*>(ka->b.ag) + slot * ka->d.aln_cap);
+    const SizeT* ar  = glb(static_cast<const SizeT*>(ka->b.ar) + slot * ka->d.aln_cap);
+    const int8_t* wt = glb(ka->b.wts + woff);
+    uint16_t* ecov   = MSA ? glb(ka->b.edge_cov + w * mn * kMaxEdges * max_seqs) : nullptr;
+    uint16_t* ecovc  = MSA ? glb(ka->b.edge_cov_cnt + w * mn * kMaxEdges) : nullptr;
+    SizeT* seq_begin = MSA ? glb(static_cast<SizeT*>(ka->b.seq_begin) + w * max_seqs) : nullptr;
+    lds              = (GWAMD_LDS uint8_t*)(uintptr_t)(uint32_t)uniform(int((uint32_t)(uintptr_t)lds));
+    const AddScratch X =
+        lds_add_scratch(lds + int(lds_read_bytes(max_seq_len)), max_seq_len, int(mn), true, nullptr);
+    int nc       = uniform(node_count);
+    const int rc = add_alignment_parallel_batched<SizeT, MSA, 4>(g, nc, ag, ar, uniform(alen), uniform(L),
+                                                                 (const uint8_t*)(lds), wt, s, ecov, ecovc,
+                                                                 seq_begin, max_seqs, X, lane, nullptr, wv, NW);
+    return (nc << 8) | (rc & 0xff);
 }
 
 // racon/SPOA DFS sort (cudapoa_topsort.cuh:94-189) by one wave with the node

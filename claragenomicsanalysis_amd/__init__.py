@@ -1,9 +1,11 @@
-"""MI355X-native batched POA consensus/MSA and global alignment.
+"""MI355X-native batched POA consensus/MSA, global alignment and cudamapper's
+minimizer index and anchor matcher.
 
 Python mirror of the reference's pygenomeworks bindings (genomeworks.cudapoa,
 genomeworks.cudaaligner) over the C ABI of libgwamd.so (include/*.h).  All
 compute runs in hand-written HIP kernels for gfx950; there is no CPU fallback.
 """
 from ._lib import load_library, library_path  # noqa: F401
+from .cudamapper import Index, match_anchors  # noqa: F401
 
-__all__ = ["load_library", "library_path"]
+__all__ = ["load_library", "library_path", "Index", "match_anchors"]

@@ -7,6 +7,7 @@
 #include <claraparabricks/genomeworks/cudaaligner/cudaaligner.hpp>
 
 #include "aligner_common.hpp"
+#include "allocator_handle.hpp"
 #include "gwamd_cudaaligner.h"
 #include "host_common.hpp"
 
@@ -1113,11 +1114,6 @@ int32_t guarded_aln(F&& f)
 struct gwamd_aligner
 {
     std::unique_ptr<ca::AlignerGlobalHip> impl;
-};
-
-struct gwamd_device_allocator
-{
-    claraparabricks::genomeworks::DefaultDeviceAllocator alloc;
 };
 
 extern "C" {

@@ -1,0 +1,373 @@
+// Host side of cudamapper's minimizer index and anchor matcher: the
+// reference's C++ API (Index::create_index, Matcher::create_matcher;
+// cudamapper/src/index.cu, matcher.cu) and the C ABI of
+// include/gwamd_cudamapper.h.  Device work is in mapper_index.hip and
+// mapper_match.hip.  Every argument is checked here, before any device call.
+#include <claraparabricks/genomeworks/cudamapper/index.hpp>
+#include <claraparabricks/genomeworks/cudamapper/matcher.hpp>
+
+#include "../../include/gwamd_cudamapper.h"
+#include "allocator_handle.hpp"
+#include "mapper_common.hpp"
+
+#include <cstring>
+#include <vector>
+
+namespace gm = gwamd::mapper;
+
+namespace
+{
+
+void check_index_arguments(int64_t num_reads, int64_t first_read_id, int64_t past_the_last_read_id, uint64_t kmer_size,
+                           uint64_t window_size, double filtering_parameter)
+{
+    if (kmer_size < 1 || kmer_size > uint64_t(gm::kMaxKmerSize))
+        throw std::invalid_argument("kmer_size must be between 1 and " + std::to_string(gm::kMaxKmerSize) + ", got " +
+                                    std::to_string(kmer_size));
+    if (window_size < 1 || window_size > uint64_t(gm::kMaxWindowSize))
+        throw std::invalid_argument("window_size must be between 1 and " + std::to_string(gm::kMaxWindowSize) +
+                                    ", got " + std::to_string(window_size));
+    if (!(filtering_parameter >= 0.0 && filtering_parameter <= 1.0))
+        throw std::invalid_argument("filtering_parameter must be between 0 and 1");
+    if (num_reads < 0 || first_read_id < 0 || first_read_id > past_the_last_read_id ||
+        past_the_last_read_id > num_reads)
+        throw std::invalid_argument("read range [" + std::to_string(first_read_id) + ", " +
+                                    std::to_string(past_the_last_read_id) + ") is not within the " +
+                                    std::to_string(num_reads) + " reads");
+}
+
+void check_read_lengths(const int64_t* offsets, int64_t n)
+{
+    for (int64_t i = 0; i < n; i++)
+    {
+        if (offsets[i] < 0 || offsets[i] > offsets[i + 1])
+            throw std::invalid_argument("read offsets must be non-decreasing");
+        // a position and the direction share 32 bits of the sort payload
+        if (offsets[i + 1] - offsets[i] >= (int64_t(1) << 31))
+            throw std::invalid_argument("reads must be shorter than 2^31 bases");
+    }
+}
+
+} // namespace
+
+namespace claraparabricks
+{
+namespace genomeworks
+{
+namespace cudamapper
+{
+namespace
+{
+
+class IndexHip : public Index
+{
+public:
+    using Direction = SketchElement::DirectionOfRepresentation;
+    static_assert(sizeof(Direction) == 1, "directions are stored as bytes");
+
+    gm::IndexData data;
+
+    void refresh_views()
+    {
+        representations_    = {data.representations.data(), std::ptrdiff_t(data.representations.size())};
+        read_ids_           = {data.read_ids.data(), std::ptrdiff_t(data.read_ids.size())};
+        positions_in_reads_ = {data.positions_in_reads.data(), std::ptrdiff_t(data.positions_in_reads.size())};
+        directions_         = {reinterpret_cast<Direction*>(data.directions_of_reads.data()),
+                       std::ptrdiff_t(data.directions_of_reads.size())};
+        unique_             = {data.unique_representations.data(), std::ptrdiff_t(data.unique_representations.size())};
+        first_occurrence_   = {data.first_occurrence_of_representations.data(),
+                             std::ptrdiff_t(data.first_occurrence_of_representations.size())};
+    }
+
+    const device_buffer<representation_t>& representations() const override { return representations_; }
+    const device_buffer<read_id_t>& read_ids() const override { return read_ids_; }
+    const device_buffer<position_in_read_t>& positions_in_reads() const override { return positions_in_reads_; }
+    const device_buffer<Direction>& directions_of_reads() const override { return directions_; }
+    const device_buffer<representation_t>& unique_representations() const override { return unique_; }
+    const device_buffer<std::uint32_t>& first_occurrence_of_representations() const override
+    {
+        return first_occurrence_;
+    }
+    read_id_t number_of_reads() const override { return data.number_of_reads; }
+    read_id_t smallest_read_id() const override { return data.smallest_read_id; }
+    read_id_t largest_read_id() const override { return data.largest_read_id; }
+    position_in_read_t number_of_basepairs_in_longest_read() const override
+    {
+        return data.number_of_basepairs_in_longest_read;
+    }
+
+private:
+    device_buffer<representation_t> representations_, unique_;
+    device_buffer<read_id_t> read_ids_;
+    device_buffer<position_in_read_t> positions_in_reads_;
+    device_buffer<Direction> directions_;
+    device_buffer<std::uint32_t> first_occurrence_;
+};
+
+class MatcherHip : public Matcher
+{
+public:
+    static_assert(sizeof(Anchor) == sizeof(gm::AnchorRecord), "Anchor is four u32");
+    gm::DevBuf<gm::AnchorRecord> data;
+    device_buffer<Anchor> view;
+    device_buffer<Anchor>& anchors() override { return view; }
+};
+
+std::unique_ptr<IndexHip> make_index(const char* bases, const int64_t* offsets, uint32_t first_read_id,
+                                     uint32_t num_reads, int kmer_size, int window_size, bool hash_representations,
+                                     double filtering_parameter, const gm::Budget& budget, hipStream_t stream)
+{
+    auto index = std::make_unique<IndexHip>();
+    if (num_reads > 0)
+    {
+        GWAMD_HIP_CHECK(hipGetDevice(&index->data.device_id));
+        gm::build_index(index->data, bases, offsets, first_read_id, num_reads, kmer_size, window_size,
+                        hash_representations, filtering_parameter, budget, stream);
+    }
+    index->refresh_views();
+    return index;
+}
+
+} // namespace
+
+std::unique_ptr<Index> Index::create_index(DefaultDeviceAllocator allocator, const io::FastaParser& parser,
+                                           const read_id_t first_read_id, const read_id_t past_the_last_read_id,
+                                           const std::uint64_t kmer_size, const std::uint64_t window_size,
+                                           const bool hash_representations, const double filtering_parameter,
+                                           const hipStream_t stream)
+{
+    check_index_arguments(parser.get_num_seqences(), first_read_id, past_the_last_read_id, kmer_size, window_size,
+                          filtering_parameter);
+    const uint32_t n = past_the_last_read_id - first_read_id;
+    std::vector<int64_t> offsets(size_t(n) + 1, 0);
+    for (uint32_t i = 0; i < n; i++)
+        offsets[i + 1] = offsets[i] + int64_t(parser.get_sequence_by_id(first_read_id + i).seq.size());
+    check_read_lengths(offsets.data(), n);
+    std::string bases;
+    bases.reserve(size_t(offsets[n]));
+    for (uint32_t i = 0; i < n; i++)
+        bases += parser.get_sequence_by_id(first_read_id + i).seq;
+    return make_index(bases.data(), offsets.data(), first_read_id, n, int(kmer_size), int(window_size),
+                      hash_representations, filtering_parameter, allocator.budget(), stream);
+}
+
+std::unique_ptr<Matcher> Matcher::create_matcher(DefaultDeviceAllocator allocator, const Index& query_index,
+                                                 const Index& target_index, const hipStream_t stream)
+{
+    const auto* q = dynamic_cast<const IndexHip*>(&query_index);
+    const auto* t = dynamic_cast<const IndexHip*>(&target_index);
+    if (!q || !t)
+        throw std::invalid_argument("create_matcher takes indices made by Index::create_index");
+    auto m = std::make_unique<MatcherHip>();
+    gm::match_anchors(m->data, q->data, t->data, gm::kDefaultMaxAnchors, allocator.budget(), stream);
+    m->view = {reinterpret_cast<Anchor*>(m->data.data()), std::ptrdiff_t(m->data.size())};
+    return m;
+}
+
+} // namespace cudamapper
+} // namespace genomeworks
+} // namespace claraparabricks
+
+// ---- C ABI ------------------------------------------------------------------
+
+namespace cm = claraparabricks::genomeworks::cudamapper;
+
+struct gwamd_index
+{
+    std::unique_ptr<cm::IndexHip> impl;
+};
+
+static_assert(sizeof(gwamd_anchor) == sizeof(gm::AnchorRecord), "gwamd_anchor must match cudamapper::Anchor");
+
+namespace
+{
+
+template <typename F>
+int32_t guarded_map(F&& f)
+{
+    try
+    {
+        gwamd::host::last_error().clear();
+        return f();
+    }
+    catch (const std::invalid_argument& e)
+    {
+        gwamd::host::last_error() = e.what();
+        return GWAMD_E_INVALID_ARGUMENT;
+    }
+    catch (const std::exception& e)
+    {
+        gwamd::host::last_error() = e.what();
+        return std::string(e.what()).rfind("HIP error", 0) == 0 ? GWAMD_E_HIP : GWAMD_E_RUNTIME;
+    }
+}
+
+int32_t index_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t first_read_id,
+                     int32_t past_the_last_read_id, int32_t kmer_size, int32_t window_size,
+                     int32_t hash_representations, double filtering_parameter, int32_t device_id,
+                     const gm::Budget& budget, gwamd_index** out)
+{
+    if (out)
+        *out = nullptr;
+    return guarded_map([&] {
+        if (!out)
+            throw std::invalid_argument("out is NULL");
+        if (kmer_size < 0 || window_size < 0)
+            throw std::invalid_argument("kmer_size and window_size must be positive");
+        check_index_arguments(num_reads, first_read_id, past_the_last_read_id, uint64_t(kmer_size),
+                              uint64_t(window_size), filtering_parameter);
+        if (num_reads > 0 && (!offsets || (!bases && offsets[num_reads] > 0)))
+            throw std::invalid_argument("bases or offsets is NULL");
+        if (device_id < 0)
+            throw std::invalid_argument("device_id must not be negative");
+        check_read_lengths(offsets, num_reads);
+        auto h           = std::make_unique<gwamd_index>();
+        const uint32_t n = uint32_t(past_the_last_read_id - first_read_id);
+        if (n == 0)
+        {
+            h->impl = std::make_unique<cm::IndexHip>();
+            h->impl->data.device_id = device_id;
+        }
+        else
+        {
+            gwamd::host::ScopedDevice dev(device_id);
+            h->impl = cm::make_index(bases, offsets + first_read_id, uint32_t(first_read_id), n, kmer_size,
+                                     window_size, hash_representations != 0, filtering_parameter, budget, nullptr);
+        }
+        *out = h.release();
+        return int32_t(0);
+    });
+}
+
+int32_t match(const gwamd_index* query_index, const gwamd_index* target_index, int64_t max_anchors,
+              const gm::Budget& budget, gwamd_anchor** anchors, int64_t* num_anchors)
+{
+    if (anchors)
+        *anchors = nullptr;
+    if (num_anchors)
+        *num_anchors = 0;
+    return guarded_map([&] {
+        if (!query_index || !target_index || !anchors || !num_anchors)
+            throw std::invalid_argument("index, anchors or num_anchors is NULL");
+        if (max_anchors < -1)
+            throw std::invalid_argument("max_anchors must be -1 (the default of 2^31) or not negative");
+        const gm::IndexData& q = query_index->impl->data;
+        const gm::IndexData& t = target_index->impl->data;
+        if (q.representations.size() == 0 || t.representations.size() == 0)
+            return int32_t(0);
+        if (q.device_id != t.device_id)
+            throw std::invalid_argument("the two indices are on different devices");
+        gwamd::host::ScopedDevice dev(q.device_id);
+        gm::DevBuf<gm::AnchorRecord> d;
+        gm::match_anchors(d, q, t, max_anchors < 0 ? gm::kDefaultMaxAnchors : max_anchors, budget, nullptr);
+        if (d.size() == 0)
+            return int32_t(0);
+        std::unique_ptr<gwamd_anchor[]> h(new gwamd_anchor[d.size()]);
+        GWAMD_HIP_CHECK(hipMemcpy(h.get(), d.data(), d.size() * sizeof(gwamd_anchor), hipMemcpyDeviceToHost));
+        *num_anchors = int64_t(d.size());
+        *anchors     = h.release();
+        return int32_t(0);
+    });
+}
+
+template <typename T>
+void copy_out(T* dst, const gm::DevBuf<T>& src)
+{
+    if (dst && src.size() > 0)
+        GWAMD_HIP_CHECK(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyDeviceToHost));
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t gwamd_index_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t first_read_id,
+                           int32_t past_the_last_read_id, int32_t kmer_size, int32_t window_size,
+                           int32_t hash_representations, double filtering_parameter, int32_t device_id,
+                           gwamd_index** out)
+{
+    return index_create(bases, offsets, num_reads, first_read_id, past_the_last_read_id, kmer_size, window_size,
+                        hash_representations, filtering_parameter, device_id, nullptr, out);
+}
+
+int32_t gwamd_index_create_with_allocator(const char* bases, const int64_t* offsets, int32_t num_reads,
+                                          int32_t first_read_id, int32_t past_the_last_read_id, int32_t kmer_size,
+                                          int32_t window_size, int32_t hash_representations,
+                                          double filtering_parameter, int32_t device_id,
+                                          gwamd_device_allocator* allocator, gwamd_index** out)
+{
+    if (!allocator)
+    {
+        if (out)
+            *out = nullptr;
+        gwamd::host::last_error() = "allocator is NULL";
+        return GWAMD_E_INVALID_ARGUMENT;
+    }
+    return index_create(bases, offsets, num_reads, first_read_id, past_the_last_read_id, kmer_size, window_size,
+                        hash_representations, filtering_parameter, device_id, allocator->alloc.budget(), out);
+}
+
+void gwamd_index_free(gwamd_index* index) { delete index; }
+
+int32_t gwamd_index_info(const gwamd_index* index, gwamd_index_info_t* info)
+{
+    return guarded_map([&] {
+        if (!index || !info)
+            throw std::invalid_argument("index or info is NULL");
+        const gm::IndexData& d                    = index->impl->data;
+        info->num_elements                        = int64_t(d.representations.size());
+        info->num_unique_representations          = int64_t(d.unique_representations.size());
+        info->number_of_reads                     = d.number_of_reads;
+        info->smallest_read_id                    = d.smallest_read_id;
+        info->largest_read_id                     = d.largest_read_id;
+        info->number_of_basepairs_in_longest_read = d.number_of_basepairs_in_longest_read;
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_index_copy(const gwamd_index* index, uint64_t* representations, uint32_t* read_ids,
+                         uint32_t* positions_in_reads, uint8_t* directions_of_reads,
+                         uint64_t* unique_representations, uint32_t* first_occurrence_of_representations)
+{
+    return guarded_map([&] {
+        if (!index)
+            throw std::invalid_argument("index is NULL");
+        const gm::IndexData& d = index->impl->data;
+        if (d.representations.size() == 0)
+            return int32_t(0);
+        gwamd::host::ScopedDevice dev(d.device_id);
+        copy_out(representations, d.representations);
+        copy_out(read_ids, d.read_ids);
+        copy_out(positions_in_reads, d.positions_in_reads);
+        copy_out(directions_of_reads, d.directions_of_reads);
+        copy_out(unique_representations, d.unique_representations);
+        copy_out(first_occurrence_of_representations, d.first_occurrence_of_representations);
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_match_anchors(const gwamd_index* query_index, const gwamd_index* target_index, int64_t max_anchors,
+                            gwamd_anchor** anchors, int64_t* num_anchors)
+{
+    return match(query_index, target_index, max_anchors, nullptr, anchors, num_anchors);
+}
+
+int32_t gwamd_match_anchors_with_allocator(const gwamd_index* query_index, const gwamd_index* target_index,
+                                           int64_t max_anchors, gwamd_device_allocator* allocator,
+                                           gwamd_anchor** anchors, int64_t* num_anchors)
+{
+    if (!allocator)
+    {
+        if (anchors)
+            *anchors = nullptr;
+        if (num_anchors)
+            *num_anchors = 0;
+        gwamd::host::last_error() = "allocator is NULL";
+        return GWAMD_E_INVALID_ARGUMENT;
+    }
+    return match(query_index, target_index, max_anchors, allocator->alloc.budget(), anchors, num_anchors);
+}
+
+void gwamd_anchors_free(gwamd_anchor* anchors) { delete[] anchors; }
+
+} // extern "C"

@@ -1,0 +1,137 @@
+// Host-side declarations shared by the minimizer index and the matcher
+// (mapper_index.hip, mapper_match.hip, mapper_batch.cpp).
+#pragma once
+
+#include <claraparabricks/genomeworks/utils/allocator.hpp>
+
+#include "host_common.hpp"
+
+#include <cstdint>
+#include <memory>
+#include <utility>
+
+namespace gwamd
+{
+namespace mapper
+{
+
+using Budget = std::shared_ptr<claraparabricks::genomeworks::DeviceBudget>;
+
+constexpr int kMaxKmerSize   = 32;  // 2 bits per base in a 64-bit representation
+constexpr int kMaxWindowSize = 255; // bounds the halo a sketch tile stages in LDS
+constexpr int64_t kDefaultMaxAnchors = int64_t(1) << 31;
+
+// Device array whose bytes are reserved from the caller's pool (null: no
+// pool) for its lifetime; freed and released on every path out of scope.
+template <typename T>
+class DevBuf
+{
+public:
+    DevBuf() = default;
+    DevBuf(size_t n, const Budget& budget) { alloc(n, budget); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { take(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o)
+        {
+            free();
+            take(o);
+        }
+        return *this;
+    }
+    ~DevBuf() { free(); }
+
+    void alloc(size_t n, const Budget& budget)
+    {
+        free();
+        if (n == 0)
+            return;
+        const int64_t bytes = int64_t(n * sizeof(T));
+        if (budget && budget->reserve(bytes, bytes) < 0)
+            throw std::runtime_error("Not enough memory left in the device allocator pool: " + std::to_string(bytes) +
+                                     " bytes asked, " + std::to_string(budget->capacity() - budget->used()) +
+                                     " of " + std::to_string(budget->capacity()) + " left.");
+        void* p            = nullptr;
+        const hipError_t e = hipMalloc(&p, size_t(bytes));
+        if (e != hipSuccess)
+        {
+            if (budget)
+                budget->release(bytes);
+            throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) + " at hipMalloc of " +
+                                     std::to_string(bytes) + " bytes");
+        }
+        p_      = static_cast<T*>(p);
+        n_      = n;
+        budget_ = budget;
+    }
+    void free()
+    {
+        if (!p_)
+            return;
+        (void)hipFree(p_);
+        if (budget_)
+            budget_->release(int64_t(n_ * sizeof(T)));
+        p_ = nullptr;
+        n_ = 0;
+        budget_.reset();
+    }
+    T* data() const { return p_; }
+    size_t size() const { return n_; }
+
+private:
+    void take(DevBuf& o)
+    {
+        p_      = o.p_;
+        n_      = o.n_;
+        budget_ = std::move(o.budget_);
+        o.p_    = nullptr;
+        o.n_    = 0;
+    }
+    T* p_     = nullptr;
+    size_t n_ = 0;
+    Budget budget_;
+};
+
+// cudamapper::Anchor (types.hpp), four u32
+struct AnchorRecord
+{
+    uint32_t query_read_id;
+    uint32_t target_read_id;
+    uint32_t query_position_in_read;
+    uint32_t target_position_in_read;
+};
+
+// The six device arrays of an index, ordered by (representation, read_id,
+// position_in_read), and its scalars.
+struct IndexData
+{
+    DevBuf<uint64_t> representations;
+    DevBuf<uint32_t> read_ids;
+    DevBuf<uint32_t> positions_in_reads;
+    DevBuf<uint8_t> directions_of_reads;
+    DevBuf<uint64_t> unique_representations;
+    DevBuf<uint32_t> first_occurrence_of_representations;
+    uint32_t number_of_reads                     = 0;
+    uint32_t smallest_read_id                    = 0;
+    uint32_t largest_read_id                     = 0;
+    uint32_t number_of_basepairs_in_longest_read = 0;
+    int device_id                                = 0;
+};
+
+// Index of the reads [first_read_id, first_read_id + num_reads): read i of the
+// range is bases[offsets[i], offsets[i + 1]) (host memory, offsets has
+// num_reads + 1 entries).  Arguments are validated by the caller.
+void build_index(IndexData& out, const char* bases, const int64_t* offsets, uint32_t first_read_id, uint32_t num_reads,
+                 int kmer_size, int window_size, bool hash_representations, double filtering_parameter,
+                 const Budget& budget, hipStream_t stream);
+
+// All (query element, target element) pairs of equal representation, sorted by
+// (query_read_id, target_read_id, query_position, target_position).  Throws
+// std::runtime_error when there are more than max_anchors.
+void match_anchors(DevBuf<AnchorRecord>& out, const IndexData& query, const IndexData& target, int64_t max_anchors,
+                   const Budget& budget, hipStream_t stream);
+
+} // namespace mapper
+} // namespace gwamd

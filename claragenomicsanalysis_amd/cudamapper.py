@@ -1,12 +1,19 @@
-"""Overlap alignment and PAF output of cudamapper over the C ABI
-(include/gwamd_cudamapper.h; reference cudamapper/src/main.cu:48-175 and
-cudamapper/src/cudamapper_utils.cpp:30-112).
+"""Minimizer index, anchor matcher, overlap alignment and PAF output of
+cudamapper over the C ABI (include/gwamd_cudamapper.h; reference
+cudamapper/include/.../index.hpp, matcher.hpp, cudamapper/src/main.cu:48-175
+and cudamapper/src/cudamapper_utils.cpp:30-112).
+
+Index builds the (k,w)-minimizer index of a range of reads on the GPU and
+match_anchors pairs the sketch elements of two indices that share a
+representation.
 
 Overlaps are aligned with the MI355X global aligner (Hirschberg-Myers, the
 aligner create_aligner returns); a Reverse ('-') overlap aligns the query
 region against the reverse complement of the target region.
 """
 import ctypes as C
+
+import numpy as np
 
 from ._lib import load_library, last_error
 
@@ -30,6 +37,20 @@ class Overlap(C.Structure):
         return chr(self.relative_strand)
 
 
+class IndexInfo(C.Structure):
+    """gwamd_index_info_t."""
+    _fields_ = [("num_elements", C.c_int64), ("num_unique_representations", C.c_int64),
+                ("number_of_reads", C.c_uint32), ("smallest_read_id", C.c_uint32),
+                ("largest_read_id", C.c_uint32), ("number_of_basepairs_in_longest_read", C.c_uint32)]
+
+
+# cudamapper::Anchor (types.hpp:52-62)
+ANCHOR_DTYPE = np.dtype([("query_read_id", np.uint32), ("target_read_id", np.uint32),
+                         ("query_position_in_read", np.uint32), ("target_position_in_read", np.uint32)])
+
+FORWARD, REVERSE = 0, 1  # SketchElement::DirectionOfRepresentation
+
+
 def _declare(L):
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     P = C.POINTER
@@ -47,6 +68,23 @@ def _declare(L):
     L.gwamd_text_list_get.argtypes = [vp, i32, P(C.c_void_p), P(i64)]
     L.gwamd_text_list_free.restype = None
     L.gwamd_text_list_free.argtypes = [vp]
+    index_args = [C.c_char_p, vp, i32, i32, i32, i32, i32, i32, C.c_double, i32]
+    L.gwamd_index_create.restype = i32
+    L.gwamd_index_create.argtypes = index_args + [P(vp)]
+    L.gwamd_index_create_with_allocator.restype = i32
+    L.gwamd_index_create_with_allocator.argtypes = index_args + [vp, P(vp)]
+    L.gwamd_index_free.restype = None
+    L.gwamd_index_free.argtypes = [vp]
+    L.gwamd_index_info.restype = i32
+    L.gwamd_index_info.argtypes = [vp, P(IndexInfo)]
+    L.gwamd_index_copy.restype = i32
+    L.gwamd_index_copy.argtypes = [vp] * 7
+    L.gwamd_match_anchors.restype = i32
+    L.gwamd_match_anchors.argtypes = [vp, vp, i64, P(vp), P(i64)]
+    L.gwamd_match_anchors_with_allocator.restype = i32
+    L.gwamd_match_anchors_with_allocator.argtypes = [vp, vp, i64, vp, P(vp), P(i64)]
+    L.gwamd_anchors_free.restype = None
+    L.gwamd_anchors_free.argtypes = [vp]
 
 
 def _check(rc):
@@ -137,3 +175,98 @@ def read_fasta(path, min_sequence_length=0, shuffle=True):
     _check(L.gwamd_read_fasta(str(path).encode(), int(min_sequence_length), int(bool(shuffle)), C.byref(n),
                               C.byref(s)))
     return list(zip(_take(L, n), _take(L, s)))
+
+
+class Index:
+    """(k,w)-minimizer index of reads[first_read_id:past_the_last_read_id]
+    (Index::create_index, index.hpp:97-106), built on the GPU.
+
+    reads: sequences (str or bytes), or (name, sequence) records as read_fasta
+    returns them.  The six arrays are numpy arrays ordered by (representation,
+    read_id, position_in_read); read ids are indices into reads.  A read
+    shorter than window_size + kmer_size - 1 contributes nothing and keeps its
+    id.  allocator: a cudaaligner.DeviceAllocator whose pool the device memory
+    is counted against."""
+
+    def __init__(self, reads, kmer_size, window_size, first_read_id=0, past_the_last_read_id=None,
+                 hash_representations=True, filtering_parameter=1.0, device_id=0, allocator=None):
+        self._lib = load_library()
+        self._handle = C.c_void_p()
+        seqs = [r[1] if isinstance(r, tuple) else r for r in reads]
+        if past_the_last_read_id is None:
+            past_the_last_read_id = len(seqs)
+        bases, offsets = _pack(seqs)
+        args = [bases, offsets, len(seqs), int(first_read_id), int(past_the_last_read_id), int(kmer_size),
+                int(window_size), int(bool(hash_representations)), float(filtering_parameter), int(device_id)]
+        if allocator is not None:
+            _check(self._lib.gwamd_index_create_with_allocator(*args, allocator._handle, C.byref(self._handle)))
+            self._allocator = allocator  # the index holds bytes of its pool
+        else:
+            _check(self._lib.gwamd_index_create(*args, C.byref(self._handle)))
+        try:
+            info = IndexInfo()
+            _check(self._lib.gwamd_index_info(self._handle, C.byref(info)))
+            n, u = info.num_elements, info.num_unique_representations
+            self.representations = np.empty(n, np.uint64)
+            self.read_ids = np.empty(n, np.uint32)
+            self.positions_in_reads = np.empty(n, np.uint32)
+            self.directions_of_reads = np.empty(n, np.uint8)
+            self.unique_representations = np.empty(u, np.uint64)
+            self.first_occurrence_of_representations = np.empty(u + 1 if n else 0, np.uint32)
+            _check(self._lib.gwamd_index_copy(
+                self._handle, *[a.ctypes.data_as(C.c_void_p) for a in (
+                    self.representations, self.read_ids, self.positions_in_reads, self.directions_of_reads,
+                    self.unique_representations, self.first_occurrence_of_representations)]))
+        except Exception:
+            self.close()
+            raise
+        self.number_of_reads = int(info.number_of_reads)
+        self.smallest_read_id = int(info.smallest_read_id)
+        self.largest_read_id = int(info.largest_read_id)
+        self.number_of_basepairs_in_longest_read = int(info.number_of_basepairs_in_longest_read)
+
+    def close(self):
+        """Frees the index's device memory; the numpy arrays stay valid."""
+        h, self._handle = self._handle, C.c_void_p()
+        if h:
+            self._lib.gwamd_index_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def match_anchors(query_index, target_index, max_anchors=None, allocator=None):
+    """Anchors of two indices (Matcher::create_matcher, matcher.hpp:45-48): a
+    structured numpy array (ANCHOR_DTYPE) of every pair of a query and a target
+    sketch element with the same representation, sorted by (query_read_id,
+    target_read_id, query_position_in_read, target_position_in_read).
+
+    RuntimeError when there are more than max_anchors (default 2^31)."""
+    L = load_library()
+    if not query_index._handle or not target_index._handle:
+        raise ValueError("index is closed")
+    p, n = C.c_void_p(), C.c_int64()
+    cap = -1 if max_anchors is None else int(max_anchors)
+    if cap < 0 and max_anchors is not None:
+        raise ValueError("max_anchors must not be negative")
+    if allocator is not None:
+        _check(L.gwamd_match_anchors_with_allocator(query_index._handle, target_index._handle, cap,
+                                                    allocator._handle, C.byref(p), C.byref(n)))
+    else:
+        _check(L.gwamd_match_anchors(query_index._handle, target_index._handle, cap, C.byref(p), C.byref(n)))
+    try:
+        out = np.empty(n.value, ANCHOR_DTYPE)
+        if n.value:
+            C.memmove(out.ctypes.data, p, n.value * ANCHOR_DTYPE.itemsize)
+        return out
+    finally:
+        L.gwamd_anchors_free(p)

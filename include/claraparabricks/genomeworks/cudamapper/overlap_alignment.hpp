@@ -1,7 +1,7 @@
 // The cudamapper caller of the global aligner: base-level alignment of overlap
 // regions and PAF output (reference cudamapper/src/main.cu:48-175,
-// cudamapper/src/cudamapper_utils.cpp:30-112).  The rest of cudamapper
-// (indexing, matching, overlapping) is outside this build.
+// cudamapper/src/cudamapper_utils.cpp:30-112).  Indexing and matching are in
+// index.hpp and matcher.hpp; chaining anchors into overlaps is outside this build.
 #pragma once
 
 #include <claraparabricks/genomeworks/cudamapper/types.hpp>

@@ -1,5 +1,6 @@
 /*
- * gwamd_cudamapper.h -- C ABI of the overlap-alignment caller (libgwamd.so).
+ * gwamd_cudamapper.h -- C ABI of cudamapper's minimizer index, anchor matcher
+ * and overlap-alignment caller (libgwamd.so).
  *
  * The reference aligns cudamapper overlaps inside its cudamapper executable
  * (cudamapper/src/main.cu:48-175: run_alignment_batch / align_overlaps) and
@@ -11,6 +12,10 @@
  *   gwamd_read_fasta       io::create_kseq_fasta_parser(path, min_len, shuffle) fasta_parser.hpp:62-64
  *   gwamd_format_paf       print_paf(overlaps, cigars, query_parser,
  *                          target_parser, kmer_size, mutex)                cudamapper_utils.cpp:30-112
+ *   gwamd_index_create     Index::create_index(allocator, parser, first, past,
+ *                          kmer_size, window_size, hash, filtering)        index.hpp:97-106
+ *   gwamd_match_anchors    Matcher::create_matcher(allocator, query_index,
+ *                          target_index)->anchors()                        matcher.hpp:45-48
  *
  * Reads are passed as one byte array per side with n+1 offsets (read i is
  * bases[offsets[i], offsets[i+1])); names as NUL-separated strings with n+1
@@ -80,6 +85,73 @@ int32_t gwamd_text_list_create(const char* const* texts, const int64_t* lengths,
 int32_t gwamd_text_list_size(const gwamd_text_list* list);
 int32_t gwamd_text_list_get(const gwamd_text_list* list, int32_t i, const char** text, int64_t* length);
 void gwamd_text_list_free(gwamd_text_list* list);
+
+/* ---- (k,w)-minimizer index and anchor matcher -------------------------------
+ *
+ * The index of the reads [first_read_id, past_the_last_read_id) of the given
+ * reads holds one sketch element per distinct window minimizer, ordered by
+ * (representation, read_id, position_in_read).  A read shorter than
+ * window_size + kmer_size - 1 contributes nothing but keeps its id (the
+ * reference shifts the ids of the reads after it, index_gpu.cuh:720-734).
+ * Limits, each GWAMD_E_INVALID_ARGUMENT before any device call:
+ * 1 <= kmer_size <= 32, 1 <= window_size <= 255, 0 <= filtering_parameter <= 1,
+ * 0 <= first_read_id <= past_the_last_read_id <= num_reads, reads shorter than
+ * 2^31 bases.  An index holds fewer than 2^32 sketch elements and a match at
+ * most max_anchors anchors (GWAMD_E_RUNTIME beyond). */
+typedef struct gwamd_index gwamd_index;
+struct gwamd_device_allocator; /* the pool handle of gwamd_cudaaligner.h (gwamd_device_allocator_create) */
+
+/* cudamapper::Anchor (types.hpp:52-62) */
+typedef struct gwamd_anchor
+{
+    uint32_t query_read_id;
+    uint32_t target_read_id;
+    uint32_t query_position_in_read;
+    uint32_t target_position_in_read;
+} gwamd_anchor;
+
+typedef struct gwamd_index_info_t
+{
+    int64_t num_elements;
+    int64_t num_unique_representations;
+    uint32_t number_of_reads; /* past - first, or 0 when no read is long enough */
+    uint32_t smallest_read_id;
+    uint32_t largest_read_id;
+    uint32_t number_of_basepairs_in_longest_read;
+} gwamd_index_info_t;
+
+int32_t gwamd_index_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t first_read_id,
+                           int32_t past_the_last_read_id, int32_t kmer_size, int32_t window_size,
+                           int32_t hash_representations, double filtering_parameter, int32_t device_id,
+                           gwamd_index** out);
+/* ... with every device byte (the index's arrays for its lifetime, scratch
+ * while it is built) counted against the allocator's pool */
+int32_t gwamd_index_create_with_allocator(const char* bases, const int64_t* offsets, int32_t num_reads,
+                                          int32_t first_read_id, int32_t past_the_last_read_id, int32_t kmer_size,
+                                          int32_t window_size, int32_t hash_representations,
+                                          double filtering_parameter, int32_t device_id,
+                                          struct gwamd_device_allocator* allocator, gwamd_index** out);
+void gwamd_index_free(gwamd_index* index);
+int32_t gwamd_index_info(const gwamd_index* index, gwamd_index_info_t* info);
+/* Copies the arrays to host buffers sized by gwamd_index_info (num_elements
+ * for the first four, num_unique_representations for the fifth and, unless
+ * the index is empty, one more than that for the last).  A NULL pointer skips
+ * its array. */
+int32_t gwamd_index_copy(const gwamd_index* index, uint64_t* representations, uint32_t* read_ids,
+                         uint32_t* positions_in_reads, uint8_t* directions_of_reads,
+                         uint64_t* unique_representations, uint32_t* first_occurrence_of_representations);
+
+/* All pairs of a query and a target sketch element of equal representation,
+ * sorted by (query_read_id, target_read_id, query_position_in_read,
+ * target_position_in_read), in a host array owned by the library (free with
+ * gwamd_anchors_free; NULL when there are none).  The two indices may be the
+ * same; self-matches are kept.  max_anchors: -1 for the default of 2^31. */
+int32_t gwamd_match_anchors(const gwamd_index* query_index, const gwamd_index* target_index, int64_t max_anchors,
+                            gwamd_anchor** anchors, int64_t* num_anchors);
+int32_t gwamd_match_anchors_with_allocator(const gwamd_index* query_index, const gwamd_index* target_index,
+                                           int64_t max_anchors, struct gwamd_device_allocator* allocator,
+                                           gwamd_anchor** anchors, int64_t* num_anchors);
+void gwamd_anchors_free(gwamd_anchor* anchors);
 
 #ifdef __cplusplus
 }

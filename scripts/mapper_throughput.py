@@ -1,0 +1,177 @@
+#!/usr/bin/env python
+"""Throughput of the minimizer index and the anchor matcher on one GPU.
+
+Builds the index of 2,000 synthetic 10 kb reads at (k,w) = (15,10), hashed,
+filtering_parameter 0.001, and matches it against itself.  The reads are
+substrings of one random 2 Mb genome (10x coverage, every second one reverse
+complemented), so the reads share minimizers and the anchor count is bounded
+by the coverage.  Prints one JSON line with bases/s for the index and
+anchors/s for the matcher, then checks a 16-read subset against the
+plain-Python model (tests/mapper_model.py).
+
+Each GPU step (index, match, verify) runs in a child process of its own under
+a time limit; a step that fails or runs out of time ends the run.  The timed
+calls are gwamd_index_create and gwamd_match_anchors (upload, kernels and, for
+the matcher, the copy of the anchors to the host), timed with device events
+on the stream the library works on and with the host clock.
+
+    python scripts/mapper_throughput.py [--reads 2000] [--length 10000] [--steps 5] [--warmup 2]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+K, W, FILTERING = 15, 10, 0.001
+STEP_TIMEOUT = {"index": 300, "match": 300, "verify": 300}
+
+
+def synthetic_reads(num_reads, length, seed=1):
+    rng = np.random.default_rng(seed)
+    genome_length = max(num_reads * length // 10, 2 * length)
+    letters = np.frombuffer(b"ACGT", np.uint8)
+    genome = rng.integers(0, 4, genome_length, dtype=np.uint8)
+    starts = rng.integers(0, genome_length - length, num_reads)
+    reads = []
+    for i, s in enumerate(starts):
+        codes = genome[s:s + length]
+        if i % 2:
+            codes = 3 - codes[::-1]
+        reads.append(letters[codes].tobytes())
+    return reads
+
+
+def pack(reads):
+    offsets = (C.c_int64 * (len(reads) + 1))()
+    for i, r in enumerate(reads):
+        offsets[i + 1] = offsets[i] + len(r)
+    return b"".join(reads), offsets
+
+
+class Timer:
+    """Device-event and host-clock time of one synchronous library call."""
+
+    def __init__(self):
+        import torch
+        self.torch = torch
+        torch.cuda.init()
+
+    def run(self, fn):
+        torch = self.torch
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        start.record(torch.cuda.default_stream())
+        fn()
+        stop.record(torch.cuda.default_stream())
+        stop.synchronize()
+        return start.elapsed_time(stop) * 1e-3, time.perf_counter() - t0
+
+
+def create_index(L, bases, offsets, n):
+    h = C.c_void_p()
+    rc = L.gwamd_index_create(bases, offsets, n, 0, n, K, W, 1, FILTERING, 0, C.byref(h))
+    if rc != 0:
+        raise RuntimeError(L.gwamd_last_error().decode())
+    return h
+
+
+def worker(args):
+    import torch  # noqa: F401  (before libgwamd, so that both share one HIP runtime)
+    from claragenomicsanalysis_amd import load_library
+    from claragenomicsanalysis_amd.cudamapper import IndexInfo
+    L = load_library()
+    reads = synthetic_reads(args.reads, args.length)
+    if args.worker == "verify":
+        import mapper_model as model
+        from claragenomicsanalysis_amd import Index, match_anchors
+        subset = reads[:16]
+        expected = model.Index(subset, K, W, filtering_parameter=FILTERING)
+        with Index(subset, K, W, filtering_parameter=FILTERING) as idx:
+            for name in ("representations", "read_ids", "positions_in_reads", "directions_of_reads",
+                         "unique_representations", "first_occurrence_of_representations"):
+                assert getattr(idx, name).tolist() == getattr(expected, name), name
+            anchors = match_anchors(idx, idx)
+        want = model.match_anchors(expected, expected)
+        assert [tuple(int(x) for x in a) for a in anchors] == want
+        print(json.dumps({"verified_reads": len(subset), "verified_elements": len(expected.representations),
+                          "verified_anchors": len(want)}))
+        return
+    bases, offsets = pack(reads)
+    timer = Timer()
+    info = IndexInfo()
+    if args.worker == "index":
+        samples = []
+        for step in range(args.warmup + args.steps):
+            holder = []
+            ev, wall = timer.run(lambda: holder.append(create_index(L, bases, offsets, len(reads))))
+            L.gwamd_index_info(holder[0], C.byref(info))
+            L.gwamd_index_free(holder[0])
+            if step >= args.warmup:
+                samples.append((ev, wall))
+        ev = float(np.median([s[0] for s in samples]))
+        wall = float(np.median([s[1] for s in samples]))
+        print(json.dumps({"bases": len(bases), "elements": info.num_elements,
+                          "unique_representations": info.num_unique_representations,
+                          "index_event_s": round(ev, 6), "index_wall_s": round(wall, 6),
+                          "index_bases_per_s": round(len(bases) / ev, 1)}))
+    else:
+        h = create_index(L, bases, offsets, len(reads))
+        samples, n = [], C.c_int64()
+        for step in range(args.warmup + args.steps):
+            p = C.c_void_p()
+
+            def call():
+                rc = L.gwamd_match_anchors(h, h, -1, C.byref(p), C.byref(n))
+                if rc != 0:
+                    raise RuntimeError(L.gwamd_last_error().decode())
+            ev, wall = timer.run(call)
+            L.gwamd_anchors_free(p)
+            if step >= args.warmup:
+                samples.append((ev, wall))
+        L.gwamd_index_free(h)
+        ev = float(np.median([s[0] for s in samples]))
+        wall = float(np.median([s[1] for s in samples]))
+        print(json.dumps({"anchors": n.value, "match_event_s": round(ev, 6), "match_wall_s": round(wall, 6),
+                          "match_anchors_per_s": round(n.value / ev, 1)}))
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    p.add_argument("--reads", type=int, default=2000)
+    p.add_argument("--length", type=int, default=10000)
+    p.add_argument("--steps", type=int, default=5)
+    p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--no-verify", action="store_true")
+    p.add_argument("--worker", choices=sorted(STEP_TIMEOUT), default=None, help=argparse.SUPPRESS)
+    args = p.parse_args()
+    if args.worker:
+        worker(args)
+        return 0
+    result = {"metric": "mapper_throughput", "reads": args.reads, "read_length": args.length, "kmer_size": K,
+              "window_size": W, "hash_representations": True, "filtering_parameter": FILTERING,
+              "steps": args.steps, "warmup": args.warmup}
+    for step in ("index", "match") + (() if args.no_verify else ("verify",)):
+        cmd = [sys.executable, os.path.abspath(__file__), "--worker", step, "--reads", str(args.reads), "--length",
+               str(args.length), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+        try:
+            out = subprocess.run(cmd, timeout=STEP_TIMEOUT[step], stdout=subprocess.PIPE, check=True).stdout
+        except (subprocess.TimeoutExpired, subprocess.CalledProcessError) as e:
+            sys.stderr.write("mapper_throughput: step %s failed: %s\n" % (step, e))
+            return 1  # nothing more is started on the GPU
+        result.update(json.loads(out.decode().strip().splitlines()[-1]))
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,6 +1,8 @@
 // Host-side helpers shared by the POA batch and the aligner (C++ API + C ABI).
 #pragma once
 
+#include "diag_env.hpp"
+
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,18 +23,6 @@ namespace gwamd
 {
 namespace host
 {
-
-// Tuning and diagnostic switches (GWAMD_POA_KERNEL, GWAMD_TB_WALK,
-// GWAMD_BAND_FWD, ...): read only when GWAMD_DIAG=1 is set, so a drop-in
-// user's environment never changes which kernel runs.  The parity tests set
-// GWAMD_DIAG=1 (tests/conftest.py).  GWAMD_SPOA_ACCURATE is not one of them:
-// it is the runtime form of the reference's spoa_accurate build option.
-inline bool diag_enabled()
-{
-    const char* d = std::getenv("GWAMD_DIAG");
-    return d && d[0] == '1' && d[1] == '\0';
-}
-inline const char* diag_env(const char* name) { return diag_enabled() ? std::getenv(name) : nullptr; }
 
 // Per-thread message of the last failed C ABI call (gwamd_last_error()).
 inline std::string& last_error()

@@ -1587,7 +1587,7 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             ph.lap<kPhForward>();
             const int alen = band_traceback<ScoreT, SizeT, CPL>(g, X, V, lread, L, end_row, B, sc, spill, rowsz, tile,
-                                                                ag, ar, d.aln_cap, lane, bp, (d.tb_rank & 1) != 0,
+                                                                ag, ar, d.aln_cap, lane, bp, (d.tb_rank & kTbRanked) != 0,
                                                                 d.tb_rank);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             wave_sync();
@@ -1642,10 +1642,10 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
             rc = uniform(rc); // wave-uniform: the sort below runs scalar control flow
             nc = uniform(nc);
             bool lv_done = false;
-            if (rc == kSuccess && !d.spoa_accurate && !(d.diag & 4))
+            if (rc == kSuccess && !d.spoa_accurate && !(d.diag & kDiagTopsortFifo))
             {
                 // level-keyed Kahn sort on every wave of the workgroup
-                // (GWAMD_TOPSORT=fifo, Dims::diag bit 2, keeps the FIFO below)
+                // (GWAMD_TOPSORT=fifo, kDiagTopsortFifo, keeps the FIFO below)
                 if (nw > 1)
                 {
                     if (lane == 0)
@@ -1788,92 +1788,34 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
 } // namespace poa
 } // namespace gwamd
 
-// Launch and occupancy entry points of one band-width class: poa_band.hip is
-// compiled once per cells-per-lane value (poa_band_c2/c4/c8.hip define
-// GWAMD_BAND_TU_CPL) so the three instantiation sets build in parallel;
+// The kernels of one band-width class: poa_band.hip is compiled once per
+// cells-per-lane value (the Makefile builds poa_band_c<CPL>.o with
+// -DGWAMD_BAND_TU_CPL=<CPL>) so the instantiation sets build in parallel;
 // poa_band_dispatch.cpp picks the one the plan needs.
 #ifndef GWAMD_BAND_TU_CPL
-#error "poa_band.hip is built through poa_band_c<CPL>.hip (CPL 2, 4, 6, 8, 10, 12, 14, 16)"
+#error "poa_band.hip is built with -DGWAMD_BAND_TU_CPL=<CPL> (2, 4, 6, 8, 10, 12, 14, 16: see the Makefile)"
 #endif
 #define GWAMD_BAND_CAT2(a, b) a##b
 #define GWAMD_BAND_CAT(a, b) GWAMD_BAND_CAT2(a, b)
 
-extern "C" hipError_t GWAMD_BAND_CAT(gwamd_internal_poa_band_launch_cpl, GWAMD_BAND_TU_CPL)(
-    const gwamd::poa::Buffers* b, const gwamd::poa::Dims* d, const gwamd::poa::Scores* sc, int score_bits,
-    int size_bits, int msa, hipStream_t stream)
+namespace
+{
+template <typename ScoreT, typename SizeT>
+const void* band_kernel(bool msa)
 {
     using namespace gwamd::poa;
-    constexpr int CPL = GWAMD_BAND_TU_CPL;
-    const dim3 grid(b->head ? b->num_slots : b->num_windows), blk(kWave * (d->band_ad ? d->band_ad : 1));
-    const size_t lb = size_t(d->lds_bytes);
-#define GWAMD_BAND_LAUNCH(ST, ZT, MS)                                                                           \
-    {                                                                                                         \
-        auto kfn = poa_window_kernel_band<ST, ZT, MS, CPL>;                                                   \
-        if (lb > 65536)                                                                                       \
-        {                                                                                                     \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                            \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, int(lb));          \
-            if (e != hipSuccess)                                                                              \
-                return e;                                                                                     \
-        }                                                                                                     \
-        hipLaunchKernelGGL(kfn, grid, blk, lb, stream, *b, *d, *sc);                                          \
-        return hipGetLastError();                                                                             \
-    }
-#define GWAMD_BAND_MSA(ST, ZT)              \
-    if (msa)                                \
-        GWAMD_BAND_LAUNCH(ST, ZT, true)     \
-    GWAMD_BAND_LAUNCH(ST, ZT, false)
-    if (d->lds_cpl != CPL)
-        return hipErrorInvalidConfiguration;
-    if (score_bits == 16)
-    {
-        GWAMD_BAND_MSA(int16_t, int16_t)
-    }
-    if (size_bits == 16)
-    {
-        GWAMD_BAND_MSA(int32_t, int16_t)
-    }
-    GWAMD_BAND_MSA(int32_t, int32_t)
-#undef GWAMD_BAND_MSA
-#undef GWAMD_BAND_LAUNCH
+    const void* k[] = {reinterpret_cast<const void*>(&poa_window_kernel_band<ScoreT, SizeT, true, GWAMD_BAND_TU_CPL>),
+                       reinterpret_cast<const void*>(&poa_window_kernel_band<ScoreT, SizeT, false, GWAMD_BAND_TU_CPL>)};
+    return k[msa ? 0 : 1];
 }
+} // namespace
 
-// Resident workgroups per CU of the planned banded kernel (persistent grid).
-extern "C" int GWAMD_BAND_CAT(gwamd_internal_poa_band_blocks_per_cu_cpl, GWAMD_BAND_TU_CPL)(
-    const gwamd::poa::Dims* d, int score_bits, int size_bits, int msa)
+extern "C" const void* GWAMD_BAND_CAT(gwamd_internal_poa_band_kernel_cpl, GWAMD_BAND_TU_CPL)(int score_bits,
+                                                                                            int size_bits, int msa)
 {
-    using namespace gwamd::poa;
-    constexpr int CPL = GWAMD_BAND_TU_CPL;
-    const size_t lb = size_t(d->lds_bytes);
-#define GWAMD_BAND_OCC(ST, ZT, MS)                                                                              \
-    {                                                                                                         \
-        auto kfn = poa_window_kernel_band<ST, ZT, MS, CPL>;                                                   \
-        if (lb > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                             \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, int(lb)) != hipSuccess) \
-            return 0;                                                                                         \
-        int n = 0;                                                                                            \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kfn, kWave * (d->band_ad ? d->band_ad : 1), lb) !=      \
-            hipSuccess)                                                                                       \
-            return 0;                                                                                         \
-        return n;                                                                                             \
-    }
-#define GWAMD_BAND_OCC_MSA(ST, ZT)         \
-    if (msa)                               \
-        GWAMD_BAND_OCC(ST, ZT, true)       \
-    GWAMD_BAND_OCC(ST, ZT, false)
-    if (d->lds_cpl != CPL)
-        return 0;
-    if (score_bits == 16)
-    {
-        GWAMD_BAND_OCC_MSA(int16_t, int16_t)
-    }
-    if (size_bits == 16)
-    {
-        GWAMD_BAND_OCC_MSA(int32_t, int16_t)
-    }
-    GWAMD_BAND_OCC_MSA(int32_t, int32_t)
-#undef GWAMD_BAND_OCC_MSA
-#undef GWAMD_BAND_OCC
+    return score_bits == 16  ? band_kernel<int16_t, int16_t>(msa != 0)
+           : size_bits == 16 ? band_kernel<int32_t, int16_t>(msa != 0)
+                             : band_kernel<int32_t, int32_t>(msa != 0);
 }
 #undef GWAMD_BAND_CAT
 #undef GWAMD_BAND_CAT2

@@ -15,6 +15,7 @@
 #include "host_common.hpp"
 #include "poa_batch_internal.hpp"
 #include "poa_common.hpp"
+#include "poa_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,8 @@ extern "C" hipError_t gwamd_internal_poa_launch(const gwamd::poa::Buffers* b, co
                                        int msa, hipStream_t stream);
 extern "C" int gwamd_internal_poa_blocks_per_cu(const gwamd::poa::Dims* d, int score_bits, int size_bits, int banded,
                                                 int msa);
+extern "C" gwamd::poa::KernelRef gwamd_internal_poa_kernel(const gwamd::poa::Dims* d, int score_bits, int size_bits,
+                                                           int banded, int msa);
 
 namespace claraparabricks
 {
@@ -93,6 +96,34 @@ int64_t reference_device_bytes_per_poa(const BatchSize& bs, bool banded, bool ms
     return b;
 }
 
+// The batch constructor's planning steps: score and size widths, capacities,
+// and the kernel plan (poa_plan.cpp).  Touches no device (gwamd_internal_poa_plan).
+gwamd::poa::Dims plan_batch(const BatchSize& bs, bool banded, int8_t output_mask, int16_t gap, int16_t mismatch,
+                            int16_t match, const gwamd::poa::PoaTuning& tune, int& score_bits, int& size_bits)
+{
+    score_bits = use32bit_score(bs, gap, mismatch, match) ? 32 : 16;
+    // batch.cu:45-73: 16-bit score implies 16-bit size
+    size_bits  = (score_bits == 32 && use32bit_size(bs, banded)) ? 32 : 16;
+    gwamd::poa::Dims dims{};
+    // this build's own per-window footprint
+    dims.max_nodes     = banded ? bs.max_nodes_per_window_banded : bs.max_nodes_per_window;
+    dims.max_seqs      = bs.max_sequences_per_poa;
+    dims.max_seq_len   = bs.max_sequence_size;
+    dims.max_consensus = bs.max_consensus_size;
+    dims.band_width    = bs.alignment_band_width;
+    dims.score_stride  = banded ? bs.alignment_band_width + gwamd::poa::kBandPad
+                                : int32_t(align8(int64_t(bs.max_sequence_size) + 48));
+    dims.score_rows    = dims.max_nodes + 2;
+    dims.aln_cap       = dims.max_nodes + bs.max_sequence_size + 4;
+    dims.want_consensus = (output_mask & OutputType::consensus) ? 1 : 0;
+    // the reference's spoa_accurate build option (CMakeLists.txt:23-30) as a
+    // process-wide default; gwamd_poa_set_spoa_accurate switches one batch
+    if (const char* sa = std::getenv("GWAMD_SPOA_ACCURATE"))
+        dims.spoa_accurate = std::atoi(sa) != 0 ? 1 : 0;
+    gwamd::poa::plan_kernels(dims, banded, gap, score_bits, size_bits, tune);
+    return dims;
+}
+
 struct DevBuf
 {
     void* p = nullptr;
@@ -117,9 +148,7 @@ public:
     {
         detail::check_non_negative(bs.max_sequences_per_poa, "Maximum sequences per POA has to be non-negative");
         ScopedDevice dev(device_id_);
-        score_bits_ = use32bit_score(bs_, gap_, mismatch_, match_) ? 32 : 16;
-        size_bits_  = (score_bits_ == 32 && use32bit_size(bs_, banded_)) ? 32 : 16;
-        // batch.cu:45-73: 16-bit score implies 16-bit size
+        dims_ = plan_batch(bs_, banded_, output_mask_, gap_, mismatch_, match_, tune_, score_bits_, size_bits_);
         const int sz      = size_bits_ / 8;
         const int sbytes  = score_bits_ / 8;
         const bool msa    = (output_mask_ & OutputType::msa) != 0;
@@ -136,24 +165,6 @@ public:
         const int64_t ref_score_matrix = ref_seq_dim * gdim * sbytes;
         int64_t max_poas               = int64_t(max_mem) / (per_poa + ref_score_matrix);
 
-        // this build's own per-window footprint
-        dims_.max_nodes     = banded_ ? bs_.max_nodes_per_window_banded : bs_.max_nodes_per_window;
-        dims_.max_seqs      = bs_.max_sequences_per_poa;
-        dims_.max_seq_len   = bs_.max_sequence_size;
-        dims_.max_consensus = bs_.max_consensus_size;
-        dims_.band_width    = bs_.alignment_band_width;
-        dims_.score_stride  = banded_ ? bs_.alignment_band_width + gwamd::poa::kBandPad
-                                      : int32_t(align8(int64_t(bs_.max_sequence_size) + 48));
-        dims_.score_rows    = dims_.max_nodes + 2;
-        dims_.aln_cap       = dims_.max_nodes + bs_.max_sequence_size + 4;
-        dims_.want_consensus = (output_mask_ & OutputType::consensus) ? 1 : 0;
-        // the reference's spoa_accurate build option (CMakeLists.txt:23-30) as a
-        // process-wide default; gwamd_poa_set_spoa_accurate switches one batch
-        if (const char* sa = std::getenv("GWAMD_SPOA_ACCURATE"))
-            dims_.spoa_accurate = std::atoi(sa) != 0 ? 1 : 0;
-        plan_lds_kernel();
-        plan_band_kernel();
-        dims_.diag = diag_bits();
         // this build's footprint: graph + inputs + outputs per window, and the
         // forward/traceback scratch per slot.  The LDS and banded kernels run
         // a persistent grid of as many workgroups as are resident at once, so
@@ -168,9 +179,8 @@ public:
             GWAMD_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id_));
             resident = int64_t(gwamd_internal_poa_blocks_per_cu(&dims_, score_bits_, size_bits_, banded_ ? 1 : 0,
                                                                 msa ? 1 : 0)) * cus;
-            if (const char* ev = gwamd::host::diag_env("GWAMD_POA_SLOTS")) // diagnostic: a smaller persistent grid
-                if (std::atoi(ev) > 0)
-                    resident = std::min<int64_t>(resident > 0 ? resident : INT32_MAX, std::atoi(ev));
+            if (tune_.slots > 0) // diagnostic: a smaller persistent grid
+                resident = std::min<int64_t>(resident > 0 ? resident : INT32_MAX, tune_.slots);
             if (resident > 0 && own_cap > resident)
                 own_cap = std::max(own_cap, (int64_t(max_mem) - resident * sbytes_slot) / wbytes);
         }
@@ -269,9 +279,8 @@ public:
         bufs_.head  = nullptr;
         int cus     = 0;
         GWAMD_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id_));
-        if (const char* ev = gwamd::host::diag_env("GWAMD_LAUNCH_ORDER_CUS")) // diagnostic: plan for fewer CUs
-            if (std::atoi(ev) > 0)
-                cus = std::atoi(ev);
+        if (tune_.order_cus > 0) // diagnostic: plan for fewer CUs
+            cus = tune_.order_cus;
         const int n           = poa_count_;
         const bool persistent = dims_.lds_kernel != 0 && n > slots_;
         if (!persistent && (cus <= 0 || n <= cus))
@@ -605,287 +614,6 @@ private:
         return b;
     }
 
-    // LDS-resident kernel (poa_window_kernel_lds): full alignment with 16-bit
-    // scores and node ids.  LDS image per window: read | ring of E rows (also
-    // the traceback tile and the add-alignment scratch) | row program |
-    // predecessor lists | shared words; the topological sort reuses everything
-    // below the shared words.  Span carries of multi-sweep reads live in HBM
-    // next to the traceback codes.
-    void plan_lds_kernel() { plan_lds_layout(dims_, banded_, size_bits_, score_bits_); }
-
-public:
-    // ... as a function of the capacities in `dims` alone (and the diagnostic
-    // environment), so that the plan can be examined without a device
-    // (gwamd_internal_poa_lds_add_plan)
-    static void plan_lds_layout(gwamd::poa::Dims& dims, bool banded, int size_bits, int score_bits)
-    {
-        dims.lds_kernel = 0;
-        const char* env  = gwamd::host::diag_env("GWAMD_POA_KERNEL");
-        if (env && std::string(env) == "v1")
-            return;
-        // 16-bit node ids; 16-bit scores, or 32-bit ones (the reference's
-        // use32bitScore batches: nw_forward_lds_w)
-        if (banded || size_bits != 16 || (score_bits != 16 && score_bits != 32))
-            return;
-        const bool wide      = score_bits == 32;
-        auto a16             = [](int64_t v) { return (v + 15) & ~int64_t(15); };
-        int ring_rows        = 8;
-        const int64_t read_b = gwamd::poa::lds_read_bytes(dims.max_seq_len);
-        // forward pass shape: CPL columns per lane on NW waves; a sweep covers
-        // NW*64*CPL read columns, longer reads take several sweeps
-        // (GWAMD_POA_LDS_SHAPE="cpl,waves").  32-bit scores: one sweep up to
-        // 4,096 columns (8 waves), 8,192 with 16 columns per lane
-        int cpl = 8, nw = 1;
-        const int ms = dims.max_seq_len;
-        if (!wide && ms > 512)
-            nw = 2;
-        if (wide)
-        {
-            nw  = ms <= 512 ? 1 : (ms <= 1024 ? 2 : (ms <= 2048 ? 4 : 8));
-            cpl = ms <= 4096 ? 8 : 16;
-        }
-        if (const char* sh = gwamd::host::diag_env("GWAMD_POA_LDS_SHAPE"))
-        {
-            int c = 0, n = 0;
-            if (std::sscanf(sh, "%d,%d", &c, &n) == 2)
-            {
-                const bool known =
-                    wide ? ((c == 8 && (n == 1 || n == 2 || n == 4 || n == 8)) || (c == 16 && n == 8))
-                         : ((n == 1 && (c == 8 || c == 16 || c == 24 || c == 32)) || (c == 8 && n >= 2 && n <= 4) ||
-                            (c == 16 && n == 4) || (c == 4 && n == 4));
-                if (!known)
-                    throw std::invalid_argument("GWAMD_POA_LDS_SHAPE: unsupported columns/waves pair");
-                cpl = c, nw = n;
-            }
-        }
-        const int ebytes     = wide ? 4 : 2;
-        // the one-wave graph update's scratch always fits the ring region
-        // (this is lds_add_wave0_bytes rounded up); the every-wave update's
-        // larger one is not planned for: the kernel runs it where
-        // lds_add_fits(max_seq_len, max_nodes, lds_rec_off - lds_ring_off)
-        const int64_t add_b  = 5 * a16(dims.max_seq_len + 16) + 2 * (int64_t(dims.max_nodes) + dims.max_seq_len);
-        const int64_t tile_b = int64_t(gwamd::poa::kTileRows) * gwamd::poa::kTileCols + gwamd::poa::kTbRankBytes;
-        const int64_t rec_b  = a16(int64_t(dims.max_nodes + 2) * 4);
-        const int64_t sh_b   = a16(wide ? gwamd::poa::kShBytesW(nw) : gwamd::poa::kShBytes(nw));
-        auto ring_bytes      = [&](int rows) {
-            return a16(std::max<int64_t>({int64_t(rows) * dims.score_stride * ebytes, tile_b, add_b}));
-        };
-        int64_t ring_b       = ring_bytes(ring_rows);
-        int64_t fixed        = read_b + ring_b + rec_b + sh_b;
-        int64_t target       = 40960 - 16; // 4 workgroups per CU incl. static LDS: one batch of
-                                           // 1024 windows is resident on the 256 CUs at once
-        if (wide)
-        {
-            // 32-bit rows are twice as wide: two windows per CU when their
-            // images fit, else one; an 8-row ring when it fits, else 4 rows
-            // (predecessors farther back go through the HBM spill rows)
-            int64_t chosen = 0;
-            for (int64_t budget : {int64_t(81920 - 16), int64_t(163840 - 64)})
-            {
-                for (int rows : {8, 4})
-                {
-                    const int64_t rb = ring_bytes(rows);
-                    const int64_t fx = read_b + rb + rec_b + sh_b;
-                    if (fx + 2048 <= budget)
-                    {
-                        ring_rows = rows, ring_b = rb, fixed = fx, chosen = budget;
-                        break;
-                    }
-                }
-                if (chosen)
-                    break;
-            }
-            if (!chosen)
-                return;
-            target = chosen;
-        }
-        int64_t xl_cap       = std::max<int64_t>(1024, (target - fixed) / 2);
-        xl_cap               = std::min<int64_t>(xl_cap, 65535);
-        int64_t total        = fixed + a16(xl_cap * 2);
-        if (const char* pad = gwamd::host::diag_env("GWAMD_POA_LDS_PAD")) // diagnostic: fewer windows per CU
-            total += a16(std::atoi(pad));
-        if (total > (wide ? 163840 - 64 : 65536))
-            return;
-        dims.lds_kernel    = 1;
-        dims.tb_rank       = tb_rank_default();
-        dims.lds_ring_off  = int32_t(read_b);
-        dims.lds_ring_rows = ring_rows;
-        dims.lds_rec_off   = int32_t(read_b + ring_b);
-        dims.lds_xl_off    = int32_t(read_b + ring_b + rec_b);
-        dims.lds_xl_cap    = int32_t(xl_cap);
-        dims.lds_sh_off    = int32_t(read_b + ring_b + rec_b + a16(xl_cap * 2));
-        dims.lds_bytes     = int32_t(total);
-        dims.lds_cpl       = cpl;
-        dims.lds_waves     = nw;
-        dims.code_stride   = int32_t(a16(int64_t(dims.max_seq_len) + 48));
-        // HBM side buffer per window: traceback codes, span carries
-        const int64_t code_b = int64_t(dims.score_rows) * dims.code_stride;
-        const int64_t cr_b   = a16(int64_t(dims.max_nodes + 2) * ebytes);
-        dims.aux_carry_off  = int32_t(code_b);
-        dims.aux_stride     = code_b + cr_b;
-    }
-
-    // Banded kernel (poa_window_kernel_band, poa_band.hip): band widths 128 to
-    // 1,024 in steps of 128 (2 to 16 cells per lane), gap <= 0.  LDS image per window: staged
-    // read | work region (row-program flags, the 16-row ring of band rows, the
-    // traceback tile, the add-alignment scratch; the topological sort also
-    // reuses the read) | shared words.  Windows per CU: 4, 2 or 1, the most
-    // that leave room for the work region at this batch's maximum sizes.
-    // traceback move windows (TbWin, poa_wave.hpp): bit 0 walks them by
-    // pointer doubling (else the scalar walk), bit 1 shapes them as strips
-    // along the path (else 16 x 8 rectangles), bit 2 makes the strips 32
-    // columns x 4 rows (else 16 x 8).  Default: pointer doubling over 16 x 8
-    // strips; GWAMD_TB_WALK=scalar | rect | scalar_rect | strip32 |
-    // scalar_strip32 for parity tests and A/B runs.
-public:
-    static int tb_rank_default()
-    {
-        // GWAMD_TB_ABOVE=k (0-6): strip rows above the slope line (A/B runs;
-        // default 3)
-        int above_bits = 0;
-        if (const char* ab = gwamd::host::diag_env("GWAMD_TB_ABOVE"))
-            above_bits = (std::min(std::max(std::atoi(ab), 0), 6) + 1) << 3;
-        return tb_walk_bits() | above_bits;
-    }
-    // Dims::diag: bit 0 forces the Kahn sort's ring of queued words
-    // (GWAMD_TOPSORT_RING=1, ring-mode parity tests); bit 1 keeps the LDS
-    // kernel on the round-3 forward pass (GWAMD_POA_FWD=v1, A/B runs); bit 2
-    // keeps the LDS and banded kernels on the FIFO Kahn sort instead of the
-    // level-keyed one (GWAMD_TOPSORT=fifo, cross-check tests and A/B runs);
-    // bit 3 keeps the MSA's racon sort on the round-5 DFS step (GWAMD_RACON=v1);
-    // bit 4 keeps the consensus on lane 0 in HBM (GWAMD_CONSENSUS=hbm, parity
-    // tests and A/B runs); bits 16-31 cap the LDS bytes offered to the
-    // wave-wide consensus (GWAMD_CONSENSUS_LDS_BYTES, 1..65535: tests push
-    // small graphs over the fit limit); bit 5 keeps the LDS kernel's graph
-    // update on wave 0 with one read position per lane (GWAMD_POA_ADD=wave0),
-    // bit 6 runs the sequential restatement on lane 0 for every read
-    // (GWAMD_POA_ADD=serial): parity tests and A/B runs
-    static int diag_bits()
-    {
-        const char* r = gwamd::host::diag_env("GWAMD_TOPSORT_RING");
-        const char* f = gwamd::host::diag_env("GWAMD_POA_FWD");
-        const char* t = gwamd::host::diag_env("GWAMD_TOPSORT");
-        const char* d = gwamd::host::diag_env("GWAMD_RACON");
-        const char* c = gwamd::host::diag_env("GWAMD_CONSENSUS");
-        const char* b = gwamd::host::diag_env("GWAMD_CONSENSUS_LDS_BYTES");
-        const char* a = gwamd::host::diag_env("GWAMD_POA_ADD");
-        const int cap = b ? std::min(std::max(std::atoi(b), 1), 65535) : 0;
-        const int add = (a && std::string(a) == "wave0") ? 32 : ((a && std::string(a) == "serial") ? 64 : 0);
-        return add | ((r && std::atoi(r) != 0) ? 1 : 0) | ((f && std::string(f) == "v1") ? 2 : 0) |
-               ((t && std::string(t) == "fifo") ? 4 : 0) | ((d && std::string(d) == "v1") ? 8 : 0) |
-               ((c && std::string(c) == "hbm") ? 16 : 0) | int(uint32_t(cap) << 16);
-    }
-    static int tb_walk_bits()
-    {
-        const char* ev = gwamd::host::diag_env("GWAMD_TB_WALK");
-        const std::string v = ev ? ev : "";
-        if (v == "scalar")
-            return 2;
-        if (v == "rect")
-            return 1;
-        if (v == "scalar_rect")
-            return 0;
-        if (v == "strip32")
-            return 7;
-        if (v == "scalar_strip32")
-            return 6;
-        return 3;
-    }
-
-private:
-    void plan_band_kernel()
-    {
-        if (!banded_ || dims_.lds_kernel)
-            return;
-        const char* env = gwamd::host::diag_env("GWAMD_POA_KERNEL");
-        if (env && std::string(env) == "v1")
-            return;
-        const int bw = dims_.band_width;
-        // every band width the reference accepts up to 1,024 (multiples of
-        // 128, batch.hpp:85-94): CPL = bw / 64 cells per lane, one translation
-        // unit per CPL (poa_band_c<CPL>.hip)
-        if (bw % 128 != 0 || bw < 128 || bw > 1024 || gap_ > 0)
-            return;
-        auto a16          = [](int64_t v) { return (v + 15) & ~int64_t(15); };
-        const int cpl     = bw / 64;
-        const int sbytes  = score_bits_ / 8;
-        // band row: position idx + cpl - 1, whole cpl-cell groups (66-67 of them)
-        const int rowsz   = (bw + gwamd::poa::kBandPad + cpl + cpl - 1) / cpl * cpl;
-        const int64_t ms  = dims_.max_seq_len, mn = dims_.max_nodes;
-        const int64_t read_b  = a16(gwamd::poa::kReadGuard + ms + bw + 48);
-        const int64_t sh_b    = 64;
-        const int ring_rows   = gwamd::poa::band_ring_rows(cpl), tile_rows = gwamd::poa::band_tile_rows(cpl);
-        const int64_t ring_b  = a16(int64_t(ring_rows) * rowsz * sbytes) + 4 * 256 * 4 + 1024 * 4; // + record staging
-        const int64_t tile_b  = a16(int64_t(tile_rows) * bw + 64 * 16 + 512 + gwamd::poa::kTbRankBytes); // codes +
-                                                                      // per-row decode info + walk tables
-        const int64_t flags_b = 2 * a16(mn + 2); // row program: spill and far flags
-        const int64_t add_b   = 7 * a16(ms + 16) + a16(2 * (mn + ms + 16)); // + the edge-slot bytes
-        // anti-diagonal forward pass (poa_band_ad.hpp): a kAdRing-row ring and
-        // one dummy word per lane.  Default: whenever the windows-per-CU
-        // choice below leaves room for it (large windows, one or two per CU);
-        // GWAMD_BAND_FWD=ad|row forces it on (planning for it) or off.
-        const int64_t ad_b    = a16(int64_t(gwamd::poa::kAdRing) * rowsz * sbytes + gwamd::poa::kWave * sbytes) +
-                             a16(mn / 8 + 64); // + the real-row bitmap
-        const char* fwd_env   = gwamd::host::diag_env("GWAMD_BAND_FWD");
-        // (band widths 128 / 256 only: its ring of kAdRing rows is too large beyond)
-        const bool force_ad   = fwd_env && std::string(fwd_env) == "ad" && cpl <= 4;
-        const bool no_ad      = fwd_env && std::string(fwd_env) == "row";
-        const int64_t min_w   = std::max({ring_b, tile_b, flags_b, force_ad ? ad_b : int64_t(0)});
-        const int64_t want_w  = std::max(min_w, add_b);
-        const int64_t kStatic = 256; // static __shared__ bytes of the kernel
-        int64_t total         = 0;
-        int chosen_per_cu     = 1;
-        for (int per_cu : {4, 2, 1})
-        {
-            const int64_t budget = (163840 / per_cu - kStatic) & ~int64_t(15);
-            if ((!force_ad && read_b + want_w + sh_b <= budget) || per_cu == 1)
-            {
-                total         = budget;
-                chosen_per_cu = per_cu;
-                break;
-            }
-        }
-        const int64_t work = total - read_b - sh_b;
-        if (work < min_w)
-            return;
-        dims_.lds_kernel     = 3;
-        // the pass runs kAdMaxWaves waves per window: one window per CU
-        int ad_waves = gwamd::poa::kAdMaxWaves;
-        if (const char* ev = gwamd::host::diag_env("GWAMD_BAND_AD_WAVES")) // diagnostic: fewer waves per window
-            ad_waves = std::max(1, std::min(gwamd::poa::kAdMaxWaves, std::atoi(ev)));
-        dims_.band_ad        = (!no_ad && cpl <= 4 && chosen_per_cu == 1 && work >= ad_b) ? ad_waves : 0;
-        dims_.tb_rank        = tb_rank_default();
-        dims_.lds_cpl        = cpl;
-        dims_.lds_waves      = 1;
-        dims_.lds_bytes      = int32_t(total);
-        dims_.lds_ring_off   = int32_t(read_b);
-        dims_.lds_ring_rows  = ring_rows;
-        dims_.lds_work_bytes = int32_t(work);
-        dims_.lds_sh_off     = int32_t(read_b + work);
-        dims_.score_stride   = rowsz; // spill rows: band row at position idx + cpl - 1
-        dims_.code_stride    = bw;
-        const int64_t rows   = dims_.score_rows;
-        int64_t o            = a16(rows * bw); // codes
-        dims_.aux_reca_off   = int32_t(o);
-        o += a16(rows * 4);
-        dims_.aux_recb_off = int32_t(o);
-        o += a16(rows * 4);
-        dims_.aux_col0_off = int32_t(o);
-        o += a16(rows * 4);
-        dims_.aux_flag_off = int32_t(o);
-        o += a16(rows);
-        dims_.aux_xl_off = int32_t(o);
-        dims_.aux_xl_cap = int32_t(2 * mn + 64);
-        o += a16(int64_t(dims_.aux_xl_cap) * 4);
-        dims_.aux_bx_off = int32_t(o);
-        o += a16((rows / 256 + 2) * 4);
-        dims_.aux_recc_off = int32_t(o);
-        o += a16(rows * 4);
-        dims_.aux_rece_off = int32_t(o);
-        o += a16(rows * 4);
-        dims_.aux_stride = o;
-    }
-
     // Non-score bytes of the reference slab for max_poas windows
     // (allocate_block.hpp:121-285, each buffer aligned to 8 B).
     int64_t reference_fixed_slab(int sz, bool msa) const
@@ -1087,6 +815,7 @@ private:
     bool generated_     = false;
     int32_t bid_        = 0;
     hipEvent_t ev_start_ = nullptr, ev_stop_ = nullptr; // set_launch_events (multi-batch driver)
+    const gwamd::poa::PoaTuning tune_ = gwamd::poa::read_poa_tuning(); // read once, here
     gwamd::poa::Dims dims_{};
     PinnedBuf h_order_; // workgroup -> window (plan_launch_order)
     gwamd::poa::Buffers bufs_{};
@@ -1507,12 +1236,11 @@ int32_t gwamd_poa_env_tuning(int32_t* tb_rank, int32_t* band_fwd, int32_t* force
         gwamd::host::last_error() = "gwamd_poa_env_tuning: NULL output";
         return GWAMD_E_INVALID_ARGUMENT;
     }
-    *tb_rank            = claraparabricks::genomeworks::cudapoa::PoaBatch::tb_rank_default();
-    const char* fwd     = gwamd::host::diag_env("GWAMD_BAND_FWD");
-    *band_fwd           = !fwd ? 0 : (std::string(fwd) == "ad" ? 1 : (std::string(fwd) == "row" ? 2 : 0));
-    const char* kern    = gwamd::host::diag_env("GWAMD_POA_KERNEL");
-    *force_v1           = kern && std::string(kern) == "v1" ? 1 : 0;
-    *diag               = claraparabricks::genomeworks::cudapoa::PoaBatch::diag_bits();
+    const gwamd::poa::PoaTuning t = gwamd::poa::read_poa_tuning();
+    *tb_rank                      = t.tb_rank;
+    *band_fwd                     = t.band_fwd;
+    *force_v1                     = t.force_v1 ? 1 : 0;
+    *diag                         = t.diag;
     return 0;
 }
 
@@ -1563,7 +1291,7 @@ int32_t gwamd_internal_poa_lds_add_plan(int32_t max_seq_len, int32_t max_nodes, 
     d.score_rows   = max_nodes + 2;
     try
     {
-        claraparabricks::genomeworks::cudapoa::PoaBatch::plan_lds_layout(d, false, 16, score_bits);
+        gwamd::poa::plan_lds_layout(d, false, 16, score_bits, gwamd::poa::read_poa_tuning());
     }
     catch (const std::exception& e)
     {
@@ -1580,6 +1308,56 @@ int32_t gwamd_internal_poa_lds_add_plan(int32_t max_seq_len, int32_t max_nodes, 
         *lds_bytes = d.lds_bytes;
     return gwamd::poa::lds_add_fits(d.max_seq_len, d.max_nodes, d.lds_rec_off - d.lds_ring_off) ? 1 : 0;
 }
+
+// Test hook (tests/test_poa_plan.py): the plan the batch constructor makes for
+// these capacities (plan_batch), without a device.  Writes the values of
+// gwamd_internal_poa_plan_fields() in that order (score_bits, size_bits, every
+// field of the planned Dims, then kernel: 1 when the kernel table has a kernel
+// for this plan) and returns their count; negative when planning throws
+// (gwamd_last_error says why) or `cap` is too small.
+#define GWAMD_PLAN_FIELDS(F)                                                                                  \
+    F(max_nodes) F(max_seqs) F(max_seq_len) F(max_consensus) F(score_stride) F(score_rows) F(aln_cap)        \
+    F(band_width) F(want_consensus) F(spoa_accurate) F(lds_kernel) F(lds_bytes) F(lds_ring_off)              \
+    F(lds_ring_rows) F(lds_sh_off) F(lds_rec_off) F(lds_xl_off) F(lds_xl_cap) F(lds_cpl) F(lds_waves)        \
+    F(code_stride) F(aux_stride) F(aux_carry_off) F(lds_work_bytes) F(aux_reca_off) F(aux_recb_off)          \
+    F(aux_col0_off) F(aux_flag_off) F(aux_xl_off) F(aux_xl_cap) F(aux_bx_off) F(aux_recc_off)                \
+    F(aux_rece_off) F(band_ad) F(tb_rank) F(diag)
+
+const char* gwamd_internal_poa_plan_fields(void)
+{
+#define GWAMD_F(f) "," #f
+    return "score_bits,size_bits" GWAMD_PLAN_FIELDS(GWAMD_F) ",kernel";
+#undef GWAMD_F
+}
+
+int32_t gwamd_internal_poa_plan(int32_t max_sequence_size, int32_t max_sequences_per_poa, int32_t band_width,
+                                int32_t max_nodes_per_window, int32_t max_nodes_per_window_banded, int32_t banded,
+                                int32_t msa, int32_t gap, int32_t mismatch, int32_t match, int64_t* out, int32_t cap)
+{
+    return guarded([&]() -> int32_t {
+        // (the three-argument BatchSize with the node capacities replaced: no
+        // band width <= sequence size rule, as for the tests' batches)
+        cp::BatchSize bs(max_sequence_size, max_sequences_per_poa, band_width);
+        bs.max_nodes_per_window              = cp::detail::align_up(max_nodes_per_window, 4);
+        bs.max_nodes_per_window_banded       = cp::detail::align_up(max_nodes_per_window_banded, 4);
+        bs.max_matrix_graph_dimension        = bs.max_nodes_per_window;
+        bs.max_matrix_graph_dimension_banded = bs.max_nodes_per_window_banded;
+        int score_bits = 0, size_bits = 0;
+        const gwamd::poa::Dims d =
+            cp::plan_batch(bs, banded != 0, msa ? cp::OutputType::msa : cp::OutputType::consensus, int16_t(gap),
+                           int16_t(mismatch), int16_t(match), gwamd::poa::read_poa_tuning(), score_bits, size_bits);
+#define GWAMD_F(f) , int64_t(d.f)
+        const bool found  = gwamd_internal_poa_kernel(&d, score_bits, size_bits, banded, msa).fn != nullptr;
+        const int64_t v[] = {score_bits, size_bits GWAMD_PLAN_FIELDS(GWAMD_F), found ? 1 : 0};
+#undef GWAMD_F
+        const int32_t n = int32_t(sizeof(v) / sizeof(v[0]));
+        if (!out || cap < n)
+            return -1;
+        std::copy(v, v + n, out);
+        return n;
+    });
+}
+#undef GWAMD_PLAN_FIELDS
 
 static size_t query_free_memory(uint64_t given)
 {

@@ -7,6 +7,7 @@
 // the same point as in the reference.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 namespace gwamd
@@ -25,7 +26,7 @@ constexpr int kAdSpillDist   = kAdRing - kWave + 1; // successor distance that n
 // banded kernel (poa_band.hip): LDS ring rows (power of two) and traceback
 // tile rows per cells-per-lane value.  Band widths past 512 take a 32-row
 // tile and, at 1,024, an 8-row ring, so four windows share a CU (one wave per
-// SIMD) instead of two; the host plan (plan_band_kernel) sizes the LDS image
+// SIMD) instead of two; the host plan (plan_band_kernel, poa_plan.cpp) sizes the LDS image
 // from the same two functions
 constexpr int band_ring_rows(int cpl) { return cpl >= 16 ? 8 : 16; }
 constexpr int band_tile_rows(int cpl) { return cpl >= 10 ? 32 : 64; }
@@ -98,13 +99,54 @@ struct Dims
     int32_t aux_recc_off;   //   | row records c (u32)
     int32_t aux_rece_off;   //   | row records e (u32)
     int32_t band_ad;        // banded kernel: waves of the anti-diagonal forward pass (0: row-parallel pass)
-    int32_t tb_rank;        // traceback move windows (TbWin): bit 0 pointer-doubling walk, bit 1 strips, bit 2 32 x 4 strips
-    int32_t diag;           // diagnostic switches (GWAMD_DIAG=1 only): bit 0 Kahn sort queued words in a ring,
-                            // bit 1 LDS kernel on the round-3 forward pass, bit 2 FIFO Kahn sort,
-                            // bit 3 round-5 racon DFS step for the MSA, bit 4 consensus by lane 0 in HBM,
-                            // bits 16-31 cap on the LDS bytes offered to the consensus (0: none),
-                            // bit 5 graph update on wave 0, one position per lane (GWAMD_POA_ADD=wave0),
-                            // bit 6 graph update by the sequential restatement on lane 0 (GWAMD_POA_ADD=serial)
+    int32_t tb_rank;        // traceback move windows: kTb* below
+    int32_t diag;           // diagnostic switches (GWAMD_DIAG=1 only): kDiag* below
+};
+
+// Dims::tb_rank: how the traceback walks its move windows (TbWin,
+// poa_wave.hpp).  Default kTbDefault: pointer doubling over 16 x 8 strips along
+// the path.  GWAMD_TB_WALK = scalar | rect | scalar_rect | strip32 |
+// scalar_strip32 clears or sets the three mode bits (parity tests, A/B runs);
+// GWAMD_TB_ABOVE=k (0-6) puts k + 1 into the kTbAbove field.
+constexpr int kTbRanked     = 1; // walk by pointer doubling (else the scalar walk)
+constexpr int kTbStrips     = 2; // strips along the path (else 16 x 8 rectangles)
+constexpr int kTbStrip32    = 4; // strips of 32 columns x 4 rows (else 16 x 8)
+constexpr int kTbDefault    = kTbRanked | kTbStrips;
+constexpr int kTbAboveShift = 3; // bits 3-5: strip rows above the slope line + 1 (0: the default, 3)
+constexpr int kTbAboveMask  = 7;
+
+// Dims::diag: diagnostic switches for parity tests and A/B runs, all 0 by
+// default, each set by one variable (read only with GWAMD_DIAG=1).
+constexpr int kDiagTopsortRing  = 1;  // GWAMD_TOPSORT_RING=1: the Kahn sort keeps its queued words in a ring
+constexpr int kDiagFwdV1        = 2;  // GWAMD_POA_FWD=v1: LDS kernel on the round-3 forward pass
+constexpr int kDiagTopsortFifo  = 4;  // GWAMD_TOPSORT=fifo: FIFO Kahn sort instead of the level-keyed one
+constexpr int kDiagRaconV1      = 8;  // GWAMD_RACON=v1: the MSA's racon sort on the round-5 DFS step
+constexpr int kDiagConsensusHbm = 16; // GWAMD_CONSENSUS=hbm: consensus by lane 0 in HBM
+constexpr int kDiagAddWave0     = 32; // GWAMD_POA_ADD=wave0: graph update on wave 0, one read position per lane
+constexpr int kDiagAddSerial    = 64; // GWAMD_POA_ADD=serial: the sequential restatement on lane 0 for every read
+constexpr int kDiagConsLdsShift = 16; // bits 16-31, GWAMD_CONSENSUS_LDS_BYTES (1..65535): cap on the LDS bytes
+                                      // offered to the wave-wide consensus (0: none)
+
+// Forward-pass shapes of the LDS kernel: columns per lane, waves per window,
+// 32-bit scores.  The one list: the kernels are instantiated from it
+// (poa_kernels.hip) and GWAMD_POA_LDS_SHAPE is checked against it (poa_plan.cpp).
+struct LdsShape
+{
+    int cpl, waves;
+    bool wide;
+};
+constexpr LdsShape kLdsShapes[] = {{8, 1, true},   {8, 2, true},   {8, 4, true},   {8, 8, true},  {16, 8, true},
+                                   {8, 1, false},  {16, 1, false}, {24, 1, false}, {32, 1, false}, {8, 2, false},
+                                   {8, 3, false},  {8, 4, false},  {16, 4, false}, {4, 4, false}};
+constexpr int kNumLdsShapes = int(sizeof(kLdsShapes) / sizeof(kLdsShapes[0]));
+
+// A resolved kernel: its host handle, workgroup size and dynamic LDS bytes
+// (fn == nullptr: no such kernel).
+struct KernelRef
+{
+    const void* fn;
+    int threads;
+    size_t dynamic_lds;
 };
 
 // LDS kernel: bytes of the staged read at the start of the LDS image (the ring
@@ -116,7 +158,7 @@ constexpr int64_t lds_read_bytes(int64_t max_seq_len) { return (max_seq_len + 48
 // gid, curr (u16) and kind (u8) per read position, owner (u16) per node and
 // new node; the every-wave update (add_alignment_waves) also keeps hit and
 // ohit (u8 per read position) and kAddShBytes of control words behind them.
-// One layout for the host's plan (poa_batch.cpp) and the kernel.
+// One layout for the host's plan (poa_plan.cpp) and the kernel.
 constexpr int kAddShBytes = 64; // conflict word, one error word per wave (up to 8)
 constexpr int64_t lds_add_ms(int64_t max_seq_len) { return (max_seq_len + 16) & ~int64_t(15); }
 constexpr int64_t lds_add_wave0_bytes(int64_t max_seq_len, int64_t max_nodes)

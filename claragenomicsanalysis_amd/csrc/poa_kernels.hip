@@ -18,6 +18,7 @@
 #include <climits>
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 
 #include "poa_wave.hpp"
 
@@ -1207,9 +1208,9 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
                                           false, (GWAMD_LDS int*)(shb));
     // graph update: 0 every wave (add_alignment_waves; when its scratch fits
     // the ring region), 1 wave 0 with one position per lane, 2 the sequential
-    // restatement on lane 0 (Dims::diag bits 5 and 6, GWAMD_POA_ADD)
+    // restatement on lane 0 (kDiagAddWave0, kDiagAddSerial, GWAMD_POA_ADD)
     const bool add_fits = lds_add_fits(d.max_seq_len, d.max_nodes, d.lds_rec_off - d.lds_ring_off);
-    const int add_mode  = (d.diag & 64) ? 2 : (((d.diag & 32) || !add_fits) ? 1 : 0);
+    const int add_mode  = (d.diag & kDiagAddSerial) ? 2 : (((d.diag & kDiagAddWave0) || !add_fits) ? 1 : 0);
 
     for (int idx = blockIdx.x; idx < b.num_windows;)
     {
@@ -1246,11 +1247,11 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
     PhaseTimer ph;
     FwdProf fp;
     // round-4 forward pass unless the scores do not fit its byte table (or
-    // Dims::diag bit 1, GWAMD_POA_FWD=v1 under GWAMD_DIAG, asks for round 3's)
+    // kDiagFwdV1, GWAMD_POA_FWD=v1 under GWAMD_DIAG, asks for round 3's)
 #ifdef GWAMD_FWD_PROFILE
     const bool use_v2 = false;
 #else
-    const bool use_v2 = !W && fwd2_ok(sc) && !(d.diag & 2);
+    const bool use_v2 = !W && fwd2_ok(sc) && !(d.diag & kDiagFwdV1);
 #endif
     const WindowDesc wd = b.windows[w];
     const int nseq      = wd.num_seqs;
@@ -1316,7 +1317,7 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
             if (wave == 0)
             {
                 const int alen_w = traceback_codes<SizeT>(g, P, V, L, end_row, codes, d.code_stride, tile, ag, ar,
-                                                          d.aln_cap, lane, (d.tb_rank & 1) != 0,
+                                                          d.aln_cap, lane, (d.tb_rank & kTbRanked) != 0,
                                                           d.tb_rank);
                 if (lane == 0)
                     sh_len = alen_w;
@@ -1387,8 +1388,8 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
             bool lv_done = false;
             __syncthreads(); // sh_* are rewritten below
             // level-keyed Kahn sort on every wave of the workgroup
-            // (GWAMD_TOPSORT=fifo, Dims::diag bit 2, keeps the FIFO below)
-            if (rc == kSuccess && !d.spoa_accurate && !(d.diag & 4))
+            // (GWAMD_TOPSORT=fifo, kDiagTopsortFifo, keeps the FIFO below)
+            if (rc == kSuccess && !d.spoa_accurate && !(d.diag & kDiagTopsortFifo))
                 lv_done = topsort_levels<SizeT, NW>(g, nc, V, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off, tid, kThr,
                                                     cpred, lv_hint);
             lv_hint = lv_done ? nc : 0; // cpred holds c(v) of this sort for the next one
@@ -1401,7 +1402,7 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
                                                        (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off);
                     // scratch: the read and the ring (both free after the add)
                     else if (!topsort_lds<SizeT>(g, nc, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off, AX.sh, lane, nullptr,
-                                                       (d.diag & 1) != 0) &&
+                                                       (d.diag & kDiagTopsortRing) != 0) &&
                              !topsort_lds_big<SizeT>(g, nc, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off, lane))
                     {
                         if (lane == 0)
@@ -1929,23 +1930,80 @@ extern "C" int gwamd_internal_topsort_levels(int size_bits, int n, int n_prev, i
 }
 
 // ---------------------------------------------------------------------------
-extern "C" hipError_t gwamd_internal_poa_band_launch(const gwamd::poa::Buffers* b, const gwamd::poa::Dims* d,
-                                                     const gwamd::poa::Scores* sc, int score_bits, int size_bits,
-                                                     int msa, hipStream_t stream); // poa_band.hip
-extern "C" int gwamd_internal_poa_band_blocks_per_cu(const gwamd::poa::Dims* d, int score_bits, int size_bits,
-                                                     int msa); // poa_band.hip
+// Kernel table and launch.  gwamd_internal_poa_kernel resolves a plan to its
+// kernel; launch and occupancy are the same few steps over whatever it finds.
+extern "C" gwamd::poa::KernelRef gwamd_internal_poa_band_kernel(const gwamd::poa::Dims* d, int score_bits,
+                                                                int size_bits, int msa); // poa_band_dispatch.cpp
 
 namespace
 {
-template <typename K>
-int blocks_per_cu(K kfn, int threads, size_t lds)
+using namespace gwamd::poa;
+
+// the LDS kernels, instantiated from kLdsShapes: {with, without} the MSA per shape
+struct LdsPair
 {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kfn, threads, lds) != hipSuccess)
-        return 0;
-    return n;
+    const void* k[2];
+};
+template <size_t I>
+LdsPair lds_kernels_at()
+{
+    constexpr LdsShape s = kLdsShapes[I];
+    return {{reinterpret_cast<const void*>(&poa_window_kernel_lds<true, s.cpl, s.waves, s.wide>),
+             reinterpret_cast<const void*>(&poa_window_kernel_lds<false, s.cpl, s.waves, s.wide>)}};
+}
+template <size_t... I>
+const void* lds_kernel(int cpl, int waves, bool wide, bool msa, std::index_sequence<I...>)
+{
+    const LdsPair table[] = {lds_kernels_at<I>()...};
+    for (int i = 0; i < kNumLdsShapes; i++)
+        if (kLdsShapes[i].cpl == cpl && kLdsShapes[i].waves == waves && kLdsShapes[i].wide == wide)
+            return table[i].k[msa ? 0 : 1];
+    return nullptr;
+}
+
+// the v1 kernels: one workgroup of one wave per window, any score and size type
+template <typename ScoreT, typename SizeT>
+const void* v1_kernel(bool banded, bool msa)
+{
+    const void* k[] = {reinterpret_cast<const void*>(&poa_window_kernel<ScoreT, SizeT, true, true>),
+                       reinterpret_cast<const void*>(&poa_window_kernel<ScoreT, SizeT, true, false>),
+                       reinterpret_cast<const void*>(&poa_window_kernel<ScoreT, SizeT, false, true>),
+                       reinterpret_cast<const void*>(&poa_window_kernel<ScoreT, SizeT, false, false>)};
+    return k[(banded ? 0 : 2) + (msa ? 0 : 1)];
+}
+
+// above 64 KB of dynamic LDS a kernel has to be told so first
+hipError_t prepare(const KernelRef& k)
+{
+    if (k.fn == nullptr)
+        return hipErrorInvalidConfiguration;
+    if (k.dynamic_lds <= 65536)
+        return hipSuccess;
+    return hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(k.dynamic_lds));
 }
 } // namespace
+
+// The kernel of a planned Dims (fn == nullptr: none, the plan and the table
+// disagree).  Taking a kernel's host handle needs no device.
+extern "C" gwamd::poa::KernelRef gwamd_internal_poa_kernel(const gwamd::poa::Dims* d, int score_bits, int size_bits,
+                                                           int banded, int msa)
+{
+    if (d->lds_kernel == 3)
+        return banded ? gwamd_internal_poa_band_kernel(d, score_bits, size_bits, msa) : KernelRef{nullptr, 0, 0};
+    if (d->lds_kernel == 1)
+    {
+        if (banded || size_bits != 16 || (score_bits != 16 && score_bits != 32))
+            return {nullptr, 0, 0};
+        return {lds_kernel(d->lds_cpl, d->lds_waves, score_bits == 32, msa != 0,
+                           std::make_index_sequence<size_t(kNumLdsShapes)>()),
+                kWave * d->lds_waves, size_t(d->lds_bytes)};
+    }
+    const int lds_bytes = (d->max_seq_len > d->band_width + kBandPad ? d->max_seq_len : d->band_width + kBandPad) + 32;
+    const void* fn      = score_bits == 16   ? v1_kernel<int16_t, int16_t>(banded != 0, msa != 0)
+                          : size_bits == 16 ? v1_kernel<int32_t, int16_t>(banded != 0, msa != 0)
+                                            : v1_kernel<int32_t, int32_t>(banded != 0, msa != 0);
+    return {fn, kWave, size_t((lds_bytes + 15) & ~15)};
+}
 
 // Workgroups of the planned LDS or banded kernel that are resident on one CU
 // at once (the persistent grid is this times the CU count); 0 for the v1
@@ -1953,127 +2011,28 @@ int blocks_per_cu(K kfn, int threads, size_t lds)
 extern "C" int gwamd_internal_poa_blocks_per_cu(const gwamd::poa::Dims* d, int score_bits, int size_bits, int banded,
                                                 int msa)
 {
-    using namespace gwamd::poa;
-    if (d->lds_kernel == 3 && banded)
-        return gwamd_internal_poa_band_blocks_per_cu(d, score_bits, size_bits, msa);
-    if (d->lds_kernel != 1 || banded || size_bits != 16 || (score_bits != 16 && score_bits != 32))
+    if (!d->lds_kernel)
         return 0;
-    const size_t lb = size_t(d->lds_bytes);
-#define GWAMD_LDS_OCC_W(CPL, NW, WD)                                                                          \
-    if (d->lds_cpl == CPL && d->lds_waves == NW && (score_bits == 32) == WD)                                   \
-    {                                                                                                          \
-        auto kt = poa_window_kernel_lds<true, CPL, NW, WD>;                                                    \
-        auto kf = poa_window_kernel_lds<false, CPL, NW, WD>;                                                   \
-        if (lb > 65536 &&                                                                                      \
-            (hipFuncSetAttribute(reinterpret_cast<const void*>(msa ? kt : kf),                                 \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(lb)) != hipSuccess))          \
-            return 0;                                                                                          \
-        return msa ? blocks_per_cu(kt, kWave * NW, lb) : blocks_per_cu(kf, kWave * NW, lb);                    \
-    }
-#define GWAMD_LDS_OCC(CPL, NW) GWAMD_LDS_OCC_W(CPL, NW, false)
-    // 32-bit scores: (columns per lane, waves) planned by poa_batch.cpp
-    GWAMD_LDS_OCC_W(8, 1, true)
-    GWAMD_LDS_OCC_W(8, 2, true)
-    GWAMD_LDS_OCC_W(8, 4, true)
-    GWAMD_LDS_OCC_W(8, 8, true)
-    GWAMD_LDS_OCC_W(16, 8, true)
-    GWAMD_LDS_OCC(8, 1)
-    GWAMD_LDS_OCC(16, 1)
-    GWAMD_LDS_OCC(24, 1)
-    GWAMD_LDS_OCC(32, 1)
-    GWAMD_LDS_OCC(8, 2)
-    GWAMD_LDS_OCC(8, 3)
-    GWAMD_LDS_OCC(8, 4)
-    GWAMD_LDS_OCC(16, 4)
-    GWAMD_LDS_OCC(4, 4)
-#undef GWAMD_LDS_OCC
-#undef GWAMD_LDS_OCC_W
-    return 0;
+    const KernelRef k = gwamd_internal_poa_kernel(d, score_bits, size_bits, banded, msa);
+    int n             = 0;
+    if (prepare(k) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k.fn, k.threads, k.dynamic_lds) != hipSuccess)
+        return 0;
+    return n;
 }
 
-// Internal launch ABI used by the C++ batch (poa_batch.cpp).
+// Internal launch ABI used by the C++ batch (poa_batch.cpp): one workgroup per
+// window, or the persistent grid of one per scratch slot.
 extern "C" hipError_t gwamd_internal_poa_launch(const gwamd::poa::Buffers* b, const gwamd::poa::Dims* d,
                                        const gwamd::poa::Scores* sc, int score_bits, int size_bits, int banded,
                                        int msa, hipStream_t stream)
 {
-    using namespace gwamd::poa;
     if (b->num_windows <= 0)
         return hipSuccess;
-    dim3 grid(b->num_windows), block(kWave);
-    if (d->lds_kernel && b->head)
-        grid = dim3(b->num_slots); // persistent grid: one workgroup per scratch slot
-    if (d->lds_kernel == 3 && banded)
-        return gwamd_internal_poa_band_launch(b, d, sc, score_bits, size_bits, msa, stream);
-    if (d->lds_kernel == 1 && !banded && size_bits == 16 && (score_bits == 16 || score_bits == 32))
-    {
-        const size_t lb = size_t(d->lds_bytes);
-#define GWAMD_LDS_LAUNCH_W(CPL, NW, WD)                                                                        \
-    if (d->lds_cpl == CPL && d->lds_waves == NW && (score_bits == 32) == WD)                                   \
-    {                                                                                                          \
-        const dim3 blk(kWave * NW);                                                                            \
-        auto kt = poa_window_kernel_lds<true, CPL, NW, WD>;                                                    \
-        auto kf = poa_window_kernel_lds<false, CPL, NW, WD>;                                                   \
-        if (lb > 65536)                                                                                        \
-        {                                                                                                      \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(msa ? kt : kf),             \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(lb));     \
-            if (e != hipSuccess)                                                                               \
-                return e;                                                                                      \
-        }                                                                                                      \
-        if (msa)                                                                                               \
-            hipLaunchKernelGGL(kt, grid, blk, lb, stream, *b, *d, *sc);                                        \
-        else                                                                                                   \
-            hipLaunchKernelGGL(kf, grid, blk, lb, stream, *b, *d, *sc);                                        \
-        return hipGetLastError();                                                                              \
-    }
-#define GWAMD_LDS_LAUNCH(CPL, NW) GWAMD_LDS_LAUNCH_W(CPL, NW, false)
-        // (columns per lane, waves per window) pairs planned by poa_batch.cpp
-        GWAMD_LDS_LAUNCH_W(8, 1, true)
-        GWAMD_LDS_LAUNCH_W(8, 2, true)
-        GWAMD_LDS_LAUNCH_W(8, 4, true)
-        GWAMD_LDS_LAUNCH_W(8, 8, true)
-        GWAMD_LDS_LAUNCH_W(16, 8, true)
-        GWAMD_LDS_LAUNCH(8, 1)
-        GWAMD_LDS_LAUNCH(16, 1)
-        GWAMD_LDS_LAUNCH(24, 1)
-        GWAMD_LDS_LAUNCH(32, 1)
-        GWAMD_LDS_LAUNCH(8, 2)
-        GWAMD_LDS_LAUNCH(8, 3)
-        GWAMD_LDS_LAUNCH(8, 4)
-        GWAMD_LDS_LAUNCH(16, 4)
-        GWAMD_LDS_LAUNCH(4, 4)
-        return hipErrorInvalidConfiguration;
-#undef GWAMD_LDS_LAUNCH
-#undef GWAMD_LDS_LAUNCH_W
-    }
-    const int lds_bytes = (d->max_seq_len > d->band_width + kBandPad ? d->max_seq_len : d->band_width + kBandPad) + 32;
-    const size_t lds    = size_t((lds_bytes + 15) & ~15);
-#define GWAMD_LAUNCH(ST, ZT, BD, MS)                                                                          \
-    hipLaunchKernelGGL((poa_window_kernel<ST, ZT, BD, MS>), grid, block, lds, stream, *b, *d, *sc);           \
-    return hipGetLastError();
-#define GWAMD_DISPATCH_MODE(ST, ZT)           \
-    if (banded)                               \
-    {                                         \
-        if (msa)                              \
-        {                                     \
-            GWAMD_LAUNCH(ST, ZT, true, true)  \
-        }                                     \
-        GWAMD_LAUNCH(ST, ZT, true, false)     \
-    }                                         \
-    if (msa)                                  \
-    {                                         \
-        GWAMD_LAUNCH(ST, ZT, false, true)     \
-    }                                         \
-    GWAMD_LAUNCH(ST, ZT, false, false)
-    if (score_bits == 16)
-    {
-        GWAMD_DISPATCH_MODE(int16_t, int16_t)
-    }
-    if (size_bits == 16)
-    {
-        GWAMD_DISPATCH_MODE(int32_t, int16_t)
-    }
-    GWAMD_DISPATCH_MODE(int32_t, int32_t)
-#undef GWAMD_DISPATCH_MODE
-#undef GWAMD_LAUNCH
+    const KernelRef k = gwamd_internal_poa_kernel(d, score_bits, size_bits, banded, msa);
+    if (const hipError_t e = prepare(k))
+        return e;
+    void* args[] = {const_cast<Buffers*>(b), const_cast<Dims*>(d), const_cast<Scores*>(sc)};
+    return hipLaunchKernel(k.fn, dim3((d->lds_kernel && b->head) ? b->num_slots : b->num_windows), dim3(k.threads),
+                           args, k.dynamic_lds, stream);
 }

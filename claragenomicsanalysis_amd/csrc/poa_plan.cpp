@@ -1,0 +1,224 @@
+// The POA kernel plan: which kernel a batch of given capacities runs and the
+// layout of its LDS image and HBM side buffers, as a function of the
+// capacities and the tuning switches alone.  No HIP in here, so the plan can
+// be examined (and sanitized) on the host: gwamd_internal_poa_plan.
+#include "poa_plan.hpp"
+
+#include <algorithm>
+#include <iterator>
+#include <stdexcept>
+
+namespace gwamd
+{
+namespace poa
+{
+
+// LDS-resident kernel (poa_window_kernel_lds): full alignment with 16-bit
+// scores and node ids.  LDS image per window: read | ring of E rows (also
+// the traceback tile and the add-alignment scratch) | row program |
+// predecessor lists | shared words; the topological sort reuses everything
+// below the shared words.  Span carries of multi-sweep reads live in HBM
+// next to the traceback codes.
+void plan_lds_layout(Dims& dims, bool banded, int size_bits, int score_bits, const PoaTuning& tune)
+{
+    dims.lds_kernel = 0;
+    if (tune.force_v1)
+        return;
+    // 16-bit node ids; 16-bit scores, or 32-bit ones (the reference's
+    // use32bitScore batches: nw_forward_lds_w)
+    if (banded || size_bits != 16 || (score_bits != 16 && score_bits != 32))
+        return;
+    const bool wide      = score_bits == 32;
+    auto a16             = [](int64_t v) { return (v + 15) & ~int64_t(15); };
+    int ring_rows        = 8;
+    const int64_t read_b = lds_read_bytes(dims.max_seq_len);
+    // forward pass shape: CPL columns per lane on NW waves; a sweep covers
+    // NW*64*CPL read columns, longer reads take several sweeps
+    // (GWAMD_POA_LDS_SHAPE="cpl,waves": any row of kLdsShapes of this
+    // width).  32-bit scores: one sweep up to 4,096 columns (8 waves), 8,192
+    // with 16 columns per lane
+    int cpl = 8, nw = 1;
+    const int ms = dims.max_seq_len;
+    if (!wide && ms > 512)
+        nw = 2;
+    if (wide)
+    {
+        nw  = ms <= 512 ? 1 : (ms <= 1024 ? 2 : (ms <= 2048 ? 4 : 8));
+        cpl = ms <= 4096 ? 8 : 16;
+    }
+    if (tune.lds_shape)
+    {
+        const auto* e = std::end(kLdsShapes);
+        if (std::none_of(kLdsShapes, e, [&](const LdsShape& s) {
+                return s.cpl == tune.lds_cpl && s.waves == tune.lds_waves && s.wide == wide;
+            }))
+            throw std::invalid_argument("GWAMD_POA_LDS_SHAPE: unsupported columns/waves pair");
+        cpl = tune.lds_cpl, nw = tune.lds_waves;
+    }
+    const int ebytes     = wide ? 4 : 2;
+    // the one-wave graph update's scratch always fits the ring region
+    // (this is lds_add_wave0_bytes rounded up); the every-wave update's
+    // larger one is not planned for: the kernel runs it where
+    // lds_add_fits(max_seq_len, max_nodes, lds_rec_off - lds_ring_off)
+    const int64_t add_b  = 5 * a16(dims.max_seq_len + 16) + 2 * (int64_t(dims.max_nodes) + dims.max_seq_len);
+    const int64_t tile_b = int64_t(kTileRows) * kTileCols + kTbRankBytes;
+    const int64_t rec_b  = a16(int64_t(dims.max_nodes + 2) * 4);
+    const int64_t sh_b   = a16(wide ? kShBytesW(nw) : kShBytes(nw));
+    auto ring_bytes      = [&](int rows) {
+        return a16(std::max<int64_t>({int64_t(rows) * dims.score_stride * ebytes, tile_b, add_b}));
+    };
+    int64_t ring_b       = ring_bytes(ring_rows);
+    int64_t fixed        = read_b + ring_b + rec_b + sh_b;
+    int64_t target       = 40960 - 16; // 4 workgroups per CU incl. static LDS: one batch of
+                                       // 1024 windows is resident on the 256 CUs at once
+    if (wide)
+    {
+        // 32-bit rows are twice as wide: two windows per CU when their
+        // images fit, else one; an 8-row ring when it fits, else 4 rows
+        // (predecessors farther back go through the HBM spill rows)
+        int64_t chosen = 0;
+        for (int64_t budget : {int64_t(81920 - 16), int64_t(163840 - 64)})
+        {
+            for (int rows : {8, 4})
+            {
+                const int64_t rb = ring_bytes(rows);
+                const int64_t fx = read_b + rb + rec_b + sh_b;
+                if (fx + 2048 <= budget)
+                {
+                    ring_rows = rows, ring_b = rb, fixed = fx, chosen = budget;
+                    break;
+                }
+            }
+            if (chosen)
+                break;
+        }
+        if (!chosen)
+            return;
+        target = chosen;
+    }
+    int64_t xl_cap       = std::max<int64_t>(1024, (target - fixed) / 2);
+    xl_cap               = std::min<int64_t>(xl_cap, 65535);
+    int64_t total        = fixed + a16(xl_cap * 2);
+    total += a16(tune.lds_pad); // diagnostic: fewer windows per CU
+    if (total > (wide ? 163840 - 64 : 65536))
+        return;
+    dims.lds_kernel    = 1;
+    dims.tb_rank       = tune.tb_rank;
+    dims.lds_ring_off  = int32_t(read_b);
+    dims.lds_ring_rows = ring_rows;
+    dims.lds_rec_off   = int32_t(read_b + ring_b);
+    dims.lds_xl_off    = int32_t(read_b + ring_b + rec_b);
+    dims.lds_xl_cap    = int32_t(xl_cap);
+    dims.lds_sh_off    = int32_t(read_b + ring_b + rec_b + a16(xl_cap * 2));
+    dims.lds_bytes     = int32_t(total);
+    dims.lds_cpl       = cpl;
+    dims.lds_waves     = nw;
+    dims.code_stride   = int32_t(a16(int64_t(dims.max_seq_len) + 48));
+    // HBM side buffer per window: traceback codes, span carries
+    const int64_t code_b = int64_t(dims.score_rows) * dims.code_stride;
+    const int64_t cr_b   = a16(int64_t(dims.max_nodes + 2) * ebytes);
+    dims.aux_carry_off  = int32_t(code_b);
+    dims.aux_stride     = code_b + cr_b;
+}
+
+// Banded kernel (poa_window_kernel_band, poa_band.hip): band widths 128 to
+// 1,024 in steps of 128 (2 to 16 cells per lane), gap <= 0.  LDS image per window: staged
+// read | work region (row-program flags, the 16-row ring of band rows, the
+// traceback tile, the add-alignment scratch; the topological sort also
+// reuses the read) | shared words.  Windows per CU: 4, 2 or 1, the most
+// that leave room for the work region at this batch's maximum sizes.
+void plan_band_kernel(Dims& dims, bool banded, int gap, int score_bits, const PoaTuning& tune)
+{
+    if (!banded || dims.lds_kernel || tune.force_v1)
+        return;
+    const int bw = dims.band_width;
+    // every band width the reference accepts up to 1,024 (multiples of
+    // 128, batch.hpp:85-94): CPL = bw / 64 cells per lane, one
+    // object per CPL (poa_band_c<CPL>.o)
+    if (bw % 128 != 0 || bw < 128 || bw > 1024 || gap > 0)
+        return;
+    auto a16          = [](int64_t v) { return (v + 15) & ~int64_t(15); };
+    const int cpl     = bw / 64;
+    const int sbytes  = score_bits / 8;
+    // band row: position idx + cpl - 1, whole cpl-cell groups (66-67 of them)
+    const int rowsz   = (bw + kBandPad + cpl + cpl - 1) / cpl * cpl;
+    const int64_t ms  = dims.max_seq_len, mn = dims.max_nodes;
+    const int64_t read_b  = a16(kReadGuard + ms + bw + 48);
+    const int64_t sh_b    = 64;
+    const int ring_rows   = band_ring_rows(cpl), tile_rows = band_tile_rows(cpl);
+    const int64_t ring_b  = a16(int64_t(ring_rows) * rowsz * sbytes) + 4 * 256 * 4 + 1024 * 4; // + record staging
+    const int64_t tile_b  = a16(int64_t(tile_rows) * bw + 64 * 16 + 512 + kTbRankBytes); // codes +
+                                                                  // per-row decode info + walk tables
+    const int64_t flags_b = 2 * a16(mn + 2); // row program: spill and far flags
+    const int64_t add_b   = 7 * a16(ms + 16) + a16(2 * (mn + ms + 16)); // + the edge-slot bytes
+    // anti-diagonal forward pass (poa_band_ad.hpp): a kAdRing-row ring and
+    // one dummy word per lane.  Default: whenever the windows-per-CU
+    // choice below leaves room for it (large windows, one or two per CU);
+    // GWAMD_BAND_FWD=ad|row forces it on (planning for it) or off.
+    const int64_t ad_b    = a16(int64_t(kAdRing) * rowsz * sbytes + kWave * sbytes) +
+                         a16(mn / 8 + 64); // + the real-row bitmap
+    // (band widths 128 / 256 only: its ring of kAdRing rows is too large beyond)
+    const bool force_ad   = tune.band_fwd == 1 && cpl <= 4;
+    const bool no_ad      = tune.band_fwd == 2;
+    const int64_t min_w   = std::max({ring_b, tile_b, flags_b, force_ad ? ad_b : int64_t(0)});
+    const int64_t want_w  = std::max(min_w, add_b);
+    const int64_t kStatic = 256; // static __shared__ bytes of the kernel
+    int64_t total         = 0;
+    int chosen_per_cu     = 1;
+    for (int per_cu : {4, 2, 1})
+    {
+        const int64_t budget = (163840 / per_cu - kStatic) & ~int64_t(15);
+        if ((!force_ad && read_b + want_w + sh_b <= budget) || per_cu == 1)
+        {
+            total         = budget;
+            chosen_per_cu = per_cu;
+            break;
+        }
+    }
+    const int64_t work = total - read_b - sh_b;
+    if (work < min_w)
+        return;
+    dims.lds_kernel     = 3;
+    // the pass runs kAdMaxWaves waves per window (GWAMD_BAND_AD_WAVES: fewer): one window per CU
+    dims.band_ad        = (!no_ad && cpl <= 4 && chosen_per_cu == 1 && work >= ad_b) ? tune.band_ad_waves : 0;
+    dims.tb_rank        = tune.tb_rank;
+    dims.lds_cpl        = cpl;
+    dims.lds_waves      = 1;
+    dims.lds_bytes      = int32_t(total);
+    dims.lds_ring_off   = int32_t(read_b);
+    dims.lds_ring_rows  = ring_rows;
+    dims.lds_work_bytes = int32_t(work);
+    dims.lds_sh_off     = int32_t(read_b + work);
+    dims.score_stride   = rowsz; // spill rows: band row at position idx + cpl - 1
+    dims.code_stride    = bw;
+    const int64_t rows   = dims.score_rows;
+    int64_t o            = a16(rows * bw); // codes
+    dims.aux_reca_off   = int32_t(o);
+    o += a16(rows * 4);
+    dims.aux_recb_off = int32_t(o);
+    o += a16(rows * 4);
+    dims.aux_col0_off = int32_t(o);
+    o += a16(rows * 4);
+    dims.aux_flag_off = int32_t(o);
+    o += a16(rows);
+    dims.aux_xl_off = int32_t(o);
+    dims.aux_xl_cap = int32_t(2 * mn + 64);
+    o += a16(int64_t(dims.aux_xl_cap) * 4);
+    dims.aux_bx_off = int32_t(o);
+    o += a16((rows / 256 + 2) * 4);
+    dims.aux_recc_off = int32_t(o);
+    o += a16(rows * 4);
+    dims.aux_rece_off = int32_t(o);
+    o += a16(rows * 4);
+    dims.aux_stride = o;
+}
+
+void plan_kernels(Dims& dims, bool banded, int gap, int score_bits, int size_bits, const PoaTuning& tune)
+{
+    plan_lds_layout(dims, banded, size_bits, score_bits, tune);
+    plan_band_kernel(dims, banded, gap, score_bits, tune);
+    dims.diag = tune.diag;
+}
+
+} // namespace poa
+} // namespace gwamd

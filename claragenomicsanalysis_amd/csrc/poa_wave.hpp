@@ -100,16 +100,16 @@ __device__ __forceinline__ void finish_window(const Buffers& b, const Dims& d, i
     {
         uint16_t* cov_out = b.cov + size_t(w) * d.max_consensus;
         // by the wave on a compact copy of the graph in the free LDS when it
-        // fits (poa_consensus.hpp), else by lane 0 in HBM.  Dims::diag bit 4
+        // fits (poa_consensus.hpp), else by lane 0 in HBM.  kDiagConsensusHbm
         // (GWAMD_CONSENSUS=hbm) keeps the HBM path, bits 16-31
         // (GWAMD_CONSENSUS_LDS_BYTES) cap the LDS bytes offered
         int len = 0;
         int cst = graph_status;
         if (cst == kSuccess && nseq > 0)
         {
-            const int cap = (d.diag >> 16) & 0xffff;
+            const int cap = (d.diag >> kDiagConsLdsShift) & 0xffff;
             consensus_window<SizeT, kInst>(g, node_count, cscore, cpred, cons_out, cov_out, d.max_consensus, scratch,
-                                    cap ? min(cap, scratch_bytes) : scratch_bytes, (d.diag & 16) != 0, lane, sh_len,
+                                    cap ? min(cap, scratch_bytes) : scratch_bytes, (d.diag & kDiagConsensusHbm) != 0, lane, sh_len,
                                     sh_status, len, cst);
         }
         if (lane == 0)
@@ -130,7 +130,7 @@ __device__ __forceinline__ void finish_window(const Buffers& b, const Dims& d, i
         olap(0);
         const bool lds_done = graph_status == kSuccess && nseq > 0 &&
                               topsort_racon_lds<SizeT>(g, node_count, scratch, scratch_bytes, lane, cpred, &lds_cols,
-                                                       (d.diag & 8) ? nullptr : cscore);
+                                                       (d.diag & kDiagRaconV1) ? nullptr : cscore);
         olap(1);
         if (lane == 0)
         {
@@ -1578,7 +1578,7 @@ __device__ __forceinline__ bool topsort_lds(WinGraph<SizeT> g, int n, GWAMD_LDS 
     // (all n of them, or for graphs too large for that a ring of the last
     // kQRing pushes: a pop at q reads the ring while tail - q < kQRing, the
     // node word otherwise; the queue holds about the graph's width.
-    // force_ring: Dims::diag bit 0, parity tests of the ring mode with a
+    // force_ring: kDiagTopsortRing, parity tests of the ring mode with a
     // 4-entry ring: ordinary windows queue 5-6 nodes at once, so they run
     // past it)
     constexpr int kQRing = 1024;
@@ -2653,17 +2653,17 @@ struct TbWin
         wi0   = i;
         wj0   = j;
     }
-    // mode: the tb_rank bits (bit 1 strips, bit 2 32 x 4 strips, bits 3-5
-    // rows above the line + 1, 0: default); strip windows start with the
+    // mode: Dims::tb_rank (kTb*, poa_common.hpp); strip windows start with the
     // slope of the whole path (rows x 16 / cols) and keep row_span() below
     // tile_rows
     __device__ __forceinline__ void init(int mode, int rows, int cols_, int tile_rows)
     {
-        sh   = (mode & 4) ? 2 : 3;
+        sh   = (mode & kTbStrip32) ? 2 : 3;
         // default 3 above (16 x 8) measured best of 1-4 (profiles/r3ad_tbabove)
-        ab   = ((mode >> 3) & 7) ? min(((mode >> 3) & 7) - 1, (1 << sh) - 1) : (sh == 3 ? 3 : 1);
+        const int above = (mode >> kTbAboveShift) & kTbAboveMask;
+        ab   = above ? min(above - 1, (1 << sh) - 1) : (sh == 3 ? 3 : 1);
         smax = (16 * (tile_rows - (1 << sh))) / (cols() - 1);
-        next = !(mode & 2) ? 0
+        next = !(mode & kTbStrips) ? 0
                            : (cols_ > 0 ? min(max((16 * rows + cols_ / 2) / cols_, kTbSlopeMin), smax) : kTbSlopeMin);
         slope = next;
     }

@@ -118,7 +118,7 @@ def test_banded_parity_synthetic(bw):
 def test_banded_other_widths(bw, variant, monkeypatch):
     # every other band width the reference accepts up to 1,024 (multiples of
     # 128, batch.hpp:85-94): the LDS band kernel with bw / 64 cells per lane
-    # (poa_band_c<CPL>.hip), and the global-memory kernel on the same windows;
+    # (poa_band_c<CPL>.o), and the global-memory kernel on the same windows;
     # the windows include reads much shorter than the band, empty and
     # one-base reads and a 60-read window (nodes with many predecessors)
     if variant == "v1":
@@ -192,6 +192,7 @@ def test_full_int32_lds_shapes(shape, out, monkeypatch):
     msa = out == "msa"
     b = run_gpu(wins, max_seq, 40, output_type=out)
     assert b.get_types()[0] == 32 and b.kernel_variant() == 2
+    assert b.get_grid()[1] > 0  # the planned kernel has an occupancy answer: a persistent grid
     got = b.get_msa() if msa else b.get_consensus()
     for i, w in enumerate(wins):
         r = run_oracle(w, max_seq, 40, msa=msa, score_bits=32)
@@ -319,6 +320,7 @@ def test_lds_forward_shapes(shape, monkeypatch):
                  b"ACGT" * 128, b"C" * 1100])
     b = run_gpu(wins, max_seq, 12)
     assert b.kernel_variant() == 2
+    assert b.get_grid()[1] > 0  # the planned kernel has an occupancy answer: a persistent grid
     cons, cov, st = b.get_consensus()
     for i, w in enumerate(wins):
         r = run_oracle(w, max_seq, 12)
@@ -432,6 +434,7 @@ def test_band_anti_diagonal(bw, max_seq, out, monkeypatch):
         monkeypatch.setenv("GWAMD_BAND_FWD", fwd)
         b = run_gpu(wins, max_seq, 60, banded=True, bw=bw, output_type=out)
         assert b.kernel_variant() == (4 if fwd == "ad" else 3)
+        assert b.get_grid()[1] > 0  # the planned kernel has an occupancy answer: a persistent grid
         res[fwd] = b.get_msa() if msa else b.get_consensus()
         res[fwd + "_cells"] = b.get_stats()[0]
         sbits = b.get_types()[0]

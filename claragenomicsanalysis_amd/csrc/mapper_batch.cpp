@@ -1,15 +1,19 @@
-// Host side of cudamapper's minimizer index and anchor matcher: the
-// reference's C++ API (Index::create_index, Matcher::create_matcher;
-// cudamapper/src/index.cu, matcher.cu) and the C ABI of
-// include/gwamd_cudamapper.h.  Device work is in mapper_index.hip and
-// mapper_match.hip.  Every argument is checked here, before any device call.
+// Host side of cudamapper's minimizer index, anchor matcher and overlapper:
+// the reference's C++ API (Index::create_index, Matcher::create_matcher,
+// OverlapperTriggered::get_overlaps, Overlapper::post_process_overlaps;
+// cudamapper/src/index.cu, matcher.cu, overlapper_triggered.cu, overlapper.cpp)
+// and the C ABI of include/gwamd_cudamapper.h.  Device work is in
+// mapper_index.hip, mapper_match.hip and mapper_overlap.hip.  Every argument
+// is checked here, before any device call.
 #include <claraparabricks/genomeworks/cudamapper/index.hpp>
 #include <claraparabricks/genomeworks/cudamapper/matcher.hpp>
+#include <claraparabricks/genomeworks/cudamapper/overlapper_triggered.hpp>
 
 #include "../../include/gwamd_cudamapper.h"
 #include "allocator_handle.hpp"
 #include "mapper_common.hpp"
 
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -46,6 +50,23 @@ void check_read_lengths(const int64_t* offsets, int64_t n)
         if (offsets[i + 1] - offsets[i] >= (int64_t(1) << 31))
             throw std::invalid_argument("reads must be shorter than 2^31 bases");
     }
+}
+
+gm::OverlapParams check_overlap_parameters(int64_t min_residues, int64_t min_overlap_len,
+                                           int64_t min_bases_per_residue, float min_overlap_fraction)
+{
+    // the reference converts the three integers to size_t
+    if (min_residues < 0 || min_overlap_len < 0 || min_bases_per_residue < 0)
+        throw std::invalid_argument("min_residues, min_overlap_len and min_bases_per_residue must not be negative");
+    if (min_overlap_fraction != min_overlap_fraction)
+        throw std::invalid_argument("min_overlap_fraction is not a number");
+    return gm::OverlapParams{min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction};
+}
+
+void check_anchor_count(int64_t n)
+{
+    if (n < 0 || n > gm::kDefaultMaxAnchors)
+        throw std::invalid_argument("the number of anchors must be between 0 and 2^31, got " + std::to_string(n));
 }
 
 } // namespace
@@ -164,6 +185,138 @@ std::unique_ptr<Matcher> Matcher::create_matcher(DefaultDeviceAllocator allocato
     return m;
 }
 
+static_assert(sizeof(Overlap) == sizeof(gm::OverlapRecord) &&
+                  offsetof(Overlap, relative_strand) == offsetof(gm::OverlapRecord, relative_strand) &&
+                  offsetof(Overlap, num_residues_) == offsetof(gm::OverlapRecord, num_residues) &&
+                  offsetof(Overlap, overlap_complete) == offsetof(gm::OverlapRecord, overlap_complete),
+              "OverlapRecord must match cudamapper::Overlap");
+
+OverlapperTriggered::OverlapperTriggered(DefaultDeviceAllocator allocator, const hipStream_t stream)
+    : allocator_(allocator)
+    , stream_(stream)
+{
+}
+
+void OverlapperTriggered::get_overlaps(std::vector<Overlap>& fused_overlaps, const device_buffer<Anchor>& d_anchors,
+                                       int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                       float min_overlap_fraction)
+{
+    const gm::OverlapParams params =
+        check_overlap_parameters(min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction);
+    check_anchor_count(d_anchors.size());
+    std::vector<gm::OverlapRecord> records;
+    gm::get_overlaps(records, reinterpret_cast<const gm::AnchorRecord*>(d_anchors.data()), d_anchors.size(), params,
+                     allocator_.budget(), stream_);
+    fused_overlaps.resize(records.size());
+    if (!records.empty())
+        std::memcpy(static_cast<void*>(fused_overlaps.data()), records.data(), records.size() * sizeof(Overlap));
+}
+
+namespace
+{
+
+int32_t abs_of(uint32_t difference) // abs(int) of a difference of two positions
+{
+    const int32_t d = int32_t(difference);
+    return d < 0 ? int32_t(0u - difference) : d;
+}
+
+// whether overlap b can be fused to its predecessor a (overlaps_mergable, overlapper.cpp:29-91)
+bool mergeable(const Overlap& a, const Overlap& b)
+{
+    const bool forward = a.relative_strand == RelativeStrand::Forward && b.relative_strand == RelativeStrand::Forward;
+    const bool reverse = a.relative_strand == RelativeStrand::Reverse && b.relative_strand == RelativeStrand::Reverse;
+    if (!forward && !reverse)
+        return false;
+    if (a.query_read_id_ != b.query_read_id_ || a.target_read_id_ != b.target_read_id_)
+        return false;
+    const int32_t query_gap = abs_of(b.query_start_position_in_read_ - a.query_end_position_in_read_);
+    // on the reverse strand the target positions fall while the query positions rise
+    const int32_t target_gap = reverse ? abs_of(a.target_start_position_in_read_ - b.target_end_position_in_read_)
+                                       : abs_of(b.target_start_position_in_read_ - a.target_end_position_in_read_);
+    if (query_gap < 500 && target_gap < 500)
+        return true;
+    // float32 quotients compared with double constants, as the reference writes them
+    const float gap_ratio = float(std::min(query_gap, target_gap)) / float(std::max(query_gap, target_gap));
+    if (gap_ratio > 0.8)
+        return true;
+    const uint32_t query_length = (a.query_end_position_in_read_ - a.query_start_position_in_read_) +
+                                  (b.query_end_position_in_read_ - b.query_start_position_in_read_);
+    const uint32_t target_length = (a.target_end_position_in_read_ - a.target_start_position_in_read_) +
+                                   (b.target_end_position_in_read_ - b.target_start_position_in_read_);
+    return float(query_gap) / float(query_length) < 0.2 && float(target_gap) / float(target_length) < 0.2;
+}
+
+} // namespace
+
+void Overlapper::post_process_overlaps(std::vector<Overlap>& overlaps, const bool drop_fused_overlaps)
+{
+    const size_t n = overlaps.size();
+    std::vector<bool> fused(drop_fused_overlaps ? n : 0);
+    std::vector<Overlap> added;
+    bool in_fuse = false;
+    Overlap fusion{}; // the overlap before the current one, with the fusion's span and residues
+    uint32_t query_start = 0, query_end = 0, target_start = 0, target_end = 0, residues = 0;
+    const auto close = [&] {
+        fusion.query_start_position_in_read_  = query_start;
+        fusion.query_end_position_in_read_    = query_end;
+        fusion.target_start_position_in_read_ = target_start;
+        fusion.target_end_position_in_read_   = target_end;
+        fusion.num_residues_                  = residues;
+        added.push_back(fusion);
+    };
+    for (size_t i = 1; i < n; i++)
+    {
+        const Overlap& prev = overlaps[i - 1];
+        const Overlap& cur  = overlaps[i];
+        // the reference copies the other fields of a fusion from the overlap
+        // before the last one it looked at: the fusion's last overlap when the
+        // next one ends it, its last but one when the list ends in it
+        fusion = prev;
+        if (mergeable(prev, cur))
+        {
+            if (drop_fused_overlaps)
+                fused[i] = fused[i - 1] = true;
+            const bool is_forward = cur.relative_strand == RelativeStrand::Forward;
+            if (!in_fuse)
+            {
+                in_fuse      = true;
+                residues     = prev.num_residues_ + cur.num_residues_;
+                query_start  = prev.query_start_position_in_read_;
+                query_end    = cur.query_end_position_in_read_;
+                target_start = is_forward ? prev.target_start_position_in_read_ : cur.target_start_position_in_read_;
+                target_end   = is_forward ? cur.target_end_position_in_read_ : prev.target_end_position_in_read_;
+            }
+            else
+            {
+                residues += cur.num_residues_;
+                query_end = cur.query_end_position_in_read_;
+                if (is_forward)
+                    target_end = cur.target_end_position_in_read_;
+                else
+                    target_start = cur.target_start_position_in_read_;
+            }
+        }
+        else if (in_fuse)
+        {
+            in_fuse = false;
+            close();
+        }
+    }
+    if (in_fuse)
+        close();
+    if (drop_fused_overlaps)
+    {
+        // drop_overlaps_by_mask: the mask covers the overlaps that came in
+        size_t kept = 0;
+        for (size_t i = 0; i < n; i++)
+            if (!fused[i])
+                overlaps[kept++] = overlaps[i];
+        overlaps.resize(kept);
+    }
+    overlaps.insert(overlaps.end(), added.begin(), added.end());
+}
+
 } // namespace cudamapper
 } // namespace genomeworks
 } // namespace claraparabricks
@@ -270,6 +423,100 @@ int32_t match(const gwamd_index* query_index, const gwamd_index* target_index, i
     });
 }
 
+static_assert(sizeof(gwamd_overlap) == sizeof(gm::OverlapRecord) && sizeof(gwamd_overlap) == sizeof(cm::Overlap) &&
+                  offsetof(gwamd_overlap, relative_strand) == offsetof(gm::OverlapRecord, relative_strand) &&
+                  offsetof(gwamd_overlap, num_residues) == offsetof(gm::OverlapRecord, num_residues) &&
+                  offsetof(gwamd_overlap, overlap_complete) == offsetof(gm::OverlapRecord, overlap_complete),
+              "gwamd_overlap must match cudamapper::Overlap");
+
+void clear_overlap_outputs(gwamd_overlap** overlaps, int64_t* num_overlaps, int64_t* num_anchors = nullptr)
+{
+    if (overlaps)
+        *overlaps = nullptr;
+    if (num_overlaps)
+        *num_overlaps = 0;
+    if (num_anchors)
+        *num_anchors = 0;
+}
+
+template <typename Record>
+void hand_over(const std::vector<Record>& records, gwamd_overlap** overlaps, int64_t* num_overlaps)
+{
+    static_assert(sizeof(Record) == sizeof(gwamd_overlap), "records are copied as bytes");
+    if (records.empty())
+        return;
+    std::unique_ptr<gwamd_overlap[]> h(new gwamd_overlap[records.size()]);
+    std::memcpy(static_cast<void*>(h.get()), static_cast<const void*>(records.data()),
+                records.size() * sizeof(gwamd_overlap));
+    *num_overlaps = int64_t(records.size());
+    *overlaps     = h.release();
+}
+
+int32_t overlaps_of_anchors(const gwamd_anchor* anchors, int64_t n, int64_t min_residues, int64_t min_overlap_len,
+                            int64_t min_bases_per_residue, float min_overlap_fraction, int32_t device_id,
+                            const gm::Budget& budget, gwamd_overlap** overlaps, int64_t* num_overlaps)
+{
+    clear_overlap_outputs(overlaps, num_overlaps);
+    return guarded_map([&] {
+        if (!overlaps || !num_overlaps)
+            throw std::invalid_argument("overlaps or num_overlaps is NULL");
+        const gm::OverlapParams params =
+            check_overlap_parameters(min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction);
+        check_anchor_count(n);
+        if (n > 0 && !anchors)
+            throw std::invalid_argument("anchors is NULL");
+        if (device_id < 0)
+            throw std::invalid_argument("device_id must not be negative");
+        if (n == 0)
+            return int32_t(0);
+        gwamd::host::ScopedDevice dev(device_id);
+        gm::DevBuf<gm::AnchorRecord> d(size_t(n), budget);
+        GWAMD_HIP_CHECK(hipMemcpy(d.data(), anchors, size_t(n) * sizeof(gwamd_anchor), hipMemcpyHostToDevice));
+        std::vector<gm::OverlapRecord> records;
+        gm::get_overlaps(records, d.data(), n, params, budget, nullptr);
+        hand_over(records, overlaps, num_overlaps);
+        return int32_t(0);
+    });
+}
+
+int32_t match_overlaps(const gwamd_index* query_index, const gwamd_index* target_index, int64_t max_anchors,
+                       int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                       float min_overlap_fraction, const gm::Budget& budget, gwamd_overlap** overlaps,
+                       int64_t* num_overlaps, int64_t* num_anchors)
+{
+    clear_overlap_outputs(overlaps, num_overlaps, num_anchors);
+    return guarded_map([&] {
+        if (!query_index || !target_index || !overlaps || !num_overlaps)
+            throw std::invalid_argument("index, overlaps or num_overlaps is NULL");
+        if (max_anchors < -1)
+            throw std::invalid_argument("max_anchors must be -1 (the default of 2^31) or not negative");
+        const gm::OverlapParams params =
+            check_overlap_parameters(min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction);
+        const gm::IndexData& q = query_index->impl->data;
+        const gm::IndexData& t = target_index->impl->data;
+        if (q.representations.size() == 0 || t.representations.size() == 0)
+            return int32_t(0);
+        if (q.device_id != t.device_id)
+            throw std::invalid_argument("the two indices are on different devices");
+        gwamd::host::ScopedDevice dev(q.device_id);
+        gm::DevBuf<gm::AnchorRecord> d;
+        gm::match_anchors(d, q, t, max_anchors < 0 ? gm::kDefaultMaxAnchors : max_anchors, budget, nullptr);
+        std::vector<gm::OverlapRecord> records;
+        gm::get_overlaps(records, d.data(), int64_t(d.size()), params, budget, nullptr);
+        hand_over(records, overlaps, num_overlaps);
+        if (num_anchors)
+            *num_anchors = int64_t(d.size());
+        return int32_t(0);
+    });
+}
+
+int32_t allocator_is_null(gwamd_overlap** overlaps, int64_t* num_overlaps, int64_t* num_anchors = nullptr)
+{
+    clear_overlap_outputs(overlaps, num_overlaps, num_anchors);
+    gwamd::host::last_error() = "allocator is NULL";
+    return GWAMD_E_INVALID_ARGUMENT;
+}
+
 template <typename T>
 void copy_out(T* dst, const gm::DevBuf<T>& src)
 {
@@ -369,5 +616,69 @@ int32_t gwamd_match_anchors_with_allocator(const gwamd_index* query_index, const
 }
 
 void gwamd_anchors_free(gwamd_anchor* anchors) { delete[] anchors; }
+
+int32_t gwamd_get_overlaps(const gwamd_anchor* anchors, int64_t n, int64_t min_residues, int64_t min_overlap_len,
+                           int64_t min_bases_per_residue, float min_overlap_fraction, int32_t device_id,
+                           gwamd_overlap** overlaps, int64_t* num_overlaps)
+{
+    return overlaps_of_anchors(anchors, n, min_residues, min_overlap_len, min_bases_per_residue,
+                               min_overlap_fraction, device_id, nullptr, overlaps, num_overlaps);
+}
+
+int32_t gwamd_get_overlaps_with_allocator(const gwamd_anchor* anchors, int64_t n, int64_t min_residues,
+                                          int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                          float min_overlap_fraction, int32_t device_id,
+                                          gwamd_device_allocator* allocator, gwamd_overlap** overlaps,
+                                          int64_t* num_overlaps)
+{
+    if (!allocator)
+        return allocator_is_null(overlaps, num_overlaps);
+    return overlaps_of_anchors(anchors, n, min_residues, min_overlap_len, min_bases_per_residue,
+                               min_overlap_fraction, device_id, allocator->alloc.budget(), overlaps, num_overlaps);
+}
+
+int32_t gwamd_match_overlaps(const gwamd_index* query_index, const gwamd_index* target_index, int64_t max_anchors,
+                             int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                             float min_overlap_fraction, gwamd_overlap** overlaps, int64_t* num_overlaps,
+                             int64_t* num_anchors)
+{
+    return match_overlaps(query_index, target_index, max_anchors, min_residues, min_overlap_len,
+                          min_bases_per_residue, min_overlap_fraction, nullptr, overlaps, num_overlaps, num_anchors);
+}
+
+int32_t gwamd_match_overlaps_with_allocator(const gwamd_index* query_index, const gwamd_index* target_index,
+                                            int64_t max_anchors, int64_t min_residues, int64_t min_overlap_len,
+                                            int64_t min_bases_per_residue, float min_overlap_fraction,
+                                            gwamd_device_allocator* allocator, gwamd_overlap** overlaps,
+                                            int64_t* num_overlaps, int64_t* num_anchors)
+{
+    if (!allocator)
+        return allocator_is_null(overlaps, num_overlaps, num_anchors);
+    return match_overlaps(query_index, target_index, max_anchors, min_residues, min_overlap_len,
+                          min_bases_per_residue, min_overlap_fraction, allocator->alloc.budget(), overlaps,
+                          num_overlaps, num_anchors);
+}
+
+int32_t gwamd_post_process_overlaps(const gwamd_overlap* in, int64_t n, int32_t drop_fused_overlaps,
+                                    gwamd_overlap** out, int64_t* num_out)
+{
+    clear_overlap_outputs(out, num_out);
+    return guarded_map([&] {
+        if (!out || !num_out)
+            throw std::invalid_argument("out or num_out is NULL");
+        if (n < 0)
+            throw std::invalid_argument("the number of overlaps must not be negative");
+        if (n > 0 && !in)
+            throw std::invalid_argument("in is NULL");
+        std::vector<cm::Overlap> overlaps(static_cast<size_t>(n));
+        if (n > 0)
+            std::memcpy(static_cast<void*>(overlaps.data()), in, size_t(n) * sizeof(gwamd_overlap));
+        cm::Overlapper::post_process_overlaps(overlaps, drop_fused_overlaps != 0);
+        hand_over(overlaps, out, num_out);
+        return int32_t(0);
+    });
+}
+
+void gwamd_overlaps_free(gwamd_overlap* overlaps) { delete[] overlaps; }
 
 } // extern "C"

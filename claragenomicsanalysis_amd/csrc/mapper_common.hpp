@@ -1,5 +1,6 @@
-// Host-side declarations shared by the minimizer index and the matcher
-// (mapper_index.hip, mapper_match.hip, mapper_batch.cpp).
+// Host-side declarations shared by the minimizer index, the matcher and the
+// overlapper (mapper_index.hip, mapper_match.hip, mapper_overlap.hip,
+// mapper_batch.cpp).
 #pragma once
 
 #include <claraparabricks/genomeworks/utils/allocator.hpp>
@@ -9,6 +10,7 @@
 #include <cstdint>
 #include <memory>
 #include <utility>
+#include <vector>
 
 namespace gwamd
 {
@@ -132,6 +134,46 @@ void build_index(IndexData& out, const char* bases, const int64_t* offsets, uint
 // std::runtime_error when there are more than max_anchors.
 void match_anchors(DevBuf<AnchorRecord>& out, const IndexData& query, const IndexData& target, int64_t max_anchors,
                    const Budget& budget, hipStream_t stream);
+
+// cudamapper::Overlap (types.hpp), nine 32-bit words: the strand character and
+// overlap_complete each sit in the low byte of a word of their own
+struct OverlapRecord
+{
+    uint32_t query_read_id;
+    uint32_t target_read_id;
+    uint32_t query_start;
+    uint32_t target_start;
+    uint32_t query_end;
+    uint32_t target_end;
+    uint8_t relative_strand;
+    uint32_t num_residues;
+    uint8_t overlap_complete;
+};
+static_assert(sizeof(OverlapRecord) == 36, "OverlapRecord is nine 32-bit words");
+
+// The filter of OverlapperTriggered::get_overlaps; none of the integers is negative.
+struct OverlapParams
+{
+    int64_t min_residues          = 20;
+    int64_t min_overlap_len       = 50;
+    int64_t min_bases_per_residue = 50;
+    float min_overlap_fraction    = 0.9f;
+};
+
+// What each level of the overlapper left
+struct OverlapCounts
+{
+    int64_t chains = 0, kept_chains = 0, groups = 0, overlaps = 0;
+};
+
+constexpr int kOverlapTile = 2048; // anchors per workgroup of the chain-flag kernel (mapper_overlap.hip)
+
+// Overlaps of n device anchors sorted by (query_read_id, target_read_id,
+// query_position, target_position), in anchor order (host memory).  Throws
+// std::invalid_argument when an adjacent pair is out of order or a position is
+// 2^31 or more; the parameters are validated by the caller.
+void get_overlaps(std::vector<OverlapRecord>& out, const AnchorRecord* anchors, int64_t n, const OverlapParams& params,
+                  const Budget& budget, hipStream_t stream, OverlapCounts* counts = nullptr);
 
 } // namespace mapper
 } // namespace gwamd

@@ -1,11 +1,12 @@
-"""Minimizer index, anchor matcher, overlap alignment and PAF output of
-cudamapper over the C ABI (include/gwamd_cudamapper.h; reference
-cudamapper/include/.../index.hpp, matcher.hpp, cudamapper/src/main.cu:48-175
-and cudamapper/src/cudamapper_utils.cpp:30-112).
+"""Minimizer index, anchor matcher, overlapper, overlap alignment and PAF
+output of cudamapper over the C ABI (include/gwamd_cudamapper.h; reference
+cudamapper/include/.../index.hpp, matcher.hpp, overlapper.hpp,
+cudamapper/src/main.cu:48-175 and cudamapper/src/cudamapper_utils.cpp:30-112).
 
-Index builds the (k,w)-minimizer index of a range of reads on the GPU and
+Index builds the (k,w)-minimizer index of a range of reads on the GPU,
 match_anchors pairs the sketch elements of two indices that share a
-representation.
+representation, and get_overlaps chains sorted anchors into Overlap records
+(match_overlaps does both without bringing the anchors to the host).
 
 Overlaps are aligned with the MI355X global aligner (Hirschberg-Myers, the
 aligner create_aligner returns); a Reverse ('-') overlap aligns the query
@@ -85,6 +86,19 @@ def _declare(L):
     L.gwamd_match_anchors_with_allocator.argtypes = [vp, vp, i64, vp, P(vp), P(i64)]
     L.gwamd_anchors_free.restype = None
     L.gwamd_anchors_free.argtypes = [vp]
+    filter_args = [i64, i64, i64, C.c_float]
+    L.gwamd_get_overlaps.restype = i32
+    L.gwamd_get_overlaps.argtypes = [vp, i64] + filter_args + [i32, P(vp), P(i64)]
+    L.gwamd_get_overlaps_with_allocator.restype = i32
+    L.gwamd_get_overlaps_with_allocator.argtypes = [vp, i64] + filter_args + [i32, vp, P(vp), P(i64)]
+    L.gwamd_match_overlaps.restype = i32
+    L.gwamd_match_overlaps.argtypes = [vp, vp, i64] + filter_args + [P(vp), P(i64), P(i64)]
+    L.gwamd_match_overlaps_with_allocator.restype = i32
+    L.gwamd_match_overlaps_with_allocator.argtypes = [vp, vp, i64] + filter_args + [vp, P(vp), P(i64), P(i64)]
+    L.gwamd_post_process_overlaps.restype = i32
+    L.gwamd_post_process_overlaps.argtypes = [vp, i64, i32, P(vp), P(i64)]
+    L.gwamd_overlaps_free.restype = None
+    L.gwamd_overlaps_free.argtypes = [vp]
 
 
 def _check(rc):
@@ -270,3 +284,77 @@ def match_anchors(query_index, target_index, max_anchors=None, allocator=None):
         return out
     finally:
         L.gwamd_anchors_free(p)
+
+
+def _filter_args(min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction):
+    return [int(min_residues), int(min_overlap_len), int(min_bases_per_residue), float(min_overlap_fraction)]
+
+
+def _take_overlaps(L, p, n):
+    try:
+        arr = (Overlap * n.value).from_address(p.value) if n.value else []
+        out = []
+        for o in arr:
+            c = Overlap.__new__(Overlap)
+            C.memmove(C.byref(c), C.byref(o), C.sizeof(Overlap))
+            out.append(c)
+        return out
+    finally:
+        L.gwamd_overlaps_free(p)
+
+
+def get_overlaps(anchors, min_residues=20, min_overlap_len=50, min_bases_per_residue=50, min_overlap_fraction=0.9,
+                 device_id=0, allocator=None):
+    """Overlaps of sorted anchors (OverlapperTriggered::get_overlaps,
+    overlapper_triggered.cu:232-427), chained, fused and filtered on the GPU.
+
+    anchors: an ANCHOR_DTYPE array, as match_anchors returns it, or (query_read_id,
+    target_read_id, query_position_in_read, target_position_in_read) tuples.
+    Returns a list of Overlap in anchor order, ready for align_overlaps and
+    format_paf.  ValueError for a negative or NaN parameter, for anchors that
+    are not sorted and for a position of 2^31 or more."""
+    L = load_library()
+    if not (isinstance(anchors, np.ndarray) and anchors.dtype == ANCHOR_DTYPE):
+        anchors = np.array([tuple(a) for a in anchors], dtype=ANCHOR_DTYPE)
+    anchors = np.ascontiguousarray(anchors)
+    p, n = C.c_void_p(), C.c_int64()
+    args = [anchors.ctypes.data_as(C.c_void_p), len(anchors)] + \
+        _filter_args(min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction) + [int(device_id)]
+    if allocator is not None:
+        _check(L.gwamd_get_overlaps_with_allocator(*args, allocator._handle, C.byref(p), C.byref(n)))
+    else:
+        _check(L.gwamd_get_overlaps(*args, C.byref(p), C.byref(n)))
+    return _take_overlaps(L, p, n)
+
+
+def match_overlaps(query_index, target_index, min_residues=20, min_overlap_len=50, min_bases_per_residue=50,
+                   min_overlap_fraction=0.9, max_anchors=None, allocator=None, return_num_anchors=False):
+    """get_overlaps(match_anchors(query_index, target_index)) with the anchors
+    staying on the device (main.cu:227-240).  With return_num_anchors the
+    result is (overlaps, number of anchors)."""
+    L = load_library()
+    if not query_index._handle or not target_index._handle:
+        raise ValueError("index is closed")
+    cap = -1 if max_anchors is None else int(max_anchors)
+    if cap < 0 and max_anchors is not None:
+        raise ValueError("max_anchors must not be negative")
+    p, n, na = C.c_void_p(), C.c_int64(), C.c_int64()
+    args = [query_index._handle, target_index._handle, cap] + \
+        _filter_args(min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction)
+    if allocator is not None:
+        _check(L.gwamd_match_overlaps_with_allocator(*args, allocator._handle, C.byref(p), C.byref(n), C.byref(na)))
+    else:
+        _check(L.gwamd_match_overlaps(*args, C.byref(p), C.byref(n), C.byref(na)))
+    overlaps = _take_overlaps(L, p, n)
+    return (overlaps, na.value) if return_num_anchors else overlaps
+
+
+def post_process_overlaps(overlaps, drop_fused_overlaps=False):
+    """Overlapper::post_process_overlaps (overlapper.cpp:127-228) on the host:
+    the overlaps (without those that were fused, with drop_fused_overlaps)
+    followed by the fusion of every run of mergeable neighbours."""
+    L = load_library()
+    arr = _overlap_array(overlaps)
+    p, n = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_post_process_overlaps(arr, len(overlaps), int(bool(drop_fused_overlaps)), C.byref(p), C.byref(n)))
+    return _take_overlaps(L, p, n)

@@ -1,6 +1,6 @@
 /*
- * gwamd_cudamapper.h -- C ABI of cudamapper's minimizer index, anchor matcher
- * and overlap-alignment caller (libgwamd.so).
+ * gwamd_cudamapper.h -- C ABI of cudamapper's minimizer index, anchor matcher,
+ * overlapper and overlap-alignment caller (libgwamd.so).
  *
  * The reference aligns cudamapper overlaps inside its cudamapper executable
  * (cudamapper/src/main.cu:48-175: run_alignment_batch / align_overlaps) and
@@ -16,6 +16,13 @@
  *                          kmer_size, window_size, hash, filtering)        index.hpp:97-106
  *   gwamd_match_anchors    Matcher::create_matcher(allocator, query_index,
  *                          target_index)->anchors()                        matcher.hpp:45-48
+ *   gwamd_get_overlaps     OverlapperTriggered(allocator).get_overlaps(overlaps,
+ *                          d_anchors, min_residues, min_overlap_len,
+ *                          min_bases_per_residue, min_overlap_fraction)    overlapper_triggered.hpp:49-57
+ *   gwamd_match_overlaps   create_matcher + get_overlaps on its anchors    main.cu:227-240
+ *   gwamd_post_process_overlaps
+ *                          Overlapper::post_process_overlaps(overlaps,
+ *                          drop_fused_overlaps)                            overlapper.hpp:93
  *
  * Reads are passed as one byte array per side with n+1 offsets (read i is
  * bases[offsets[i], offsets[i+1])); names as NUL-separated strings with n+1
@@ -152,6 +159,57 @@ int32_t gwamd_match_anchors_with_allocator(const gwamd_index* query_index, const
                                            int64_t max_anchors, struct gwamd_device_allocator* allocator,
                                            gwamd_anchor** anchors, int64_t* num_anchors);
 void gwamd_anchors_free(gwamd_anchor* anchors);
+
+/* ---- overlapper: sorted anchors to overlaps -----------------------------------
+ *
+ * OverlapperTriggered::get_overlaps (overlapper_triggered.cu:232-427) on the
+ * GPU.  Neighbouring anchors of the same two reads whose query positions are
+ * less than 150 apart and whose target positions differ by less than 150 form
+ * a chain; chains of three anchors or more are kept; a kept chain joins the
+ * kept chain before it when their first anchors are on the same reads and
+ * |query distance - target distance| < 300; every such group becomes one
+ * overlap from its first anchor to its last, Reverse ('-') with the target
+ * positions swapped when they fall.  An overlap is returned when
+ *   num_residues >= min_residues,
+ *   max(query span, target span) / num_residues < min_bases_per_residue,
+ *   query span >= min_overlap_len and target span >= min_overlap_len,
+ *   query_read_id != target_read_id, and
+ *   target span / longer span > min_overlap_fraction, the same for the query
+ *   span (float32 quotients),
+ * in anchor order, in a host array owned by the library (free with
+ * gwamd_overlaps_free; NULL when there are none).  The reference's defaults
+ * are 20, 50, 50 and 0.9f (overlapper_triggered.hpp:49-54).
+ * GWAMD_E_INVALID_ARGUMENT, before any device call: a negative n or min_*, a
+ * NaN fraction, n > 2^31; and after the first kernel, with nothing returned:
+ * anchors that are not sorted as gwamd_match_anchors sorts them, or a
+ * position of 2^31 or more.  n == 0 gives no overlaps without a device call. */
+
+/* OverlapperTriggered(allocator).get_overlaps(overlaps, d_anchors, min_residues, min_overlap_len,
+ * min_bases_per_residue, min_overlap_fraction) (overlapper_triggered.hpp:49-57) on n host anchors */
+int32_t gwamd_get_overlaps(const gwamd_anchor* anchors, int64_t n, int64_t min_residues, int64_t min_overlap_len,
+                           int64_t min_bases_per_residue, float min_overlap_fraction, int32_t device_id,
+                           gwamd_overlap** overlaps, int64_t* num_overlaps);
+int32_t gwamd_get_overlaps_with_allocator(const gwamd_anchor* anchors, int64_t n, int64_t min_residues,
+                                          int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                          float min_overlap_fraction, int32_t device_id,
+                                          struct gwamd_device_allocator* allocator, gwamd_overlap** overlaps,
+                                          int64_t* num_overlaps);
+/* Matcher::create_matcher followed by get_overlaps on matcher->anchors() (main.cu:227-240): the
+ * anchors stay on the device; num_anchors (may be NULL) receives their number. */
+int32_t gwamd_match_overlaps(const gwamd_index* query_index, const gwamd_index* target_index, int64_t max_anchors,
+                             int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                             float min_overlap_fraction, gwamd_overlap** overlaps, int64_t* num_overlaps,
+                             int64_t* num_anchors);
+int32_t gwamd_match_overlaps_with_allocator(const gwamd_index* query_index, const gwamd_index* target_index,
+                                            int64_t max_anchors, int64_t min_residues, int64_t min_overlap_len,
+                                            int64_t min_bases_per_residue, float min_overlap_fraction,
+                                            struct gwamd_device_allocator* allocator, gwamd_overlap** overlaps,
+                                            int64_t* num_overlaps, int64_t* num_anchors);
+/* Overlapper::post_process_overlaps(overlaps, drop_fused_overlaps) (overlapper.cpp:127-228), host
+ * only: the n overlaps (without those fused, if drop_fused_overlaps != 0) followed by the fusions. */
+int32_t gwamd_post_process_overlaps(const gwamd_overlap* in, int64_t n, int32_t drop_fused_overlaps,
+                                    gwamd_overlap** out, int64_t* num_out);
+void gwamd_overlaps_free(gwamd_overlap* overlaps);
 
 #ifdef __cplusplus
 }

@@ -1,19 +1,22 @@
 #!/usr/bin/env python
-"""Throughput of the minimizer index and the anchor matcher on one GPU.
+"""Throughput of the minimizer index, the anchor matcher and the overlapper on one GPU.
 
 Builds the index of 2,000 synthetic 10 kb reads at (k,w) = (15,10), hashed,
 filtering_parameter 0.001, and matches it against itself.  The reads are
 substrings of one random 2 Mb genome (10x coverage, every second one reverse
 complemented), so the reads share minimizers and the anchor count is bounded
-by the coverage.  Prints one JSON line with bases/s for the index and
-anchors/s for the matcher, then checks a 16-read subset against the
-plain-Python model (tests/mapper_model.py).
+by the coverage.  Prints one JSON line with bases/s for the index, anchors/s
+for the matcher and for matching and chaining in one call (default overlapper
+parameters), then checks a 16-read subset against the plain-Python models
+(tests/mapper_model.py, tests/overlapper_model.py).
 
-Each GPU step (index, match, verify) runs in a child process of its own under
-a time limit; a step that fails or runs out of time ends the run.  The timed
-calls are gwamd_index_create and gwamd_match_anchors (upload, kernels and, for
-the matcher, the copy of the anchors to the host), timed with device events
-on the stream the library works on and with the host clock.
+Each GPU step (index, match, overlap, verify) runs in a child process of its
+own under a time limit; a step that fails or runs out of time ends the run.
+The timed calls are gwamd_index_create, gwamd_match_anchors (upload, kernels
+and the copy of the anchors to the host) and gwamd_match_overlaps (the same
+matching, the overlapper's kernels and the copy of the overlaps; the anchors
+stay on the device), timed with device events on the stream the library works
+on and with the host clock.
 
     python scripts/mapper_throughput.py [--reads 2000] [--length 10000] [--steps 5] [--warmup 2]
 """
@@ -32,7 +35,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 K, W, FILTERING = 15, 10, 0.001
-STEP_TIMEOUT = {"index": 300, "match": 300, "verify": 300}
+STEP_TIMEOUT = {"index": 300, "match": 300, "overlap": 300, "verify": 300}
 
 
 def synthetic_reads(num_reads, length, seed=1):
@@ -93,7 +96,8 @@ def worker(args):
     reads = synthetic_reads(args.reads, args.length)
     if args.worker == "verify":
         import mapper_model as model
-        from claragenomicsanalysis_amd import Index, match_anchors
+        import overlapper_model
+        from claragenomicsanalysis_amd import Index, match_anchors, match_overlaps
         subset = reads[:16]
         expected = model.Index(subset, K, W, filtering_parameter=FILTERING)
         with Index(subset, K, W, filtering_parameter=FILTERING) as idx:
@@ -101,10 +105,15 @@ def worker(args):
                          "unique_representations", "first_occurrence_of_representations"):
                 assert getattr(idx, name).tolist() == getattr(expected, name), name
             anchors = match_anchors(idx, idx)
+            overlaps = match_overlaps(idx, idx)
         want = model.match_anchors(expected, expected)
         assert [tuple(int(x) for x in a) for a in anchors] == want
+        want_overlaps, counts = overlapper_model.get_overlaps(want)
+        assert [(o.query_read_id, o.target_read_id, o.query_start, o.query_end, o.target_start, o.target_end,
+                 o.strand, o.num_residues, bool(o.overlap_complete)) for o in overlaps] == want_overlaps
         print(json.dumps({"verified_reads": len(subset), "verified_elements": len(expected.representations),
-                          "verified_anchors": len(want)}))
+                          "verified_anchors": len(want), "verified_chains": counts["chains"],
+                          "verified_overlaps": len(want_overlaps)}))
         return
     bases, offsets = pack(reads)
     timer = Timer()
@@ -124,6 +133,25 @@ def worker(args):
                           "unique_representations": info.num_unique_representations,
                           "index_event_s": round(ev, 6), "index_wall_s": round(wall, 6),
                           "index_bases_per_s": round(len(bases) / ev, 1)}))
+    elif args.worker == "overlap":
+        h = create_index(L, bases, offsets, len(reads))
+        samples, n, anchors = [], C.c_int64(), C.c_int64()
+        for step in range(args.warmup + args.steps):
+            p = C.c_void_p()
+
+            def call():
+                rc = L.gwamd_match_overlaps(h, h, -1, 20, 50, 50, 0.9, C.byref(p), C.byref(n), C.byref(anchors))
+                if rc != 0:
+                    raise RuntimeError(L.gwamd_last_error().decode())
+            ev, wall = timer.run(call)
+            L.gwamd_overlaps_free(p)
+            if step >= args.warmup:
+                samples.append((ev, wall))
+        L.gwamd_index_free(h)
+        ev = float(np.median([s[0] for s in samples]))
+        wall = float(np.median([s[1] for s in samples]))
+        print(json.dumps({"overlaps": n.value, "overlap_anchors": anchors.value, "overlap_event_s": round(ev, 6),
+                          "overlap_wall_s": round(wall, 6), "overlap_anchors_per_s": round(anchors.value / ev, 1)}))
     else:
         h = create_index(L, bases, offsets, len(reads))
         samples, n = [], C.c_int64()
@@ -160,7 +188,7 @@ def main():
     result = {"metric": "mapper_throughput", "reads": args.reads, "read_length": args.length, "kmer_size": K,
               "window_size": W, "hash_representations": True, "filtering_parameter": FILTERING,
               "steps": args.steps, "warmup": args.warmup}
-    for step in ("index", "match") + (() if args.no_verify else ("verify",)):
+    for step in ("index", "match", "overlap") + (() if args.no_verify else ("verify",)):
         cmd = [sys.executable, os.path.abspath(__file__), "--worker", step, "--reads", str(args.reads), "--length",
                str(args.length), "--steps", str(args.steps), "--warmup", str(args.warmup)]
         try:

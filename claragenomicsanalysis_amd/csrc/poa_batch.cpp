@@ -574,6 +574,17 @@ public:
         GWAMD_HIP_CHECK(hipStreamSynchronize(stream_));
     }
 
+    // per-window row-order counters of the LDS kernel (poa_order.hpp; zeros from any other kernel)
+    void get_order_stats(int32_t* out)
+    {
+        ScopedDevice dev(device_id_);
+        if (poa_count_ == 0)
+            return;
+        GWAMD_HIP_CHECK(hipMemcpyAsync(out, bufs_.order_stats, size_t(poa_count_) * 4 * gwamd::poa::kOrderStats,
+                                       hipMemcpyDeviceToHost, stream_));
+        GWAMD_HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+
     void get_stats(int64_t* cells, int32_t* final_nodes)
     {
         ScopedDevice dev(device_id_);
@@ -676,6 +687,7 @@ private:
             {reinterpret_cast<void**>(&bufs_.final_nodes), align8(P * 4)},
             {reinterpret_cast<void**>(&bufs_.cells), align8(P * 8)},
             {reinterpret_cast<void**>(&bufs_.phase), align8(P * 8 * gwamd::poa::kPhases)},
+            {reinterpret_cast<void**>(&bufs_.order_stats), align8(P * 4 * gwamd::poa::kOrderStats)},
             {msa ? reinterpret_cast<void**>(&bufs_.edge_cov) : &dummy, msa ? align8(P * mn * E * S * 2) : 0},
             {msa ? reinterpret_cast<void**>(&bufs_.edge_cov_cnt) : &dummy, msa ? align8(P * mn * E * 2) : 0},
             {msa ? &bufs_.seq_begin : &dummy, msa ? align8(P * S * sz) : 0},
@@ -723,6 +735,7 @@ private:
         // status defaults so that reading before generate is defined
         GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.status, int(StatusType::generic_error), size_t(P), stream_));
         GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.msa_status, int(StatusType::generic_error), size_t(P), stream_));
+        GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.order_stats, 0, size_t(P) * 4 * gwamd::poa::kOrderStats, stream_));
         GWAMD_HIP_CHECK(hipStreamSynchronize(stream_));
     }
 
@@ -1219,6 +1232,18 @@ int32_t gwamd_poa_get_phase_ticks(gwamd_poa_batch* batch, int64_t* ticks)
     return guarded([&] {
         batch->impl->get_phases(ticks);
         return int32_t(gwamd::poa::kPhases);
+    });
+}
+
+// Row-order counters of the last run, kOrderStats int32 per window
+// (OrderStat, poa_common.hpp); returns the words per window (out == NULL:
+// only that).
+int32_t gwamd_internal_poa_order_stats(gwamd_poa_batch* batch, int32_t* out)
+{
+    return guarded([&] {
+        if (out)
+            batch->impl->get_order_stats(out);
+        return int32_t(gwamd::poa::kOrderStats);
     });
 }
 

@@ -124,6 +124,8 @@ constexpr int kDiagRaconV1      = 8;  // GWAMD_RACON=v1: the MSA's racon sort on
 constexpr int kDiagConsensusHbm = 16; // GWAMD_CONSENSUS=hbm: consensus by lane 0 in HBM
 constexpr int kDiagAddWave0     = 32; // GWAMD_POA_ADD=wave0: graph update on wave 0, one read position per lane
 constexpr int kDiagAddSerial    = 64; // GWAMD_POA_ADD=serial: the sequential restatement on lane 0 for every read
+constexpr int kDiagOrderKahn    = 128; // GWAMD_POA_ORDER=kahn: LDS kernel sorts after every read (no spliced row order)
+constexpr int kDiagSinkCap2     = 256; // GWAMD_POA_SINK_CAP=2: the spliced order gives way at more than 2 sinks, not 64
 constexpr int kDiagConsLdsShift = 16; // bits 16-31, GWAMD_CONSENSUS_LDS_BYTES (1..65535): cap on the LDS bytes
                                       // offered to the wave-wide consensus (0: none)
 
@@ -263,7 +265,27 @@ struct Buffers
     int32_t* final_nodes;
     int64_t* cells;     // per window: sum over reads of (|V|+1)*(|r|+1) (or band cells)
     int64_t* phase;     // per window kPhases counters of s_memrealtime ticks (100 MHz)
+    int32_t* order_stats; // per window kOrderStats counters of the LDS kernel's row order (OrderStat below)
 };
+
+// Per-window counters of the LDS kernel's row order (Buffers::order_stats,
+// kOrderStats int32 per window; poa_order.hpp).  CudaPoaBatch.ORDER_STATS
+// names them in this order.
+enum OrderStat
+{
+    kOsSpliced = 0,   // reads whose nodes were spliced into the order
+    kOsSortSeqAdd,    // full sorts: the sequential graph update ran (conflict, wave-0 / serial mode, no fit)
+    kOsSortCheck,     // ... the path's old nodes were not in increasing rank
+    kOsSortNoOld,     // ... the path holds no old node
+    kOsSortSinkCap,   // ... more than kSinkCap sinks (the window sorts per read from then on)
+    kOsSortEmptyRead, // ... the next read is empty
+    kOsSortLast,      // ... the window's last read (the consensus needs Kahn ranks)
+    kOsTieSorts,      // Kahn sorts into scratch that resolved a tie between sinks
+    kOsTieQuick,      // ties between sinks resolved by their shared predecessor's out-list
+    kOsSortAfterTie,  // full sorts: a tie that took a Kahn sort in this or one of the last two reads
+    kOrderStats
+};
+
 
 // Phase counters written per window (diagnostics, bench.py "phases").
 enum Phase

@@ -21,6 +21,7 @@
 #include <utility>
 
 #include "poa_wave.hpp"
+#include "poa_order.hpp"
 
 namespace gwamd
 {
@@ -236,6 +237,10 @@ __device__ __forceinline__ int prog_np(WinGraph<SizeT> g, int r, uint32_t rec)
 // ring_rows or more rows later; that is marked from the successor's side
 // (row s, predecessor row p: s - p >= ring_rows) into byte flags in `flags`
 // (V + 2 bytes of free LDS), so no out-edge lists are read.
+// Sinks: the rows of the first kSinkCap sinks are left in sinks[0..), their
+// number (all of them, capped at 65535) in sinks[kSinkCap], and every listed
+// sink row spills, so that E(sink, L) can be read back after the forward pass
+// (the tie check of a spliced row order, poa_order.hpp).
 // The base of forward-pass row r from its record (build_row_program): bits
 // 0-6, or the graph's own byte when they hold 0x7f, which stands for 0x7f and
 // for every byte >= 0x80 (the reference compares whole bytes, and bit 7 of
@@ -247,17 +252,18 @@ __device__ __forceinline__ int row_base(WinGraph<SizeT> g, uint32_t rec, int r)
     return b == 0x7f ? uniform(int(g.base[g.sorted[r - 1]])) : b;
 }
 
+constexpr int kRowProgRP  = 4;                 // rows per lane and block
+constexpr int kRowProgBlk = kRowProgRP * kWave;  // rows per block: one wave's pass
+
+// One block of the row program: rows r0 .. r0 + kRowProgBlk - 1 (up to V) by
+// one wave.  xbase / nsink: the predecessor-list entries and the sinks of the
+// rows before r0 on entry, of the rows through this block on return.
 template <typename SizeT>
-__device__ void build_row_program(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl, int xl_cap,
-                                  int ring_rows, int lane, GWAMD_LDS uint8_t* flags)
+__device__ __forceinline__ void row_program_block(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl, int xl_cap,
+                                                  int ring_rows, int lane, GWAMD_LDS uint8_t* flags,
+                                                  GWAMD_LDS uint16_t* sinks, int r0, int& xbase, int& nsink)
 {
-    g = as_global(g);
-    constexpr int kRP = 4;
-    for (int r = lane; r <= V + 1; r += kWave)
-        flags[r] = 0;
-    wave_sync();
-    int xbase = 0;
-    for (int r0 = 1; r0 <= V; r0 += kRP * kWave)
+    constexpr int kRP = kRowProgRP;
     {
         int node[kRP], np[kRP], base[kRP], oc[kRP], e0[kRP], e1[kRP], p0[kRP], p1[kRP];
 #pragma unroll
@@ -290,6 +296,17 @@ __device__ void build_row_program(WinGraph<SizeT> g, int V, uint32_t* rec, uint1
             const int n      = valid ? np[u] : 0;
             int total        = 0;
             const int excl   = wave_excl_sum(n >= 2 ? n : 0, lane, total);
+            {
+                const bool sink   = valid && oc[u] == 0;
+                const uint64_t sm = __builtin_amdgcn_ballot_w64(sink);
+                const int si      = nsink + __popcll(sm & ((1ull << lane) - 1));
+                if (sink && si < kSinkCap)
+                {
+                    sinks[si] = uint16_t(r);
+                    flags[r]  = 1;
+                }
+                nsink += __popcll(sm);
+            }
             if (valid)
             {
                 // bits 0-6: the base, 0x7f standing for 0x7f and for every
@@ -333,11 +350,169 @@ __device__ void build_row_program(WinGraph<SizeT> g, int V, uint32_t* rec, uint1
             xbase += total;
         }
     }
+}
+
+// The row program by one wave, block after block with a running list offset:
+// the form the records, lists and marks are defined by.  Before a forward
+// pass the kernel builds it on every wave (build_row_program below, byte for
+// byte the same: tests/test_poa_order_splice.py compares the two); this one
+// rebuilds it on the two rare paths that lose it to a sort's scratch (a sink
+// tie that takes a Kahn sort, more sinks than the tie check holds).
+template <typename SizeT>
+__device__ void build_row_program_wave0(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl, int xl_cap,
+                                        int ring_rows, int lane, GWAMD_LDS uint8_t* flags,
+                                        GWAMD_LDS uint16_t* sinks)
+{
+    g = as_global(g);
+    for (int r = lane; r <= V + 1; r += kWave)
+        flags[r] = 0;
+    wave_sync();
+    int xbase = 0;
+    int nsink = 0;
+    for (int r0 = 1; r0 <= V; r0 += kRowProgBlk)
+        row_program_block<SizeT>(g, V, rec, xl, xl_cap, ring_rows, lane, flags, sinks, r0, xbase, nsink);
+    if (lane == 0)
+        sinks[kSinkCap] = uint16_t(min(nsink, 65535));
     wave_sync();
     for (int r = lane + 1; r <= V; r += kWave)
         if (flags[r])
             rec[r] |= 1u << 15;
     wave_sync();
+}
+
+// The row program on every wave of the workgroup (nthr threads, a multiple of
+// kWave; called by all of them with uniform arguments): wave w takes blocks w,
+// w + nwv, ...  A block's list offset and sink index depend on the blocks
+// before it, so a first pass counts each block's list entries and sinks (node
+// -> in- and out-degree, the loads of up to kCB blocks per wave in flight
+// together) into one LDS word per block behind the flags, and a block then
+// starts from the sum over the blocks before it.  Spill flags are plain LDS
+// byte stores, as before; the bit-15 pass over them runs on every thread.
+// flags: V + 2 bytes, then (V + kRowProgBlk - 1) / kRowProgBlk words at the
+// next 16-byte boundary.  Workgroup barriers: 2 (after the counts, after the
+// blocks); the caller's follows the last stores.
+template <typename SizeT>
+__device__ __forceinline__ void build_row_program_core(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl,
+                                                       int xl_cap, int ring_rows,
+                                  int tid, int nthr, GWAMD_LDS uint8_t* flags, GWAMD_LDS uint16_t* sinks)
+{
+    g = as_global(g);
+    constexpr int kRP = kRowProgRP, kCB = 4;
+    const int lane = tid & (kWave - 1);
+    const int wv   = uniform(tid / kWave);
+    const int nwv  = nthr / kWave;
+    const int nblk = (V + kRowProgBlk - 1) / kRowProgBlk;
+    GWAMD_LDS int* blk = (GWAMD_LDS int*)(flags + ((V + 2 + 15) & ~15));
+    for (int r = tid; r <= V + 1; r += nthr)
+        flags[r] = 0;
+    // per block: list entries | sinks << 20 (at most 256 x 50 and 256)
+    for (int b0 = wv; b0 < nblk; b0 += nwv * kCB)
+    {
+        int node[kCB][kRP], ic[kCB][kRP], oc[kCB][kRP];
+#pragma unroll
+        for (int j = 0; j < kCB; j++)
+#pragma unroll
+            for (int u = 0; u < kRP; u++)
+            {
+                const int r = 1 + (b0 + j * nwv) * kRowProgBlk + u * kWave + lane;
+                node[j][u]  = int(g.sorted[min(r, V) - 1]);
+            }
+#pragma unroll
+        for (int j = 0; j < kCB; j++)
+#pragma unroll
+            for (int u = 0; u < kRP; u++)
+            {
+                ic[j][u] = int(g.in_cnt[node[j][u]]);
+                oc[j][u] = int(g.out_cnt[node[j][u]]);
+            }
+#pragma unroll
+        for (int j = 0; j < kCB; j++)
+        {
+            const int b = b0 + j * nwv;
+            int c       = 0;
+#pragma unroll
+            for (int u = 0; u < kRP; u++)
+            {
+                const int r = 1 + b * kRowProgBlk + u * kWave + lane;
+                if (b < nblk && r <= V)
+                    c += (ic[j][u] >= 2 ? ic[j][u] : 0) + (oc[j][u] == 0 ? 1 << 20 : 0);
+            }
+            int total = 0;
+            (void)wave_excl_sum(c, lane, total);
+            if (lane == 0 && b < nblk)
+                blk[b] = total;
+        }
+    }
+    __syncthreads();
+    int xbase = 0, nsink = 0, bnext = 0;
+    for (int b = wv; b < nblk; b += nwv)
+    {
+        for (int q = bnext; q < b; q++)
+        {
+            const int c = uniform(blk[q]);
+            xbase += c & 0xfffff;
+            nsink += c >> 20;
+        }
+        bnext = b + 1; // (the block's own counts are added as it is built)
+        row_program_block<SizeT>(g, V, rec, xl, xl_cap, ring_rows, lane, flags, sinks, 1 + b * kRowProgBlk, xbase,
+                                 nsink);
+    }
+    if (tid == 0)
+    {
+        int ns = 0;
+        for (int q = 0; q < nblk; q++)
+            ns += blk[q] >> 20;
+        sinks[kSinkCap] = uint16_t(min(ns, 65535));
+    }
+    __syncthreads();
+    for (int r = tid + 1; r <= V; r += nthr)
+        if (flags[r])
+            rec[r] |= 1u << 15;
+}
+
+// build_row_program_core out of line with plain arguments, for the test
+// kernel.  (Inlined into a kernel, ROCm 7.2.0's backend stops on this file
+// with "Illegal instruction detected ... V_CMP_NE_U32_e32 0,
+// $src_shared_base".)
+template <typename SizeT>
+__device__ __noinline__ void build_row_program_args(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl, int xl_cap,
+                                                    int ring_rows, int tid, int nthr, GWAMD_LDS uint8_t* flags,
+                                                    GWAMD_LDS uint16_t* sinks)
+{
+    build_row_program_core<SizeT>(g, V, rec, xl, xl_cap, ring_rows, tid, nthr, flags, sinks);
+}
+
+// build_row_program_core for poa_window_kernel_lds: window w_ with V_ rows,
+// `lds` the start of the LDS image; records, lists, sink words and flags at
+// the offsets of Dims.  Called by every thread of the workgroup.  Out of
+// line with the batch's pointers read from the kernel's own kernarg segment,
+// as add_alignment_waves; kInst: one instantiation per calling kernel.  One
+// call site per kernel: with this routine also at the two rebuilds after a
+// sort (build_row_program_wave0 there), config B's kernel came out at 256
+// VGPRs + 1 AGPR, one wave per SIMD and half the resident workgroups.
+template <int NW, int kInst = 0>
+__device__ __noinline__ void build_row_program(LdsKernelArgsPtr ka_, int w_, int V_, GWAMD_LDS uint8_t* lds)
+{
+    using SizeT               = int16_t;
+    const uint64_t kav        = uint64_t(uintptr_t(ka_));
+    const LdsKernelArgsPtr ka = (LdsKernelArgsPtr)(uintptr_t(
+        (uint64_t(uint32_t(uniform(int(uint32_t(kav >> 32))))) << 32) | uint32_t(uniform(int(uint32_t(kav))))));
+    const size_t w  = size_t(uniform(w_));
+    const size_t mn = size_t(ka->d.max_nodes);
+    lds             = (GWAMD_LDS uint8_t*)(uintptr_t)(uint32_t)uniform(int((uint32_t)(uintptr_t)lds));
+    WinGraph<SizeT> g{};
+    g.base      = ka->b.base + w * mn;
+    g.in_cnt    = ka->b.in_cnt + w * mn;
+    g.out_cnt   = ka->b.out_cnt + w * mn;
+    g.in_e      = static_cast<SizeT*>(ka->b.in_e) + w * mn * kMaxEdges;
+    g.sorted    = static_cast<SizeT*>(ka->b.sorted) + w * mn;
+    g.pos       = static_cast<SizeT*>(ka->b.pos) + w * mn;
+    g.max_nodes = int(mn);
+    const int xcap = ka->d.lds_xl_cap - kSinkWords;
+    build_row_program_core<SizeT>(g, uniform(V_), (uint32_t*)(lds + ka->d.lds_rec_off),
+                                  (uint16_t*)(lds + ka->d.lds_xl_off), xcap, ka->d.lds_ring_rows, int(threadIdx.x),
+                                  NW * kWave, lds + ka->d.lds_ring_off,
+                                  (GWAMD_LDS uint16_t*)(lds + ka->d.lds_xl_off) + xcap);
 }
 
 // ---------------------------------------------------------------------------
@@ -1259,6 +1434,52 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
     int64_t cells       = 0;
     int node_count      = 0;
     int lv_hint         = 0; // nodes whose critical predecessor of the last level sort is in cpred
+    // Row order (poa_order.hpp).  order_kahn: g.sorted is the reference's Kahn
+    // order (the backbone's is); else the previous order with the later reads
+    // spliced in.  splice_on: this window still splices (not under the racon
+    // order per read, the FIFO diagnostic or GWAMD_POA_ORDER=kahn; off for
+    // good once it has had more than kSinkCap sinks).  Both are computed from
+    // workgroup-uniform values on every thread.
+    // tie_hold: reads still to be sorted, not spliced, after a tie between
+    // sinks that took a Kahn sort to resolve.  Such ties persist (two ends that
+    // no later read matches), and a window that kept splicing would pay the
+    // splice, the tie sort and a second row program for every read; it sorts
+    // per read instead, keeps watching for ties, and goes back to splicing
+    // after two reads without one that needs a sort (a tie the out-list rule
+    // settles does not extend the hold).  The 2 is not tuned.
+    bool order_kahn = true;
+    bool splice_on  = !d.spoa_accurate && !(d.diag & (kDiagTopsortFifo | kDiagOrderKahn));
+    int tie_hold    = 0;
+    const int sink_cap = (d.diag & kDiagSinkCap2) ? 2 : kSinkCap; // (the diagnostic value: tests of that path)
+    const int xcap  = d.lds_xl_cap - kSinkWords; // predecessor lists; the sink list follows them
+    GWAMD_LDS uint16_t* sinks = (GWAMD_LDS uint16_t*)(lds + d.lds_xl_off) + xcap;
+    int32_t* ostat  = b.order_stats + size_t(w) * kOrderStats;
+    auto count      = [&](int k) {
+        if (tid == 0)
+            __hip_atomic_fetch_add(ostat + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    if (tid < kOrderStats)
+        ostat[tid] = 0;
+    // A Kahn sort of the first n nodes into gx.sorted / gx.pos on every wave,
+    // with the whole LDS image below the shared region as scratch (the staged
+    // read and the row program are lost); lane 0's FIFO sort when the level
+    // sort declines.  Barriers: the level sort's, then one.  gx.sorted[0 ..
+    // n_prev) is only read as the order in which topsort_levels walks those
+    // nodes: any permutation of the ids 0 .. n_prev - 1 will do (a walk in
+    // topological order converges fastest), so a spliced order serves as a
+    // Kahn order does, and a sort whose output goes elsewhere first copies the
+    // order in use there.  cpred[0 .. lv_hint) holds c(v) of the window's last
+    // level sort; reads spliced since then have not touched it, and every c(v)
+    // is still a predecessor of v (edges are never removed), which is all a
+    // hint has to be.
+    auto kahn_sort = [&](WinGraph<SizeT> gx, int n, int n_prev) {
+        const bool done = topsort_levels<SizeT, NW>(gx, n, n_prev, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off, tid,
+                                                    kThr, cpred, lv_hint);
+        if (!done && tid == 0)
+            topsort_kahn<SizeT>(gx, n, cscore);
+        lv_hint = done ? n : 0;
+        __syncthreads();
+    };
 
     if (nseq > 0)
     {
@@ -1281,12 +1502,28 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
             const uint8_t* read_g = b.seqs + off;
             const int8_t* wts_g   = b.wts + off;
             const int padded      = (L + 32 + 15) & ~15;
-            for (int j = tid; j < padded; j += kThr)
-                lread[j] = j < L ? read_g[j] : 0;
-            const int V = node_count;
-            if (wave == 0) // spill flags in the ring region (free until the forward pass)
-                build_row_program<SizeT>(g, V, rec, xl, d.lds_xl_cap, d.lds_ring_rows, lane,
-                                         (GWAMD_LDS uint8_t*)(lds) + d.lds_ring_off);
+            const int V           = node_count;
+            // the read staged in LDS and the row program of the order in use,
+            // on every wave (build_row_program's two barriers; the caller's
+            // follows its last stores)
+            auto stage_and_program = [&]() {
+                for (int j = tid; j < padded; j += kThr)
+                    lread[j] = j < L ? read_g[j] : 0;
+                // (spill flags and block counts in the ring region, free until the forward pass)
+                build_row_program<NW, NW + (W ? 16 : 0)>(lds_kernel_args(), w, V, (GWAMD_LDS uint8_t*)(lds));
+            };
+            // the same after a sort that used the LDS image as scratch, the
+            // program by wave 0 (the same bytes; no barrier, the caller's
+            // follows)
+            auto stage_and_program_w0 = [&]() {
+                for (int j = tid; j < padded; j += kThr)
+                    lread[j] = j < L ? read_g[j] : 0;
+                // (spill flags in the ring region, free until the forward pass)
+                if (wave == 0)
+                    build_row_program_wave0<SizeT>(g, V, rec, xl, xcap, d.lds_ring_rows, lane,
+                                                   (GWAMD_LDS uint8_t*)(lds) + d.lds_ring_off, sinks);
+            };
+            stage_and_program();
             if (NW > 1)
             {
                 // forward-pass channels and progress words start empty
@@ -1296,6 +1533,26 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
                     reinterpret_cast<GWAMD_LDS int*>(shb + kP)[t] = 0;
             }
             __syncthreads();
+            // sinks of the graph (uniform: an LDS word read after the barrier;
+            // only looked at under a spliced order or while ties are watched)
+            int nsink = (order_kahn && tie_hold == 0) ? 1 : uniform(int(sinks[kSinkCap]));
+            if (nsink > sink_cap && order_kahn)
+                nsink = 1;
+            if (nsink > sink_cap)
+            {
+                // more sinks than the tie check lists: back to the Kahn order,
+                // now and for the rest of the window.  Barriers, on every wave:
+                // this one (the sort's scratch holds the sink count just read),
+                // kahn_sort's, one more.
+                __syncthreads();
+                kahn_sort(g, V, V);
+                count(kOsSortSinkCap);
+                order_kahn = true;
+                splice_on  = false;
+                nsink      = 1;
+                stage_and_program_w0();
+                __syncthreads();
+            }
             ph.lap<kPhRowProg>();
             cells += int64_t(V + 1) * (L + 1);
             int end_row;
@@ -1314,6 +1571,108 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
                                                             d.code_stride, sc, shb, carry, tid, fp);
             __syncthreads();
             ph.lap<kPhForward>();
+            if (nsink >= 2)
+            {
+                // Several sinks, under a spliced order (or a Kahn order while
+                // ties are watched): the forward pass took the first sink in row
+                // order with the maximal final score, the reference the first in
+                // Kahn order.  Every listed sink row was spilled, so E(sink, L)
+                // is in its HBM row: wave 0 reads them, one sink per lane.
+                //   One maximal sink: end_row stands.
+                //   Several, each with one predecessor, the same one: the FIFO
+                //     releases them together when it pops that node, in the
+                //     order of its out-list, so the one in the lowest slot wins.
+                //   Else a Kahn sort into the free part of the slot's cpred
+                //     (topsort_levels keeps c(v) in its first max_nodes entries;
+                //     the racon stack that fills it is not used on this path),
+                //     and the tied sink with the smallest Kahn position wins.
+                // Under a Kahn order end_row is right as it is, and only the
+                // kind of tie is noted.  Barriers, on every wave: two here; for
+                // a sort kahn_sort's, then two, then one after the read and the
+                // row program (lost to the sort's scratch) are rebuilt.
+                int srow_l = 0, sval = INT_MIN, smax = INT_MIN;
+                bool tied  = false;
+                if (wave == 0)
+                {
+                    if (lane < nsink)
+                    {
+                        srow_l = int(sinks[lane]);
+                        sval   = int(glb(spill)[size_t(srow_l) * rstride + L + kColShift]);
+                    }
+                    smax              = wave_max(sval);
+                    tied              = lane < nsink && sval == smax;
+                    const uint64_t tm = __builtin_amdgcn_ballot_w64(tied);
+                    int code = 0, er = end_row;
+                    if (__popcll(tm) >= 2)
+                    {
+                        int node = 0, ic = 0, pr = -1;
+                        if (tied)
+                        {
+                            node = int(glb(g.sorted)[srow_l - 1]);
+                            ic   = int(glb(g.in_cnt)[node]);
+                            pr   = ic == 1 ? int(glb(g.in_e)[node * kMaxEdges]) : -1;
+                        }
+                        const int p0 = __builtin_amdgcn_readlane(pr, uniform(__builtin_ctzll(tm)));
+                        if (__builtin_amdgcn_ballot_w64(tied && (ic != 1 || pr != p0)) == 0)
+                        {
+                            int slot = INT_MAX;
+                            if (tied)
+                            {
+                                const int oc = int(glb(g.out_cnt)[p0]);
+                                for (int e = oc - 1; e >= 0; e--)
+                                    if (int(glb(g.out_e)[p0 * kMaxEdges + e]) == node)
+                                        slot = e;
+                            }
+                            const int smin = -wave_max(-slot);
+                            const uint64_t m = __builtin_amdgcn_ballot_w64(tied && slot == smin);
+                            er   = __builtin_amdgcn_readlane(srow_l, uniform(__builtin_ctzll(m)));
+                            code = 1;
+                        }
+                        else
+                            code = 2;
+                    }
+                    if (lane == 0)
+                        sh_len = code | (er << 2);
+                }
+                __syncthreads();
+                const int tv = uniform(sh_len);
+                __syncthreads();
+                const int code = tv & 3;
+                if (code == 1 && !order_kahn)
+                {
+                    end_row = tv >> 2;
+                    count(kOsTieQuick);
+                }
+                if (code == 2 && !order_kahn)
+                {
+                    WinGraph<SizeT> gk = g;
+                    gk.sorted          = cpred + mn;
+                    gk.pos             = cpred + 2 * mn;
+                    for (int i = tid; i < V; i += kThr) // the order the sort walks the nodes in
+                        glb(gk.sorted)[i] = glb(g.sorted)[i];
+                    kahn_sort(gk, V, V);
+                    count(kOsTieSorts);
+                    if (wave == 0)
+                    {
+                        int kp = INT_MAX;
+                        if (tied)
+                            kp = int(glb(gk.pos)[int(glb(g.sorted)[srow_l - 1])]);
+                        const int kmin = -wave_max(-kp);
+                        const uint64_t m = __builtin_amdgcn_ballot_w64(kp == kmin);
+                        const int er   = __builtin_amdgcn_readlane(srow_l, uniform(__builtin_ctzll(m)));
+                        if (lane == 0)
+                            sh_len = er;
+                    }
+                    __syncthreads();
+                    end_row = uniform(sh_len);
+                    __syncthreads();
+                    stage_and_program_w0();
+                    __syncthreads();
+                }
+                tie_hold = code == 2 ? 2 : max(tie_hold - 1, 0);
+            }
+            else if (tie_hold > 0)
+                tie_hold--;
             if (wave == 0)
             {
                 const int alen_w = traceback_codes<SizeT>(g, P, V, L, end_row, codes, d.code_stride, tile, ag, ar,
@@ -1387,6 +1746,43 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
             int nc       = uniform(sh_len);
             bool lv_done = false;
             __syncthreads(); // sh_* are rewritten below
+            // Row order for the next read: the read's new nodes spliced into
+            // the order in use (order_splice, poa_order.hpp) when the
+            // every-wave update wrote the graph (its curr / kind arrays still
+            // hold the path: nothing has touched the ring region since), the
+            // next read is not empty (an empty read is aligned under a Kahn
+            // order), this is not the window's last read (the consensus needs
+            // Kahn ranks) and no tie between sinks is being waited out
+            // (tie_hold); else, or when the splice declines, the full sort
+            // below.  Barriers of order_splice, on every wave: 2 when it
+            // declines or there is no new node, 4 when it writes; a spliced
+            // read skips the sort step and its two barriers.
+            int spl = -1;
+            if (splice_on && rc == kSuccess)
+            {
+                const int l_next   = s + 1 < nseq ? b.seq_len[wd.first_seq + s + 1] : -1;
+                const bool par_add = add_mode == 0 && uniform(add_r & 0xff) != 0xff;
+                if (par_add && l_next > 0 && tie_hold == 0)
+                    spl = uniform(order_splice<NW, NW + (W ? 16 : 0)>(lds_kernel_args(), w, V, L,
+                                                                      (GWAMD_LDS uint8_t*)(lds)));
+                count(spl == kSpliceDone ? kOsSpliced
+                      : !par_add         ? kOsSortSeqAdd
+                      : l_next < 0       ? kOsSortLast
+                      : l_next == 0      ? kOsSortEmptyRead
+                      : tie_hold > 0     ? kOsSortAfterTie
+                      : spl == kSpliceCheck ? kOsSortCheck
+                                            : kOsSortNoOld);
+            }
+            if (spl == kSpliceDone)
+            {
+                if (wave == 0)
+                    ph.lap<kPhTopsort>();
+                order_kahn = false;
+                status     = rc;
+                node_count = nc;
+                continue;
+            }
+            order_kahn = true;
             // level-keyed Kahn sort on every wave of the workgroup
             // (GWAMD_TOPSORT=fifo, kDiagTopsortFifo, keeps the FIFO below)
             if (rc == kSuccess && !d.spoa_accurate && !(d.diag & kDiagTopsortFifo))
@@ -1603,6 +1999,205 @@ int topsort_levels_test(int n, int n_prev, int n_hint, const uint16_t* in_cnt, c
     for (int v = 0; hint && v < n; v++)
         hint[v] = int32_t(hi[v]);
     return fin(ok);
+}
+
+// Test hook: order_splice_core on one order and one path by one workgroup.
+// LDS: curr | key | cnt | stage (u16), kind (u8), one control word.
+__global__ void __launch_bounds__(1024) order_splice_test_kernel(int16_t* sorted, int16_t* pos, int V, int L,
+                                                                 const uint16_t* curr_g, const uint8_t* kind_g,
+                                                                 int* out)
+{
+    extern __shared__ __align__(16) uint8_t lds[];
+    const int Lp             = (L + 8) & ~7;
+    GWAMD_LDS uint8_t* a     = (GWAMD_LDS uint8_t*)(lds);
+    GWAMD_LDS uint16_t* curr = (GWAMD_LDS uint16_t*)(a);
+    GWAMD_LDS uint16_t* key  = curr + Lp;
+    GWAMD_LDS uint16_t* cnt  = key + Lp;
+    GWAMD_LDS uint16_t* stg  = cnt + ((V + 1 + L + 8) & ~7);
+    GWAMD_LDS int* ctl       = (GWAMD_LDS int*)(stg + ((V + 8) & ~7));
+    GWAMD_LDS uint8_t* kind  = (GWAMD_LDS uint8_t*)(ctl + 4);
+    for (int i = int(threadIdx.x); i < L; i += int(blockDim.x))
+    {
+        curr[i] = curr_g[i];
+        kind[i] = kind_g[i];
+    }
+    __syncthreads();
+    const int r = order_splice_core<int16_t>(glb_of(sorted), glb_of(pos), V, L, curr, kind, key, cnt, stg, ctl,
+                                             int(threadIdx.x), int(blockDim.x));
+    if (threadIdx.x == 0)
+        *out = r;
+}
+
+// sorted: in V entries (a permutation of 0..V-1), out n entries; pos: out n
+// entries; curr / kind: L entries; n: node count with the path's new nodes.
+// Returns order_splice_core's value, -1 on a HIP error, -2 on bad arguments.
+int order_splice_test(int V, int n, int L, int32_t* sorted, int32_t* pos, const int32_t* curr, const uint8_t* kind,
+                      int threads)
+{
+    if (V <= 0 || n < V || n > 32767 || L <= 0 || L > 32767 || threads < 64 || threads > 1024 || threads % 64)
+        return -2;
+    std::vector<int16_t> so(n, int16_t(-1)), po(n, int16_t(-1));
+    std::vector<uint16_t> cu(L);
+    for (int q = 0; q < V; q++)
+    {
+        if (sorted[q] < 0 || sorted[q] >= V || po[sorted[q]] >= 0)
+            return -2;
+        so[q]         = int16_t(sorted[q]);
+        po[sorted[q]] = int16_t(q);
+    }
+    for (int i = 0; i < L; i++)
+    {
+        const bool isnew = (kind[i] & 3) >= 2;
+        if (curr[i] < 0 || curr[i] >= n || (isnew != (curr[i] >= V)))
+            return -2;
+        cu[i] = uint16_t(curr[i]);
+    }
+    const size_t lds_b = 2 * (2 * size_t((L + 8) & ~7) + size_t((V + 1 + L + 8) & ~7) + size_t((V + 8) & ~7)) + 16 +
+                         size_t(L) + 16;
+    if (lds_b > 65536)
+        return -2;
+    int16_t *d_so = nullptr, *d_po = nullptr;
+    uint16_t* d_cu = nullptr;
+    uint8_t* d_ki  = nullptr;
+    int* d_out     = nullptr;
+    int out        = -1;
+    auto fin       = [&](int r) {
+        (void)hipFree(d_so);
+        (void)hipFree(d_po);
+        (void)hipFree(d_cu);
+        (void)hipFree(d_ki);
+        (void)hipFree(d_out);
+        return r;
+    };
+    if (hipMalloc(&d_so, n * 2) || hipMalloc(&d_po, n * 2) || hipMalloc(&d_cu, L * 2) || hipMalloc(&d_ki, L) ||
+        hipMalloc(&d_out, sizeof(int)) || hipMemcpy(d_so, so.data(), n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_po, po.data(), n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_cu, cu.data(), L * 2, hipMemcpyHostToDevice) || hipMemcpy(d_ki, kind, L, hipMemcpyHostToDevice))
+        return fin(-1);
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&order_splice_test_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)))
+        return fin(-1);
+    hipLaunchKernelGGL(order_splice_test_kernel, dim3(1), dim3(threads), lds_b, 0, d_so, d_po, V, L, d_cu, d_ki, d_out);
+    if (hipGetLastError() || hipDeviceSynchronize() || hipMemcpy(&out, d_out, sizeof(int), hipMemcpyDeviceToHost) ||
+        hipMemcpy(so.data(), d_so, n * 2, hipMemcpyDeviceToHost) ||
+        hipMemcpy(po.data(), d_po, n * 2, hipMemcpyDeviceToHost))
+        return fin(-1);
+    for (int q = 0; q < n; q++)
+    {
+        sorted[q] = so[q];
+        pos[q]    = po[q];
+    }
+    return fin(out);
+}
+
+// Test hook: the row program of one graph and order built by one wave
+// (build_row_program_wave0) and then by every wave of the workgroup
+// (build_row_program_args), each into cleared LDS, both copied out: records
+// [V + 2] u32, then lists and sink words [xl_cap + kSinkWords] u16.
+template <typename SizeT>
+__global__ void __launch_bounds__(512) row_program_test_kernel(WinGraph<SizeT> g, int V, int xl_cap, int ring_rows,
+                                                               uint32_t* rec_out, uint16_t* xl_out)
+{
+    extern __shared__ __align__(16) uint8_t lds[];
+    const int nrec   = V + 2, nxl = xl_cap + kSinkWords;
+    uint32_t* rec    = reinterpret_cast<uint32_t*>(lds);
+    uint16_t* xl     = reinterpret_cast<uint16_t*>(lds + ((4 * nrec + 15) & ~15));
+    GWAMD_LDS uint8_t* flags = (GWAMD_LDS uint8_t*)(lds) + ((4 * nrec + 15) & ~15) + ((2 * nxl + 15) & ~15);
+    GWAMD_LDS uint16_t* sinks = (GWAMD_LDS uint16_t*)(xl) + xl_cap;
+    const int tid = int(threadIdx.x), nthr = int(blockDim.x);
+    for (int which = 0; which < 2; which++)
+    {
+        for (int i = tid; i < nrec; i += nthr)
+            rec[i] = 0;
+        for (int i = tid; i < nxl; i += nthr)
+            xl[i] = 0;
+        __syncthreads();
+        if (which == 0)
+        {
+            if (tid < kWave)
+                build_row_program_wave0<SizeT>(g, V, rec, xl, xl_cap, ring_rows, tid, flags, sinks);
+        }
+        else
+            build_row_program_args<SizeT>(g, V, rec, xl, xl_cap, ring_rows, tid, nthr, flags, sinks);
+        __syncthreads();
+        for (int i = tid; i < nrec; i += nthr)
+            rec_out[which * nrec + i] = rec[i];
+        for (int i = tid; i < nxl; i += nthr)
+            xl_out[which * nxl + i] = xl[i];
+        __syncthreads();
+    }
+}
+
+// sorted: a topological order of the n nodes.  rec_out: 2 x (n + 2) words,
+// xl_out: 2 x (xl_cap + kSinkWords) entries (the one-wave build first).
+// Returns 0, -1 on a HIP error, -2 on bad arguments.
+int row_program_test(int n, const uint8_t* base, const uint16_t* in_cnt, const uint16_t* out_cnt, const int32_t* in_e,
+                     const int32_t* sorted, int xl_cap, int ring_rows, int threads, uint32_t* rec_out,
+                     uint16_t* xl_out)
+{
+    using SizeT = int16_t;
+    if (n <= 0 || n > 8192 || xl_cap < 64 || xl_cap % 8 || threads < 64 || threads > 512 || threads % 64 ||
+        ring_rows < 1)
+        return -2;
+    const size_t ne = size_t(n) * kMaxEdges;
+    std::vector<SizeT> ie(ne), so(n), po(n, SizeT(-1));
+    for (size_t i = 0; i < ne; i++)
+        ie[i] = SizeT(in_e[i]);
+    for (int q = 0; q < n; q++)
+    {
+        if (sorted[q] < 0 || sorted[q] >= n || po[sorted[q]] >= 0)
+            return -2;
+        so[q]         = SizeT(sorted[q]);
+        po[sorted[q]] = SizeT(q);
+    }
+    const int nrec = n + 2, nxl = xl_cap + kSinkWords;
+    const int nblk = (n + kRowProgBlk - 1) / kRowProgBlk;
+    const size_t lds_b = size_t((4 * nrec + 15) & ~15) + size_t((2 * nxl + 15) & ~15) + size_t((n + 2 + 15) & ~15) +
+                         4 * size_t(nblk) + 16;
+    if (lds_b > 163840)
+        return -2;
+    uint8_t* d_base = nullptr;
+    uint16_t *d_ic = nullptr, *d_oc = nullptr, *d_xl = nullptr;
+    SizeT *d_ie = nullptr, *d_so = nullptr, *d_po = nullptr;
+    uint32_t* d_rec = nullptr;
+    auto fin = [&](int r) {
+        (void)hipFree(d_base);
+        (void)hipFree(d_ic);
+        (void)hipFree(d_oc);
+        (void)hipFree(d_xl);
+        (void)hipFree(d_ie);
+        (void)hipFree(d_so);
+        (void)hipFree(d_po);
+        (void)hipFree(d_rec);
+        return r;
+    };
+    if (hipMalloc(&d_base, n) || hipMalloc(&d_ic, n * 2) || hipMalloc(&d_oc, n * 2) ||
+        hipMalloc(&d_xl, 2 * nxl * 2) || hipMalloc(&d_ie, ne * 2) || hipMalloc(&d_so, n * 2) ||
+        hipMalloc(&d_po, n * 2) || hipMalloc(&d_rec, 2 * nrec * 4) ||
+        hipMemcpy(d_base, base, n, hipMemcpyHostToDevice) || hipMemcpy(d_ic, in_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oc, out_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ie, ie.data(), ne * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_so, so.data(), n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_po, po.data(), n * 2, hipMemcpyHostToDevice))
+        return fin(-1);
+    WinGraph<SizeT> g{};
+    g.base      = d_base;
+    g.in_cnt    = d_ic;
+    g.out_cnt   = d_oc;
+    g.in_e      = d_ie;
+    g.sorted    = d_so;
+    g.pos       = d_po;
+    g.max_nodes = n;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&row_program_test_kernel<SizeT>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)))
+        return fin(-1);
+    hipLaunchKernelGGL(row_program_test_kernel<SizeT>, dim3(1), dim3(threads), lds_b, 0, g, n, xl_cap, ring_rows, d_rec,
+                       d_xl);
+    if (hipGetLastError() || hipDeviceSynchronize() ||
+        hipMemcpy(rec_out, d_rec, 2 * nrec * 4, hipMemcpyDeviceToHost) ||
+        hipMemcpy(xl_out, d_xl, 2 * nxl * 2, hipMemcpyDeviceToHost))
+        return fin(-1);
+    return fin(0);
 }
 
 // Test hook: the racon DFS sort (topsort_racon_lds) of one graph by one wave,
@@ -1889,6 +2484,28 @@ extern "C" int gwamd_internal_topsort_racon(int size_bits, int n, const uint16_t
                                                        ncols, reps, ms);
     return gwamd::poa::topsort_racon_test<int32_t>(n, in_cnt, in_e, aln_cnt, aln, scratch, v1, sorted, mpos, ncols,
                                                    reps, ms);
+}
+
+// Test hook (tests/test_poa_order_splice.py): the LDS kernel's row program of
+// one graph (fixed-slot in-edge lists, base bytes, degrees) under the order
+// `sorted`, built by one wave and by every wave of a workgroup of `threads`
+// threads; see row_program_test for the outputs.
+extern "C" int gwamd_internal_row_program(int n, const uint8_t* base, const uint16_t* in_cnt, const uint16_t* out_cnt,
+                                          const int32_t* in_e, const int32_t* sorted, int xl_cap, int ring_rows,
+                                          int threads, uint32_t* rec_out, uint16_t* xl_out)
+{
+    return gwamd::poa::row_program_test(n, base, in_cnt, out_cnt, in_e, sorted, xl_cap, ring_rows, threads, rec_out,
+                                        xl_out);
+}
+
+// Test hook (tests/test_poa_order_splice.py): order_splice_core on the order
+// sorted[0..V) and the path curr / kind [L] by one workgroup of `threads`
+// threads; sorted and pos come back with n entries.  Returns 0 spliced, 1 / 2
+// declined (order check / no old node; nothing written), negative on errors.
+extern "C" int gwamd_internal_order_splice(int V, int n, int L, int32_t* sorted, int32_t* pos, const int32_t* curr,
+                                           const uint8_t* kind, int threads)
+{
+    return gwamd::poa::order_splice_test(V, n, L, sorted, pos, curr, kind, threads);
 }
 
 // Test hook (tests/test_poa_topsort.py): topsort_levels of one graph given as

@@ -50,7 +50,9 @@ inline PoaTuning read_poa_tuning()
                                    {"GWAMD_RACON", "v1", kDiagRaconV1},
                                    {"GWAMD_CONSENSUS", "hbm", kDiagConsensusHbm},
                                    {"GWAMD_POA_ADD", "wave0", kDiagAddWave0},
-                                   {"GWAMD_POA_ADD", "serial", kDiagAddSerial}};
+                                   {"GWAMD_POA_ADD", "serial", kDiagAddSerial},
+                                   {"GWAMD_POA_ORDER", "kahn", kDiagOrderKahn},
+                                   {"GWAMD_POA_SINK_CAP", "2", kDiagSinkCap2}};
     static const Choice kFwd[]  = {{"GWAMD_BAND_FWD", "ad", 1}, {"GWAMD_BAND_FWD", "row", 2}};
     auto is = [](const Choice& c) {
         const char* v = diag_env(c.name);

@@ -296,6 +296,22 @@ class CudaPoaBatch:
         _check(self._lib.gwamd_poa_get_phase_ticks(self._handle, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out[:n]
 
+    ORDER_STATS = ("spliced", "sort_seq_add", "sort_order_check", "sort_no_old_node", "sort_sink_cap",
+                   "sort_empty_read", "sort_last_read", "tie_sorts", "tie_quick", "sort_after_tie")
+
+    def get_order_stats(self):
+        """Per-window row-order counters of the full-alignment LDS kernel's last run, shape
+        (n, 10), columns ORDER_STATS: reads spliced into the row order, full sorts by cause,
+        and Kahn sorts that resolved a tie between sinks (zeros from the other kernels)."""
+        n = self.total_poas
+        out = np.zeros((max(n, 1), len(self.ORDER_STATS)), np.int32)
+        words = _check(self._lib.gwamd_internal_poa_order_stats(self._handle, None))
+        if words != len(self.ORDER_STATS):
+            raise RuntimeError("libgwamd.so counts %d row-order words, ORDER_STATS names %d"
+                               % (words, len(self.ORDER_STATS)))
+        _check(self._lib.gwamd_internal_poa_order_stats(self._handle, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out[:n]
+
     def get_types(self):
         """(score bits, size bits) chosen by create_batch (cudapoa_limits.hpp:28-53)."""
         sb, zb = C.c_int32(), C.c_int32()

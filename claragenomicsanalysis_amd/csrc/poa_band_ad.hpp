@@ -357,6 +357,13 @@ __device__ __forceinline__ int ad_block(const AdCtx<ScoreT>& C, const WinGraphG<
         cur = e;
         }
     }
+    // The steps store idx 0 .. bw of a spill row.  The reference's row ends in
+    // the min_score_value initialize_band wrote (:90-105), and get_scores() of
+    // a far successor reads up to 4 cells past bw: the stored rows get that
+    // padding too (as band_forward's padding groups), not what the slot held
+    if (any_store && store)
+        for (int k = bw + CPL; k < C.rowsz; k++)
+            C.spill[size_t(r) * C.rowsz + k] = ScoreT(minv);
     return sv;
 }
 

@@ -120,7 +120,7 @@ gwamd::poa::Dims plan_batch(const BatchSize& bs, bool banded, int8_t output_mask
     // process-wide default; gwamd_poa_set_spoa_accurate switches one batch
     if (const char* sa = std::getenv("GWAMD_SPOA_ACCURATE"))
         dims.spoa_accurate = std::atoi(sa) != 0 ? 1 : 0;
-    gwamd::poa::plan_kernels(dims, banded, gap, score_bits, size_bits, tune);
+    gwamd::poa::plan_kernels(dims, banded, gwamd::poa::Scores{gap, mismatch, match}, score_bits, size_bits, tune);
     return dims;
 }
 

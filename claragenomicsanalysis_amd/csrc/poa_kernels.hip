@@ -516,11 +516,14 @@ __device__ __noinline__ void build_row_program(LdsKernelArgsPtr ka_, int w_, int
 }
 
 // ---------------------------------------------------------------------------
-// Packed 16-bit forward pass.  E values are int16 (the E-domain bounds of a
-// window that selects 16-bit scores fit: cudapoa_limits.hpp:28-53), two cells
-// per 32-bit register, so the diagonal/vertical/max work runs on v_pk_*
-// instructions.  Cells beyond the read may wrap; they only feed cells further
-// right, never a cell <= L.
+// Packed 16-bit forward pass.  E values are int16, two cells per 32-bit
+// register, so the diagonal/vertical/max work runs on v_pk_* instructions.
+// The reference's rule for 16-bit scores (cudapoa_limits.hpp:28-37) bounds H,
+// not E = H - j*gap: a read equal to its graph has E(j, j) = j * (match - gap).
+// The host plans this pass only when the E range over the batch's columns
+// fits int16 (lds_e_domain_fits16, poa_plan.cpp); a 16-bit batch past that
+// bound runs the global-memory kernel.  Cells beyond the read may wrap; they
+// only feed cells further right, never a cell <= L.
 typedef short pk_s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short pk_u16x2 __attribute__((ext_vector_type(2)));
 

@@ -5,6 +5,7 @@
 #include "poa_plan.hpp"
 
 #include <algorithm>
+#include <cstdint>
 #include <iterator>
 #include <stdexcept>
 
@@ -19,6 +20,24 @@ namespace poa
 // predecessor lists | shared words; the topological sort reuses everything
 // below the shared words.  Span carries of multi-sweep reads live in HBM
 // next to the traceback codes.
+//
+// 16-bit rows hold E[i][j] = H[i][j] - j * gap, not H.  The reference's width
+// rule (cudapoa_limits.hpp:28-37) bounds H by upper = max_sequence_size * match
+// and lower = max_sequence_size * max(gap, mismatch) + (graph rows -
+// max_sequence_size) * gap; over the columns j <= max_sequence_size E then lies
+// in [lower - max_sequence_size * max(gap, 0), upper - max_sequence_size *
+// min(gap, 0)] (a read equal to its graph reaches j * (match - gap) at cell
+// (j, j)).  That range can pass int16 where H does not, e.g. gap -20, match 40
+// at 600 bases: 36,000.  Such a batch keeps the reference's 16-bit types and
+// runs the global-memory kernel, which works in H (plan_kernels).
+bool lds_e_domain_fits16(const Dims& dims, const Scores& sc)
+{
+    const int64_t ms    = dims.max_seq_len;
+    const int64_t upper = ms * sc.match;
+    const int64_t lower = ms * std::max(sc.gap, sc.mismatch) + (int64_t(dims.max_nodes) - ms) * sc.gap;
+    return upper - ms * std::min(sc.gap, 0) <= INT16_MAX && lower - ms * std::max(sc.gap, 0) >= INT16_MIN;
+}
+
 void plan_lds_layout(Dims& dims, bool banded, int size_bits, int score_bits, const PoaTuning& tune)
 {
     dims.lds_kernel = 0;
@@ -213,10 +232,12 @@ void plan_band_kernel(Dims& dims, bool banded, int gap, int score_bits, const Po
     dims.aux_stride = o;
 }
 
-void plan_kernels(Dims& dims, bool banded, int gap, int score_bits, int size_bits, const PoaTuning& tune)
+void plan_kernels(Dims& dims, bool banded, const Scores& sc, int score_bits, int size_bits, const PoaTuning& tune)
 {
-    plan_lds_layout(dims, banded, size_bits, score_bits, tune);
-    plan_band_kernel(dims, banded, gap, score_bits, tune);
+    dims.lds_kernel = 0;
+    if (banded || score_bits != 16 || lds_e_domain_fits16(dims, sc))
+        plan_lds_layout(dims, banded, size_bits, score_bits, tune);
+    plan_band_kernel(dims, banded, sc.gap, score_bits, tune);
     dims.diag = tune.diag;
 }
 

@@ -97,6 +97,36 @@ def test_cudapoa_file_consensus(tmp_path, banded):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("mode", [["-f"], ["-b", "256"]])
+def test_cudapoa_scores_reach_the_batch(tmp_path, mode):
+    # -m / -n / -g reach the batch in the right places: main passes (mismatch,
+    # gap, match) to get_multi_batch_sizes and (gap, mismatch, match) to
+    # create_batch.  Full alignment (-f) and banded (the default; -b sets the
+    # band width): every printed consensus equals the oracle's with these
+    # scores, which differs from the oracle's with the default scores
+    from oracle import oracle
+    gap, mismatch, match = -2, -4, 5
+    wins = synth.poa_windows(109, 6, 300, 8, 15, 15, 15)
+    p = tmp_path / "windows.txt"
+    _write_cudapoa(p, wins)
+    r = _run(["-i", str(p), "-m", str(match), "-n", str(mismatch), "-g", str(gap)] + mode)
+    assert r.returncode == 0, r.stderr
+    lines = r.stdout.split("\n")[:-1]
+    banded = mode[0] == "-b"
+    want, default = [], []
+    for w in wins:
+        max_seq = max(len(s) for s in w)
+        kw = dict(banded=banded, band_width=256, max_nodes=((4 if banded else 3) * max_seq + 3) // 4 * 4,
+                  max_consensus=2 * max_seq, max_seqs=len(w))
+        res = oracle.poa_window(w, gap=gap, mismatch=mismatch, match=match, **kw)
+        assert res.status == 0
+        want.append(res.consensus)
+        default.append(oracle.poa_window(w, **kw).consensus)
+    assert want != default
+    assert lines == want  # one batch: the printed order is the input order
+
+
+@pytest.mark.gpu
 def test_cudapoa_print_order_follows_batch_bins(tmp_path):
     # main.cpp:189-289: windows are binned by get_multi_batch_sizes (utils.cu:24-138)
     # and printed batch by batch in each batch's group order.  A small memory

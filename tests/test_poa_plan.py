@@ -15,13 +15,16 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "poa_plan.json")
 
-DEFAULT = (-8, -6, 8)    # gap, mismatch, match: 16-bit scores up to 1,365 bases
+DEFAULT = (-8, -6, 8)    # gap, mismatch, match: 16-bit scores up to 1,489 bases
 BIG = (-80, -60, 80)     # 32-bit scores at every length
 # every max_sequence_size of the tests and of bench.py's configs, and the
 # lengths the full-alignment plan branches on
 FULL_LENGTHS = [128, 130, 256, 400, 600, 700, 900, 1000, 1100, 1600, 1700, 2200, 4400, 10600,
                 512, 513, 1024, 1025, 2048, 2049, 4096, 4097, 8192]
 BAND_LENGTHS = [256, 600, 1100, 4400, 10600]
+SCORE_SETS = [(-4, -6, 8), (-2, -4, 5), (-8, -9, 8), (-8, -8, 8), (-8, -16, 8), (0, -6, 8), (-8, -6, 0), (-8, 0, 8),
+              (-1, -1, 1), (0, 0, 0), (-127, -1, 128), (-127, -6, 128), (-127, -1, 129), (-127, -6, 129),
+              (-20, -1, 40), (-15, -20, 45), (-30, -70, 90)]
 SHAPES = ["8,1", "16,1", "24,1", "32,1", "8,2", "8,3", "8,4", "16,4", "4,4", "8,8", "16,8"]
 
 
@@ -60,6 +63,13 @@ def grid():
         for v in values:
             for a in some:
                 g.append((dict(d, **{name: v}), a))
+    # the score sets of tests/test_poa_scores.py: widths by the reference's rule, and no
+    # packed 16-bit rows where the E domain does not fit ((-20, -1, 40) and (-15, -20, 45) at 600,
+    # (-127, -1, 129) at 128: lds_kernel 0)
+    for sc in SCORE_SETS:
+        for ms in (128, 400, 600):
+            g.append(({}, _args(ms, scores=sc)))
+            g.append(({}, _args(ms, banded=1, bw=128 if ms == 128 else 256, scores=sc)))
     # forced anti-diagonal pass with fewer waves, and the switches without GWAMD_DIAG=1: ignored
     g.append((dict(d, GWAMD_BAND_FWD="ad", GWAMD_BAND_AD_WAVES="2"), _args(1100, banded=1)))
     g.append(({"GWAMD_DIAG": "0", "GWAMD_POA_KERNEL": "v1", "GWAMD_TB_WALK": "scalar", "GWAMD_POA_ADD": "serial"},

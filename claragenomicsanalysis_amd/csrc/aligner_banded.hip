@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "aligner_common.hpp"
+#include "aligner_plan.hpp"
 #include <type_traits>
 #include "aligner_device.hpp"
 
@@ -1590,105 +1591,33 @@ __global__ void __launch_bounds__(1024) ukkonen_wide_kernel(Args a)
 } // namespace aln
 } // namespace gwamd
 
-extern "C" hipError_t gwamd_internal_banded_launch(const gwamd::aln::Args* a, int algo, int grid, hipStream_t stream)
+// This file's part of the aligner kernel table (aligner_kernels.hip has the
+// resolver, the launch and the occupancy query over it).
+extern "C" gwamd::aln::KernelRef gwamd_internal_banded_kernel(const gwamd::aln::KernelKey* k)
 {
     using namespace gwamd::aln;
-    if (a->n <= 0)
-        return hipSuccess;
-    if (algo == 2)
+    if (k->algo == kAlgoBanded)
     {
-        const int nwv = a->band_waves;
-        if (nwv != 1 && nwv != 4 && nwv != 8 && nwv != 16)
-            return hipErrorInvalidValue;
-        const void* k = nwv == 4    ? reinterpret_cast<const void*>(myers_banded_kernel<4>)
-                        : nwv == 8  ? reinterpret_cast<const void*>(myers_banded_kernel<8>)
-                        : nwv == 16 ? reinterpret_cast<const void*>(myers_banded_kernel<16>)
-                                    : reinterpret_cast<const void*>(myers_banded_kernel<1>);
-        if (a->lds_bytes > 65536)
+        // (in the order the kernels have always been instantiated, which is
+        // their order in the code object)
+        static const struct
         {
-            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, a->lds_bytes);
-            if (e != hipSuccess)
-                return e;
-        }
-        if (nwv == 4)
-            hipLaunchKernelGGL(myers_banded_kernel<4>, dim3(grid), dim3(kWave * 4), size_t(a->lds_bytes), stream, *a);
-        else if (nwv == 8)
-            hipLaunchKernelGGL(myers_banded_kernel<8>, dim3(grid), dim3(kWave * 8), size_t(a->lds_bytes), stream, *a);
-        else if (nwv == 16)
-            hipLaunchKernelGGL(myers_banded_kernel<16>, dim3(grid), dim3(kWave * 16), size_t(a->lds_bytes), stream, *a);
-        else
-            hipLaunchKernelGGL(myers_banded_kernel<1>, dim3(grid), dim3(kWave), size_t(a->lds_bytes), stream, *a);
+            int waves;
+            const void* fn;
+        } kWaves[] = {{4, reinterpret_cast<const void*>(&myers_banded_kernel<4>)},
+                      {8, reinterpret_cast<const void*>(&myers_banded_kernel<8>)},
+                      {16, reinterpret_cast<const void*>(&myers_banded_kernel<16>)},
+                      {1, reinterpret_cast<const void*>(&myers_banded_kernel<1>)}};
+        for (const auto& w : kWaves)
+            if (w.waves == k->band_waves)
+                return {w.fn, kWave * w.waves};
+        return {nullptr, 0};
     }
-    else if (a->uk_threads > 0)
-    {
-        if (a->uk_threads % kWave != 0 || a->uk_threads > 1024)
-            return hipErrorInvalidValue;
-        if (a->lds_bytes > 65536)
-        {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ukkonen_wide_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, a->lds_bytes);
-            if (e != hipSuccess)
-                return e;
-        }
-        hipLaunchKernelGGL(ukkonen_wide_kernel, dim3(grid), dim3(a->uk_threads), size_t(a->lds_bytes), stream, *a);
-    }
-    else
-    {
-        if (a->lds_bytes > 65536)
-        {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ukkonen_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, a->lds_bytes);
-            if (e != hipSuccess)
-                return e;
-        }
-        hipLaunchKernelGGL(ukkonen_kernel, dim3(grid), dim3(kWave), size_t(a->lds_bytes), stream, *a);
-    }
-    return hipGetLastError();
-}
-
-extern "C" hipError_t gwamd_internal_banded_occupancy(int algo, int lds_bytes, int band_waves, int* blocks_per_cu)
-{
-    using namespace gwamd::aln;
-    if (algo == 2)
-    {
-        auto occ = [&](auto kern, int threads) -> hipError_t {
-            if (lds_bytes > 65536)
-            {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                if (e != hipSuccess)
-                    return e;
-            }
-            return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kern, threads, size_t(lds_bytes));
-        };
-        if (band_waves == 4)
-            return occ(myers_banded_kernel<4>, kWave * 4);
-        if (band_waves == 8)
-            return occ(myers_banded_kernel<8>, kWave * 8);
-        if (band_waves == 16)
-            return occ(myers_banded_kernel<16>, kWave * 16);
-        return occ(myers_banded_kernel<1>, kWave);
-    }
-    if (lds_bytes > 65536)
-    {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ukkonen_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ukkonen_kernel, kWave, size_t(lds_bytes));
-}
-
-extern "C" hipError_t gwamd_internal_ukkonen_wide_occupancy(int threads, int lds_bytes, int* blocks_per_cu)
-{
-    using namespace gwamd::aln;
-    if (lds_bytes > 65536)
-    {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ukkonen_wide_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ukkonen_wide_kernel, threads,
-                                                        size_t(lds_bytes));
+    if (k->algo != kAlgoUkkonen)
+        return {nullptr, 0};
+    if (k->uk_threads == 0)
+        return {reinterpret_cast<const void*>(&ukkonen_kernel), kWave};
+    if (k->uk_threads < 0 || k->uk_threads % kWave != 0 || k->uk_threads > 1024)
+        return {nullptr, 0};
+    return {reinterpret_cast<const void*>(&ukkonen_wide_kernel), k->uk_threads};
 }

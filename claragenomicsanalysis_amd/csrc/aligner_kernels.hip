@@ -20,6 +20,7 @@
 
 #include "aligner_common.hpp"
 #include "aligner_device.hpp"
+#include "aligner_plan.hpp"
 
 #include <climits>
 #include <type_traits>
@@ -1202,33 +1203,57 @@ __global__ void __launch_bounds__(kWave) myers_kernel(Args a)
 } // namespace aln
 } // namespace gwamd
 
-extern "C" hipError_t gwamd_internal_align_launch(const gwamd::aln::Args* a, int algo, int grid, hipStream_t stream)
+// ---------------------------------------------------------------------------
+// Kernel table and launch.  gwamd_internal_aligner_kernel resolves a key to
+// its kernel (fn == nullptr: none); launch and occupancy are the same few
+// steps over whatever it finds.  Taking a kernel's host handle needs no device.
+extern "C" gwamd::aln::KernelRef gwamd_internal_banded_kernel(const gwamd::aln::KernelKey* k); // aligner_banded.hip
+
+extern "C" gwamd::aln::KernelRef gwamd_internal_aligner_kernel(const gwamd::aln::KernelKey* k)
 {
     using namespace gwamd::aln;
-    if (a->n <= 0)
-        return hipSuccess;
-    if (algo == 0 && a->long_mode)
-        hipLaunchKernelGGL(hm_kernel<true>, dim3(grid), dim3(kWave), size_t(a->lds_bytes), stream, *a);
-    else if (algo == 0)
-        hipLaunchKernelGGL(hm_kernel<false>, dim3(grid), dim3(kWave), size_t(a->lds_bytes), stream, *a);
-    else if (a->long_mode)
-        hipLaunchKernelGGL(myers_kernel<true>, dim3(grid), dim3(kWave), size_t(a->lds_bytes), stream, *a);
-    else
-        hipLaunchKernelGGL(myers_kernel<false>, dim3(grid), dim3(kWave), size_t(a->lds_bytes), stream, *a);
-    return hipGetLastError();
+    if (k->algo == kAlgoHm)
+        return {k->long_mode ? reinterpret_cast<const void*>(&hm_kernel<true>)
+                             : reinterpret_cast<const void*>(&hm_kernel<false>),
+                kWave};
+    if (k->algo == kAlgoMyers)
+        return {k->long_mode ? reinterpret_cast<const void*>(&myers_kernel<true>)
+                             : reinterpret_cast<const void*>(&myers_kernel<false>),
+                kWave};
+    return gwamd_internal_banded_kernel(k);
 }
 
-extern "C" hipError_t gwamd_internal_align_occupancy(int algo, int lds_bytes, int* blocks_per_cu)
+// above 64 KB of dynamic LDS a kernel has to be told so first
+static hipError_t prepare(const gwamd::aln::KernelRef& k, int lds_bytes)
 {
-    using namespace gwamd::aln;
-    if (algo == 0)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, hm_kernel<false>, kWave, size_t(lds_bytes));
-    if (algo == 100)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, hm_kernel<true>, kWave, size_t(lds_bytes));
-    if (algo == 101)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, myers_kernel<true>, kWave,
-                                                            size_t(lds_bytes));
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, myers_kernel<false>, kWave, size_t(lds_bytes));
+    if (k.fn == nullptr)
+        return hipErrorInvalidValue;
+    if (lds_bytes <= 65536)
+        return hipSuccess;
+    return hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+}
+
+// Workgroups of the kernel with lds_bytes of dynamic LDS that are resident on one CU at once.
+extern "C" hipError_t gwamd_internal_aligner_occupancy(const gwamd::aln::KernelKey* key, int lds_bytes,
+                                                       int* blocks_per_cu)
+{
+    const gwamd::aln::KernelRef k = gwamd_internal_aligner_kernel(key);
+    if (const hipError_t e = prepare(k, lds_bytes))
+        return e;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k.fn, k.threads, size_t(lds_bytes));
+}
+
+// Internal launch ABI used by the C++ aligner (aligner_batch.cpp): `grid` workgroups, a->lds_bytes of LDS.
+extern "C" hipError_t gwamd_internal_aligner_launch(const gwamd::aln::Args* a, const gwamd::aln::KernelKey* key,
+                                                    int grid, hipStream_t stream)
+{
+    if (a->n <= 0)
+        return hipSuccess;
+    const gwamd::aln::KernelRef k = gwamd_internal_aligner_kernel(key);
+    if (const hipError_t e = prepare(k, a->lds_bytes))
+        return e;
+    void* args[] = {const_cast<gwamd::aln::Args*>(a)};
+    return hipLaunchKernel(k.fn, dim3(grid), dim3(k.threads), args, size_t(a->lds_bytes), stream);
 }
 
 #ifdef GWAMD_ALN_PROFILE

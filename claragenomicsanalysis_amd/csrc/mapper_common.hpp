@@ -3,8 +3,6 @@
 // mapper_batch.cpp).
 #pragma once
 
-#include <claraparabricks/genomeworks/utils/allocator.hpp>
-
 #include "host_common.hpp"
 
 #include <cstdint>
@@ -17,84 +15,12 @@ namespace gwamd
 namespace mapper
 {
 
-using Budget = std::shared_ptr<claraparabricks::genomeworks::DeviceBudget>;
+using gwamd::host::Budget;
+using gwamd::host::DevBuf;
 
 constexpr int kMaxKmerSize   = 32;  // 2 bits per base in a 64-bit representation
 constexpr int kMaxWindowSize = 255; // bounds the halo a sketch tile stages in LDS
 constexpr int64_t kDefaultMaxAnchors = int64_t(1) << 31;
-
-// Device array whose bytes are reserved from the caller's pool (null: no
-// pool) for its lifetime; freed and released on every path out of scope.
-template <typename T>
-class DevBuf
-{
-public:
-    DevBuf() = default;
-    DevBuf(size_t n, const Budget& budget) { alloc(n, budget); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept { take(o); }
-    DevBuf& operator=(DevBuf&& o) noexcept
-    {
-        if (this != &o)
-        {
-            free();
-            take(o);
-        }
-        return *this;
-    }
-    ~DevBuf() { free(); }
-
-    void alloc(size_t n, const Budget& budget)
-    {
-        free();
-        if (n == 0)
-            return;
-        const int64_t bytes = int64_t(n * sizeof(T));
-        if (budget && budget->reserve(bytes, bytes) < 0)
-            throw std::runtime_error("Not enough memory left in the device allocator pool: " + std::to_string(bytes) +
-                                     " bytes asked, " + std::to_string(budget->capacity() - budget->used()) +
-                                     " of " + std::to_string(budget->capacity()) + " left.");
-        void* p            = nullptr;
-        const hipError_t e = hipMalloc(&p, size_t(bytes));
-        if (e != hipSuccess)
-        {
-            if (budget)
-                budget->release(bytes);
-            throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e) + " at hipMalloc of " +
-                                     std::to_string(bytes) + " bytes");
-        }
-        p_      = static_cast<T*>(p);
-        n_      = n;
-        budget_ = budget;
-    }
-    void free()
-    {
-        if (!p_)
-            return;
-        (void)hipFree(p_);
-        if (budget_)
-            budget_->release(int64_t(n_ * sizeof(T)));
-        p_ = nullptr;
-        n_ = 0;
-        budget_.reset();
-    }
-    T* data() const { return p_; }
-    size_t size() const { return n_; }
-
-private:
-    void take(DevBuf& o)
-    {
-        p_      = o.p_;
-        n_      = o.n_;
-        budget_ = std::move(o.budget_);
-        o.p_    = nullptr;
-        o.n_    = 0;
-    }
-    T* p_     = nullptr;
-    size_t n_ = 0;
-    Budget budget_;
-};
 
 // cudamapper::Anchor (types.hpp), four u32
 struct AnchorRecord

@@ -341,3 +341,42 @@ def test_shared_allocator_pool_caps_aligners():
     # a pool too small for the fixed buffers plus one slot throws
     with pytest.raises(RuntimeError):
         CudaAlignerBatch(5000, 5000, 4000, allocator=DeviceAllocator(1 << 20))
+
+
+def test_plan_is_what_the_aligner_built(monkeypatch):
+    # the plan the CPU tests pin (tests/test_aligner_plan.py), asked with this
+    # device's facts, is the one the constructor acted on
+    from test_aligner_plan import ENV_NAMES, _lib, plan
+    for k in ENV_NAMES:  # no switches (restored after the test)
+        monkeypatch.setenv(k, "")
+    L = _lib()
+    cases = [(algo, 300, 330, 64) for algo, _ in ALGOS] + [("myers_banded", 12000, 12000, 2)]
+    for algo, q, t, n in cases:
+        grid, device_bytes = CudaAlignerBatch(q, t, n, algorithm=algo).config()
+        p = plan(L, {}, [[a for a, _ in ALGOS].index(algo), q, t, n, 0, 0, 0, 0, 0, 0, 0, 0])
+        assert "error" not in p, p
+        assert p["kernel"] == 1
+        assert grid == p["slots"], (algo, q)
+        assert device_bytes == p["fixed_bytes"] + p["slots"] * p["slot_bytes"], (algo, q)
+
+
+def test_failed_construction_returns_the_pool():
+    # a device allocation that fails part-way through construction (the first
+    # array alone is twice the card's memory, so the runtime refuses it) gives
+    # back the pool reservation and whatever was allocated before it
+    import torch
+    from claragenomicsanalysis_amd.cudaaligner import DeviceAllocator
+    pool = DeviceAllocator(1 << 42)
+    total = torch.cuda.get_device_properties(0).total_memory
+    n = total // 5000 + 1
+    with pytest.raises(RuntimeError):
+        CudaAlignerBatch(5000, 5000, n, allocator=pool)
+    assert pool.used == 0
+    qs, ts = synth.pairs(9, 64, 300, 330, 10, 10, 10)
+    b = CudaAlignerBatch(max(len(q) for q in qs), max(len(t) for t in ts), 64, allocator=pool)
+    assert pool.used == b.config()[1]
+    for q, t in zip(qs, ts):
+        assert b.add_alignment(q, t) == 0
+    b.align_all()
+    want, _ = oracle.align_batch(list(zip(qs, ts)), oracle.ALIGN_HM, max(len(q) for q in qs))
+    assert [states(a) for a in b.get_alignments()] == want

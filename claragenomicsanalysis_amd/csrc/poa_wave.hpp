@@ -209,9 +209,14 @@ __device__ __forceinline__ void finish_window(const Buffers& b, const Dims& d, i
                     }
                 }
             }
-            for (int sr = lane; sr < nseq; sr += kWave)
+            // The update writes seq_begin[s] with a read's first position, so an
+            // empty read leaves it unwritten (whatever an earlier window left in
+            // the slot): such a read begins at node 0, as in a zeroed array.  An
+            // empty graph has no node and no column: its rows are the terminator.
+            const int first_seq = b.windows[w].first_seq;
+            for (int sr = lane; sr < nseq && node_count > 0; sr += kWave)
             {
-                const int node                                = int(seq_begin[sr]);
+                const int node = b.seq_len[first_seq + sr] > 0 ? int(seq_begin[sr]) : 0;
                 msa_out[size_t(sr) * d.max_consensus + int(mpos[node])] = g.base[node];
             }
         }

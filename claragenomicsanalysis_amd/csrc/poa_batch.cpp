@@ -67,33 +67,17 @@ bool use32bit_size(const BatchSize& bs, bool banded)
 
 inline int64_t align8(int64_t v) { return (v + 7) & ~int64_t(7); }
 
-// Device bytes per window as accounted by the reference
-// (allocate_block.hpp:292-338); sizes of SizeT/ScoreT are the chosen types.
-int64_t reference_device_bytes_per_poa(const BatchSize& bs, bool banded, bool msa, int size_bytes)
+// The BatchSize numbers of the batch's alignment mode, for the plan (poa_plan.hpp)
+gwamd::poa::RefSizes ref_sizes(const BatchSize& bs, bool banded)
 {
-    const int64_t gdim  = banded ? bs.max_matrix_graph_dimension_banded : bs.max_matrix_graph_dimension;
-    const int64_t nodes = banded ? bs.max_nodes_per_window_banded : bs.max_nodes_per_window;
-    const int64_t E = gwamd::poa::kMaxEdges, A = gwamd::poa::kMaxAlignments, S = bs.max_sequences_per_poa;
-    int64_t b = 0;
-    b += bs.max_consensus_size;                                   // consensus
-    b += !msa ? bs.max_consensus_size * 2 : 0;                    // coverage
-    b += msa ? bs.max_consensus_size * S : 0;                     // msa
-    b += S * bs.max_sequence_size * 2;                            // sequences + weights
-    b += S * size_bytes;                                          // sequence lengths
-    b += 32;                                                      // WindowDetails
-    b += msa ? S * size_bytes : 0;                                // sequence_begin_nodes_ids
-    b += nodes;                                                   // nodes
-    b += nodes * A * size_bytes + nodes * 2;                      // node_alignments (+count)
-    b += nodes * E * size_bytes + nodes * 2;                      // incoming edges (+count)
-    b += nodes * E * size_bytes + nodes * 2;                      // outgoing edges (+count)
-    b += nodes * E * 2 * 2;                                       // in/out edge weights
-    b += nodes * size_bytes * 2 + nodes * 2;                      // sorted, node map, local count
-    b += !msa ? nodes * 4 + nodes * size_bytes : 0;               // consensus scores / predecessors
-    b += nodes + nodes + nodes * size_bytes;                      // marks, check, nodes_to_visit
-    b += nodes * 2;                                               // node coverage
-    b += msa ? nodes * E * S * 2 + nodes * E * 2 + nodes * size_bytes : 0; // edge coverage, msa pos
-    b += gdim * size_bytes * 2;                                   // alignment graph/read
-    return b;
+    gwamd::poa::RefSizes rs{};
+    rs.seq_len   = bs.max_sequence_size;
+    rs.consensus = bs.max_consensus_size;
+    rs.seqs      = bs.max_sequences_per_poa;
+    rs.nodes     = banded ? bs.max_nodes_per_window_banded : bs.max_nodes_per_window;
+    rs.graph_dim = banded ? bs.max_matrix_graph_dimension_banded : bs.max_matrix_graph_dimension;
+    rs.seq_dim   = banded ? bs.alignment_band_width + gwamd::poa::kBandPad : bs.max_matrix_sequence_dimension;
+    return rs;
 }
 
 // The batch constructor's planning steps: score and size widths, capacities,
@@ -124,12 +108,6 @@ gwamd::poa::Dims plan_batch(const BatchSize& bs, bool banded, int8_t output_mask
     return dims;
 }
 
-struct DevBuf
-{
-    void* p = nullptr;
-    size_t n = 0;
-};
-
 } // namespace
 
 class PoaBatch : public Batch
@@ -149,79 +127,36 @@ public:
         detail::check_non_negative(bs.max_sequences_per_poa, "Maximum sequences per POA has to be non-negative");
         ScopedDevice dev(device_id_);
         dims_ = plan_batch(bs_, banded_, output_mask_, gap_, mismatch_, match_, tune_, score_bits_, size_bits_);
-        const int sz      = size_bits_ / 8;
-        const int sbytes  = score_bits_ / 8;
-        const bool msa    = (output_mask_ & OutputType::msa) != 0;
-        const int64_t gdim = banded_ ? bs_.max_matrix_graph_dimension_banded : bs_.max_matrix_graph_dimension;
-        const int64_t ref_seq_dim = banded_ ? bs_.alignment_band_width + gwamd::poa::kBandPad : bs_.max_matrix_sequence_dimension;
-
-        // BatchBlock ctor (allocate_block.hpp:51-91)
-        const int64_t per_poa = reference_device_bytes_per_poa(bs_, banded_, msa, sz);
-        if (int64_t(max_mem) < per_poa)
-        {
-            throw std::runtime_error(std::string("Require at least ") + std::to_string(per_poa) +
-                                     " bytes of device memory per CUDAPOA batch to process correctly.");
-        }
-        const int64_t ref_score_matrix = ref_seq_dim * gdim * sbytes;
-        int64_t max_poas               = int64_t(max_mem) / (per_poa + ref_score_matrix);
-
-        // this build's footprint: graph + inputs + outputs per window, and the
-        // forward/traceback scratch per slot.  The LDS and banded kernels run
-        // a persistent grid of as many workgroups as are resident at once, so
-        // they need only that many slots however many windows the batch holds.
-        const int64_t wbytes = window_bytes(sz, msa);
-        const int64_t sbytes_slot = slot_bytes(sz, sbytes);
-        int64_t own_cap = int64_t(max_mem) / (wbytes + sbytes_slot); // a slot per window
-        int64_t resident = 0;
+        const int sz     = size_bits_ / 8;
+        const int sbytes = score_bits_ / 8;
+        const bool msa   = (output_mask_ & OutputType::msa) != 0;
+        // the device's facts, asked once: the plan (poa_plan.cpp) decides every number from them
+        gwamd::poa::PoaDeviceFacts facts;
+        GWAMD_HIP_CHECK(hipDeviceGetAttribute(&facts.cus, hipDeviceAttributeMultiprocessorCount, device_id_));
         if (dims_.lds_kernel)
-        {
-            int cus = 0;
-            GWAMD_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id_));
-            resident = int64_t(gwamd_internal_poa_blocks_per_cu(&dims_, score_bits_, size_bits_, banded_ ? 1 : 0,
-                                                                msa ? 1 : 0)) * cus;
-            if (tune_.slots > 0) // diagnostic: a smaller persistent grid
-                resident = std::min<int64_t>(resident > 0 ? resident : INT32_MAX, tune_.slots);
-            if (resident > 0 && own_cap > resident)
-                own_cap = std::max(own_cap, (int64_t(max_mem) - resident * sbytes_slot) / wbytes);
-        }
-        max_poas = std::min<int64_t>(max_poas, own_cap);
-        if (max_poas < 1)
-            throw std::runtime_error("Require more device memory per CUDAPOA batch to process correctly.");
-        max_poas_ = int32_t(std::min<int64_t>(max_poas, INT32_MAX));
-        slots_    = resident > 0 ? int32_t(std::min<int64_t>(resident, max_poas_)) : max_poas_;
-        blocks_per_cu_ = resident > 0 ? int32_t(resident) : 0;
-
-        // score budget (allocate_block.hpp:196-201): what the reference's slab
-        // leaves for the variable-width score matrices
-        scorebuf_alloc_ = int64_t(max_mem) - reference_fixed_slab(sz, msa);
-        if (scorebuf_alloc_ < 0)
-            scorebuf_alloc_ = 0;
-
-        allocate(sz, sbytes, msa);
+            facts.blocks_per_cu = gwamd_internal_poa_blocks_per_cu(&dims_, score_bits_, size_bits_, banded_ ? 1 : 0,
+                                                                   msa ? 1 : 0);
+        order_cus_ = tune_.order_cus > 0 ? tune_.order_cus : facts.cus; // diagnostic: order for fewer CUs
+        cap_ = gwamd::poa::plan_capacity(facts, dims_, ref_sizes(bs_, banded_), sz, sbytes, msa, int64_t(max_mem),
+                                         tune_.slots);
+        lay_ = gwamd::poa::plan_layout(dims_, sz, sbytes, msa, cap_.max_poas, cap_.slots);
+        allocate();
         // pinned host staging for a full batch, as the reference's BatchBlock
         // allocates it up front (allocate_block.hpp:84-118), so filling a
         // batch never re-pins memory (capped; beyond the cap it grows)
         {
             const size_t cap_b = size_t(2) << 30;
-            const size_t in_b  = std::min(cap_b, size_t(max_poas_) * size_t(bs_.max_sequences_per_poa) *
+            const size_t in_b  = std::min(cap_b, size_t(cap_.max_poas) * size_t(bs_.max_sequences_per_poa) *
                                                     size_t(bs_.max_sequence_size) + 16);
             h_seqs_.reserve(in_b, stream_);
             h_wts_.reserve(in_b, stream_);
-            const size_t nseq = std::min(cap_b / 8, size_t(max_poas_) * size_t(bs_.max_sequences_per_poa));
+            const size_t nseq = std::min(cap_b / 8, size_t(cap_.max_poas) * size_t(bs_.max_sequences_per_poa));
             h_len_.reserve(nseq * 4, stream_);
             h_off_.reserve(nseq * 8, stream_);
-            h_win_.reserve(size_t(max_poas_) * sizeof(gwamd::poa::WindowDesc), stream_);
+            h_win_.reserve(size_t(cap_.max_poas) * sizeof(gwamd::poa::WindowDesc), stream_);
         }
         bid_ = batches_++;
         reset();
-    }
-
-    ~PoaBatch() override
-    {
-        (void)hipSetDevice(device_id_);
-        for (auto* b : {&d_seqs_, &d_wts_, &d_len_, &d_off_, &d_win_, &d_slab_, &d_codes_})
-            if (b->p)
-                (void)hipFree(b->p);
     }
 
     StatusType add_poa_group(std::vector<StatusType>& per_seq_status, const Group& poa_group) override
@@ -254,78 +189,32 @@ public:
     {
         ScopedDevice dev(device_id_);
         const size_t nb = num_bases_;
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.p, h_seqs_.as<uint8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_wts_.p, h_wts_.as<int8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_len_.p, h_len_.as<int32_t>(), size_t(num_seqs_) * 4, hipMemcpyHostToDevice,
-                                       stream_));
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_off_.p, h_off_.as<int64_t>(), size_t(num_seqs_) * 8, hipMemcpyHostToDevice,
-                                       stream_));
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_win_.p, h_win_.as<gwamd::poa::WindowDesc>(),
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.data(), h_seqs_.as<uint8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_wts_.data(), h_wts_.as<int8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_len_.data(), h_len_.as<int32_t>(), size_t(num_seqs_) * 4,
+                                       hipMemcpyHostToDevice, stream_));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_off_.data(), h_off_.as<int64_t>(), size_t(num_seqs_) * 8,
+                                       hipMemcpyHostToDevice, stream_));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_win_.data(), h_win_.as<gwamd::poa::WindowDesc>(),
                                        size_t(poa_count_) * sizeof(gwamd::poa::WindowDesc), hipMemcpyHostToDevice,
                                        stream_));
-        plan_launch_order();
-    }
-
-    // Queue order of the windows.  Workgroups i, i + C, i + 2C, ... (C =
-    // CUs) share a CU; windows are ranked by estimated DP cells and the
-    // first grid's worth is dealt to those rounds in snake order, so every CU
-    // gets a mix of heavy and light windows.  When the batch holds more
-    // windows than the persistent grid has slots, the rest follow heaviest
-    // first and are dequeued by whichever workgroup finishes first (longest
-    // processing time first).  Outputs stay indexed by window.
-    void plan_launch_order()
-    {
+        // the windows' queue order (plan_window_order, poa_plan.cpp), staged
+        // pinned so the copy stays asynchronous (generate_poa does not block)
         bufs_.order = nullptr;
         bufs_.head  = nullptr;
-        int cus     = 0;
-        GWAMD_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id_));
-        if (tune_.order_cus > 0) // diagnostic: plan for fewer CUs
-            cus = tune_.order_cus;
-        const int n           = poa_count_;
-        const bool persistent = dims_.lds_kernel != 0 && n > slots_;
-        if (!persistent && (cus <= 0 || n <= cus))
+        const auto kind = gwamd::poa::plan_window_order(h_win_.as<gwamd::poa::WindowDesc>(), h_len_.as<int32_t>(),
+                                                        poa_count_, order_cus_, cap_.slots, dims_.lds_kernel != 0,
+                                                        order_);
+        if (kind == gwamd::poa::kNoOrder)
             return;
-        const auto* wd = h_win_.as<gwamd::poa::WindowDesc>();
-        const auto* ln = h_len_.as<int32_t>();
-        std::vector<std::pair<int64_t, int32_t>> cost(static_cast<size_t>(n));
-        for (int w = 0; w < n; w++)
-        {
-            int64_t sum = 0, mx = 0;
-            for (int s = 0; s < wd[w].num_seqs; s++)
-            {
-                const int64_t l = ln[wd[w].first_seq + s];
-                mx              = std::max(mx, l);
-                if (s > 0)
-                    sum += l;
-            }
-            cost[size_t(w)] = {-sum * mx, w}; // heaviest first, ties by window
-        }
-        std::sort(cost.begin(), cost.end());
-        // pinned, so the copy stays asynchronous (generate_poa does not block)
-        h_order_.reserve(size_t(n) * 4, stream_);
-        int32_t* order = h_order_.as<int32_t>();
-        const int m    = persistent ? slots_ : n; // positions placed statically
-        for (int k = 0; k < m; k++)
-        {
-            if (cus <= 0)
-            {
-                order[k] = cost[size_t(k)].second;
-                continue;
-            }
-            const int t = k / cus, pos = k % cus;
-            const int r = std::min(cus, m - t * cus); // workgroups in this round
-            const int j = (t % 2 == 0) ? pos : r - 1 - pos;
-            order[t * cus + j] = cost[size_t(k)].second;
-        }
-        for (int k = m; k < n; k++)
-            order[k] = cost[size_t(k)].second;
-        const size_t order_off = (size_t(max_poas_) * sizeof(gwamd::poa::WindowDesc) + 15) & ~size_t(15);
-        int32_t* d_order       = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(d_win_.p) + order_off);
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_order, order, size_t(n) * 4, hipMemcpyHostToDevice, stream_));
+        const size_t order_b = size_t(poa_count_) * 4;
+        h_order_.reserve(order_b, stream_);
+        std::memcpy(h_order_.as<int32_t>(), order_.data(), order_b);
+        int32_t* d_order = reinterpret_cast<int32_t*>(d_win_.data() + lay_.order_off);
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_order, h_order_.as<int32_t>(), order_b, hipMemcpyHostToDevice, stream_));
         bufs_.order = d_order;
-        if (persistent)
-            bufs_.head = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(d_win_.p) +
-                                                    ((order_off + size_t(max_poas_) * 4 + 15) & ~size_t(15)));
+        if (kind == gwamd::poa::kOrderAndHead)
+            bufs_.head = reinterpret_cast<int32_t*>(d_win_.data() + lay_.head_off);
     }
 
     void launch()
@@ -335,7 +224,7 @@ public:
         ScopedDevice dev(device_id_);
         gwamd::poa::Buffers b = bufs_;
         b.num_windows         = poa_count_;
-        b.num_slots           = slots_;
+        b.num_slots           = cap_.slots;
         if (b.head) // the dequeue counter starts at 0 for every launch
             GWAMD_HIP_CHECK(hipMemsetAsync(b.head, 0, sizeof(int32_t), stream_));
         gwamd::poa::Scores sc{gap_, mismatch_, match_};
@@ -530,7 +419,7 @@ public:
         num_bases_          = 0;
         num_seqs_           = 0;
         next_scores_offset_ = 0;
-        avail_scorebuf_     = scorebuf_alloc_;
+        avail_scorebuf_     = cap_.scorebuf_alloc;
         generated_          = false;
     }
 
@@ -552,15 +441,15 @@ public:
     const std::vector<int32_t>& host_final_nodes() const { return h_final_nodes_; }
     int32_t window_num_seqs(int32_t w) const { return h_win_.as<const gwamd::poa::WindowDesc>()[w].num_seqs; }
     int8_t output_mask() const { return output_mask_; }
-    int64_t device_bytes() const { return int64_t(d_slab_.n + d_codes_.n + d_seqs_.n + d_wts_.n + d_len_.n + d_off_.n + d_win_.n); }
+    int64_t device_bytes() const { return lay_.device_bytes(); }
     int32_t kernel_kind() const
     {
         return dims_.lds_kernel == 3 ? (dims_.band_ad ? 4 : 3) : (dims_.lds_kernel ? 2 : 1);
     }
-    int32_t max_poas() const { return max_poas_; }
+    int32_t max_poas() const { return cap_.max_poas; }
     int32_t max_sequence_size() const { return bs_.max_sequence_size; }
-    int32_t slots() const { return slots_; }
-    int32_t resident_slots() const { return blocks_per_cu_; }
+    int32_t slots() const { return cap_.slots; }
+    int32_t resident_slots() const { return cap_.resident; }
     void set_spoa_accurate(bool on) { dims_.spoa_accurate = on ? 1 : 0; }
     bool spoa_accurate() const { return dims_.spoa_accurate != 0; }
 
@@ -597,145 +486,34 @@ public:
     }
 
 private:
-    // Graph, inputs and outputs of one window.
-    int64_t window_bytes(int sz, bool msa) const
+    // Allocates what the layout (plan_layout) lists and binds the kernels' pointers into it.
+    void allocate()
     {
-        const int64_t mn = dims_.max_nodes, E = gwamd::poa::kMaxEdges, S = dims_.max_seqs;
-        int64_t b        = 0;
-        b += align8(mn) + 4 * align8(mn * 2) + align8(mn * E * 2);   // base, counts, coverage, in_w
-        b += 3 * align8(mn * E * sz) + 2 * align8(mn * sz);           // in_e, out_e, aln, sorted, pos
-        b += align8(dims_.max_consensus) + align8(int64_t(dims_.max_consensus) * 2) + 32; // outputs
-        b += int64_t(S) * dims_.max_seq_len * 2 + S * 12;             // inputs
-        if (msa)
-            b += align8(mn * E * S * 2) + align8(mn * E * 2) + align8(S * sz) +
-                 align8(S * int64_t(dims_.max_consensus));
-        return b;
-    }
-
-    // Forward-pass / traceback / consensus scratch of one slot.
-    int64_t slot_bytes(int sz, int sbytes) const
-    {
-        const int64_t mn = dims_.max_nodes;
-        int64_t b        = 0;
-        b += 2 * align8(int64_t(dims_.aln_cap) * sz);                 // ag, ar
-        b += int64_t(dims_.score_rows) * dims_.score_stride * sbytes; // scores (LDS kernel: spill rows)
-        if (dims_.lds_kernel)
-            b += dims_.aux_stride; // traceback codes, row program, predecessor lists, carries
-        b += align8(mn * 4) + align8(mn * 4 * sz);                    // cscore, cpred
-        return b;
-    }
-
-    // Non-score bytes of the reference slab for max_poas windows
-    // (allocate_block.hpp:121-285, each buffer aligned to 8 B).
-    int64_t reference_fixed_slab(int sz, bool msa) const
-    {
-        const int64_t P = max_poas_, S = bs_.max_sequences_per_poa, E = gwamd::poa::kMaxEdges;
-        const int64_t nodes = banded_ ? bs_.max_nodes_per_window_banded : bs_.max_nodes_per_window;
-        const int64_t gdim  = banded_ ? bs_.max_matrix_graph_dimension_banded : bs_.max_matrix_graph_dimension;
-        const bool cons     = (output_mask_ & OutputType::consensus) != 0;
-        int64_t o           = 0;
-        o += align8(P * bs_.max_consensus_size);
-        o += cons ? align8(P * bs_.max_consensus_size * 2) : 0;
-        o += msa ? align8(P * bs_.max_consensus_size * S) : 0;
-        o += 2 * align8(P * S * bs_.max_sequence_size);
-        o += align8(P * S * sz) + align8(P * 32);
-        o += msa ? align8(P * S * sz) : 0;
-        o += 2 * align8(P * gdim * sz); // alignment graph / read
-        o += align8(P * nodes) + align8(P * nodes * E * sz) + align8(P * nodes * 2);
-        o += align8(P * nodes * E * sz) + align8(P * nodes * 2);
-        o += align8(P * nodes * E * sz) + align8(P * nodes * 2);
-        o += 2 * align8(P * nodes * E * 2);
-        o += 2 * align8(P * nodes * sz) + align8(P * nodes * 2);
-        o += cons ? align8(P * nodes * 4) + align8(P * nodes * sz) : 0;
-        o += 2 * align8(P * nodes) + align8(P * nodes * sz) + align8(P * nodes * 2);
-        o += msa ? align8(P * nodes * E * S * 2) + align8(P * nodes * E * 2) + align8(P * nodes * sz) : 0;
-        return o;
-    }
-
-    void allocate(int sz, int sbytes, bool msa)
-    {
-        const int64_t P = max_poas_, mn = dims_.max_nodes, E = gwamd::poa::kMaxEdges, S = dims_.max_seqs;
-        const int64_t Z = slots_; // scratch slots
-        struct Item
-        {
-            void** dst;
-            int64_t bytes;
-        };
-        void* dummy = nullptr;
-        std::vector<Item> items = {
-            {reinterpret_cast<void**>(&bufs_.base), align8(P * mn)},
-            {reinterpret_cast<void**>(&bufs_.in_cnt), align8(P * mn * 2)},
-            {reinterpret_cast<void**>(&bufs_.out_cnt), align8(P * mn * 2)},
-            {reinterpret_cast<void**>(&bufs_.aln_cnt), align8(P * mn * 2)},
-            {reinterpret_cast<void**>(&bufs_.node_cov), align8(P * mn * 2)},
-            {reinterpret_cast<void**>(&bufs_.in_w), align8(P * mn * E * 2)},
-            {&bufs_.in_e, align8(P * mn * E * sz)},
-            {&bufs_.out_e, align8(P * mn * E * sz)},
-            {&bufs_.aln, align8(P * mn * E * sz)},
-            {&bufs_.sorted, align8(P * mn * sz)},
-            {&bufs_.pos, align8(P * mn * sz)},
-            {&bufs_.ag, align8(Z * dims_.aln_cap * sz)},
-            {&bufs_.ar, align8(Z * dims_.aln_cap * sz)},
-            {reinterpret_cast<void**>(&bufs_.cscore), align8(Z * mn * 4)},
-            {&bufs_.cpred, align8(Z * mn * 4 * sz)},
-            {reinterpret_cast<void**>(&bufs_.cons), align8(P * dims_.max_consensus)},
-            {reinterpret_cast<void**>(&bufs_.cov), align8(P * dims_.max_consensus * 2)},
-            {reinterpret_cast<void**>(&bufs_.cons_len), align8(P * 4)},
-            {reinterpret_cast<void**>(&bufs_.status), align8(P)},
-            {reinterpret_cast<void**>(&bufs_.msa_status), align8(P)},
-            {reinterpret_cast<void**>(&bufs_.msa_len), align8(P * 4)},
-            {reinterpret_cast<void**>(&bufs_.final_nodes), align8(P * 4)},
-            {reinterpret_cast<void**>(&bufs_.cells), align8(P * 8)},
-            {reinterpret_cast<void**>(&bufs_.phase), align8(P * 8 * gwamd::poa::kPhases)},
-            {reinterpret_cast<void**>(&bufs_.order_stats), align8(P * 4 * gwamd::poa::kOrderStats)},
-            {msa ? reinterpret_cast<void**>(&bufs_.edge_cov) : &dummy, msa ? align8(P * mn * E * S * 2) : 0},
-            {msa ? reinterpret_cast<void**>(&bufs_.edge_cov_cnt) : &dummy, msa ? align8(P * mn * E * 2) : 0},
-            {msa ? &bufs_.seq_begin : &dummy, msa ? align8(P * S * sz) : 0},
-            {msa ? reinterpret_cast<void**>(&bufs_.msa) : &dummy, msa ? align8(P * S * dims_.max_consensus) : 0},
-        };
-        // the score matrices go last, 256-B aligned
-        int64_t off = 0;
-        for (auto& it : items)
-            off += it.bytes;
-        off                   = (off + 255) & ~int64_t(255);
-        const int64_t sc_off  = off;
-        const int64_t sc_size = Z * int64_t(dims_.score_rows) * dims_.score_stride * sbytes;
-        d_slab_.n             = size_t(off + sc_size);
-        GWAMD_HIP_CHECK(hipMalloc(&d_slab_.p, d_slab_.n));
-        uint8_t* base = static_cast<uint8_t*>(d_slab_.p);
-        int64_t cur   = 0;
-        for (auto& it : items)
-        {
-            if (it.bytes > 0)
-                *it.dst = base + cur;
-            cur += it.bytes;
-        }
-        bufs_.scores = base + sc_off;
-        if (dims_.lds_kernel)
-        {
-            const size_t code_bytes = size_t(Z) * size_t(dims_.aux_stride);
-            GWAMD_HIP_CHECK(hipMalloc(&d_codes_.p, code_bytes));
-            d_codes_.n   = code_bytes;
-            bufs_.codes = static_cast<uint8_t*>(d_codes_.p);
-        }
-        // inputs (allocate_block.hpp:84: max_poas * max_seqs * max_seq bytes)
-        const int64_t in_bytes = P * S * dims_.max_seq_len + 64;
-        d_seqs_.n              = size_t(in_bytes);
-        d_wts_.n               = size_t(in_bytes);
-        d_len_.n               = size_t(P * S * 4 + 8);
-        d_off_.n               = size_t(P * S * 8 + 8);
-        d_win_.n               = size_t(P * (sizeof(gwamd::poa::WindowDesc) + 4) + 64); // + order, dequeue head
-        for (auto* b : {&d_seqs_, &d_wts_, &d_len_, &d_off_, &d_win_})
-            GWAMD_HIP_CHECK(hipMalloc(&b->p, b->n));
-        bufs_.seqs    = static_cast<const uint8_t*>(d_seqs_.p);
-        bufs_.wts     = static_cast<const int8_t*>(d_wts_.p);
-        bufs_.seq_len = static_cast<const int32_t*>(d_len_.p);
-        bufs_.seq_off = static_cast<const int64_t*>(d_off_.p);
-        bufs_.windows = static_cast<const gwamd::poa::WindowDesc*>(d_win_.p);
+        const gwamd::host::Budget none;
+        d_slab_.alloc(size_t(lay_.slab_bytes), none);
+        d_codes_.alloc(size_t(lay_.codes_bytes), none);
+        d_seqs_.alloc(size_t(lay_.seqs_bytes), none);
+        d_wts_.alloc(size_t(lay_.wts_bytes), none);
+        d_len_.alloc(size_t(lay_.len_bytes), none);
+        d_off_.alloc(size_t(lay_.off_bytes), none);
+        d_win_.alloc(size_t(lay_.win_bytes), none);
+#define GWAMD_F(name, bytes)                                                                                  \
+    if (lay_.name >= 0)                                                                                       \
+        bufs_.name = reinterpret_cast<decltype(bufs_.name)>(d_slab_.data() + lay_.name);
+        GWAMD_POA_SLAB_ARRAYS(GWAMD_F)
+#undef GWAMD_F
+        bufs_.scores  = d_slab_.data() + lay_.scores;
+        bufs_.codes   = d_codes_.data();
+        bufs_.seqs    = d_seqs_.data();
+        bufs_.wts     = reinterpret_cast<const int8_t*>(d_wts_.data());
+        bufs_.seq_len = reinterpret_cast<const int32_t*>(d_len_.data());
+        bufs_.seq_off = reinterpret_cast<const int64_t*>(d_off_.data());
+        bufs_.windows = reinterpret_cast<const gwamd::poa::WindowDesc*>(d_win_.data());
         // status defaults so that reading before generate is defined
-        GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.status, int(StatusType::generic_error), size_t(P), stream_));
-        GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.msa_status, int(StatusType::generic_error), size_t(P), stream_));
-        GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.order_stats, 0, size_t(P) * 4 * gwamd::poa::kOrderStats, stream_));
+        const size_t P = size_t(cap_.max_poas);
+        GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.status, int(StatusType::generic_error), P, stream_));
+        GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.msa_status, int(StatusType::generic_error), P, stream_));
+        GWAMD_HIP_CHECK(hipMemsetAsync(bufs_.order_stats, 0, P * 4 * gwamd::poa::kOrderStats, stream_));
         GWAMD_HIP_CHECK(hipStreamSynchronize(stream_));
     }
 
@@ -764,7 +542,7 @@ private:
     // cudapoa_batch.cuh:471-487
     StatusType add_poa()
     {
-        if (poa_count_ == max_poas_)
+        if (poa_count_ == cap_.max_poas)
             return StatusType::exceeded_maximum_poas;
         h_win_.reserve(size_t(poa_count_ + 1) * sizeof(gwamd::poa::WindowDesc), stream_);
         gwamd::poa::WindowDesc& wd = h_win_.as<gwamd::poa::WindowDesc>()[poa_count_];
@@ -818,10 +596,10 @@ private:
     int16_t gap_, mismatch_, match_;
     bool banded_;
     int32_t score_bits_ = 16, size_bits_ = 16;
-    int32_t max_poas_   = 0;
-    int32_t slots_      = 0; // scratch slots (persistent grid size for the LDS / banded kernels)
-    int32_t blocks_per_cu_ = 0; // resident workgroups on the device (0: v1 kernel)
-    int64_t scorebuf_alloc_ = 0, avail_scorebuf_ = 0, next_scores_offset_ = 0;
+    gwamd::poa::PoaCapacity cap_; // windows, slots, resident grid, score budget (plan_capacity)
+    gwamd::poa::PoaLayout lay_;   // where every device array lies (plan_layout)
+    int32_t order_cus_ = 0;       // CUs the window order is planned for
+    int64_t avail_scorebuf_ = 0, next_scores_offset_ = 0;
     int32_t poa_count_  = 0;
     int32_t num_seqs_   = 0;
     size_t num_bases_   = 0;
@@ -830,9 +608,10 @@ private:
     hipEvent_t ev_start_ = nullptr, ev_stop_ = nullptr; // set_launch_events (multi-batch driver)
     const gwamd::poa::PoaTuning tune_ = gwamd::poa::read_poa_tuning(); // read once, here
     gwamd::poa::Dims dims_{};
-    PinnedBuf h_order_; // workgroup -> window (plan_launch_order)
+    std::vector<int32_t> order_; // queue position -> window (plan_window_order)
+    PinnedBuf h_order_;          // ... staged for the copy
     gwamd::poa::Buffers bufs_{};
-    DevBuf d_seqs_, d_wts_, d_len_, d_off_, d_win_, d_slab_, d_codes_;
+    gwamd::host::DevBuf<uint8_t> d_seqs_, d_wts_, d_len_, d_off_, d_win_, d_slab_, d_codes_;
     PinnedBuf h_seqs_, h_wts_, h_len_, h_off_, h_win_;
     std::vector<uint8_t> h_cons_, h_status_, h_msa_, h_msa_status_, h_g_bases_, h_g_in_e_raw_;
     std::vector<uint16_t> h_cov_, h_g_in_cnt_, h_g_in_w_;
@@ -858,19 +637,16 @@ int64_t estimate_max_poas(const BatchSize& batch_size, bool banded_alignment, bo
     const size_t mem_per_batch = size_t(memory_usage_quota * double(free_device_memory));
     int64_t sizeof_score       = 2;
     int64_t per_poa            = 0;
+    const gwamd::poa::RefSizes rs = ref_sizes(batch_size, banded_alignment);
     if (use32bit_score(batch_size, int16_t(gap_score), int16_t(mismatch_score), int16_t(match_score)))
     {
         sizeof_score = 4;
-        per_poa      = reference_device_bytes_per_poa(batch_size, banded_alignment, msa_flag,
-                                                 use32bit_size(batch_size, banded_alignment) ? 4 : 2);
+        per_poa      = gwamd::poa::reference_device_bytes_per_poa(rs, msa_flag,
+                                                             use32bit_size(batch_size, banded_alignment) ? 4 : 2);
     }
     else
-        per_poa = reference_device_bytes_per_poa(batch_size, banded_alignment, msa_flag, 2);
-    const int64_t seq_dim = banded_alignment ? batch_size.alignment_band_width + gwamd::poa::kBandPad
-                                             : batch_size.max_matrix_sequence_dimension;
-    const int64_t graph_dim = banded_alignment ? batch_size.max_matrix_graph_dimension_banded
-                                               : batch_size.max_matrix_graph_dimension;
-    return int64_t(mem_per_batch) / (per_poa + seq_dim * graph_dim * sizeof_score);
+        per_poa = gwamd::poa::reference_device_bytes_per_poa(rs, msa_flag, 2);
+    return int64_t(mem_per_batch) / (per_poa + rs.seq_dim * rs.graph_dim * sizeof_score);
 }
 
 // get_multi_batch_sizes (utils.cu:24-138): groups are binned by their batch
@@ -1340,6 +1116,19 @@ int32_t gwamd_internal_poa_lds_add_plan(int32_t max_seq_len, int32_t max_nodes, 
 // field of the planned Dims, then kernel: 1 when the kernel table has a kernel
 // for this plan) and returns their count; negative when planning throws
 // (gwamd_last_error says why) or `cap` is too small.
+// The BatchSize of the plan hooks: the three-argument one with the node
+// capacities replaced (no band width <= sequence size rule, as for the tests' batches)
+static cp::BatchSize hook_batch_size(int32_t max_sequence_size, int32_t max_sequences_per_poa, int32_t band_width,
+                                     int32_t max_nodes_per_window, int32_t max_nodes_per_window_banded)
+{
+    cp::BatchSize bs(max_sequence_size, max_sequences_per_poa, band_width);
+    bs.max_nodes_per_window              = cp::detail::align_up(max_nodes_per_window, 4);
+    bs.max_nodes_per_window_banded       = cp::detail::align_up(max_nodes_per_window_banded, 4);
+    bs.max_matrix_graph_dimension        = bs.max_nodes_per_window;
+    bs.max_matrix_graph_dimension_banded = bs.max_nodes_per_window_banded;
+    return bs;
+}
+
 #define GWAMD_PLAN_FIELDS(F)                                                                                  \
     F(max_nodes) F(max_seqs) F(max_seq_len) F(max_consensus) F(score_stride) F(score_rows) F(aln_cap)        \
     F(band_width) F(want_consensus) F(spoa_accurate) F(lds_kernel) F(lds_bytes) F(lds_ring_off)              \
@@ -1360,13 +1149,8 @@ int32_t gwamd_internal_poa_plan(int32_t max_sequence_size, int32_t max_sequences
                                 int32_t msa, int32_t gap, int32_t mismatch, int32_t match, int64_t* out, int32_t cap)
 {
     return guarded([&]() -> int32_t {
-        // (the three-argument BatchSize with the node capacities replaced: no
-        // band width <= sequence size rule, as for the tests' batches)
-        cp::BatchSize bs(max_sequence_size, max_sequences_per_poa, band_width);
-        bs.max_nodes_per_window              = cp::detail::align_up(max_nodes_per_window, 4);
-        bs.max_nodes_per_window_banded       = cp::detail::align_up(max_nodes_per_window_banded, 4);
-        bs.max_matrix_graph_dimension        = bs.max_nodes_per_window;
-        bs.max_matrix_graph_dimension_banded = bs.max_nodes_per_window_banded;
+        const cp::BatchSize bs = hook_batch_size(max_sequence_size, max_sequences_per_poa, band_width,
+                                                 max_nodes_per_window, max_nodes_per_window_banded);
         int score_bits = 0, size_bits = 0;
         const gwamd::poa::Dims d =
             cp::plan_batch(bs, banded != 0, msa ? cp::OutputType::msa : cp::OutputType::consensus, int16_t(gap),
@@ -1383,6 +1167,70 @@ int32_t gwamd_internal_poa_plan(int32_t max_sequence_size, int32_t max_sequences
     });
 }
 #undef GWAMD_PLAN_FIELDS
+
+// Test hooks (tests/test_poa_capacity.py), without a device.  The capacity and
+// layout the batch constructor plans for these capacities (the arguments of
+// gwamd_internal_poa_plan), `max_mem` bytes and a device of `cus` CUs holding
+// `blocks_per_cu` workgroups of the planned kernel each: the values of
+// gwamd_internal_poa_capacity_fields() in that order (PoaCapacity, the slab
+// offset of every Buffers array or -1, the rest of PoaLayout, device_bytes);
+// returns their count, negative as gwamd_internal_poa_plan does.
+#define GWAMD_SLAB_NAME(name, bytes) #name ","
+#define GWAMD_SLAB_VALUE(name, bytes) lay.name,
+const char* gwamd_internal_poa_capacity_fields(void)
+{
+    return "max_poas,slots,resident,scorebuf_alloc,window_bytes,slot_bytes," GWAMD_POA_SLAB_ARRAYS(GWAMD_SLAB_NAME)
+           "scores,slab_bytes,codes_bytes,seqs_bytes,wts_bytes,len_bytes,off_bytes,win_bytes,order_off,head_off,"
+           "device_bytes";
+}
+
+int32_t gwamd_internal_poa_capacity(int32_t max_sequence_size, int32_t max_sequences_per_poa, int32_t band_width,
+                                    int32_t max_nodes_per_window, int32_t max_nodes_per_window_banded,
+                                    int32_t banded, int32_t msa, int32_t gap, int32_t mismatch, int32_t match,
+                                    int64_t max_mem, int32_t cus, int32_t blocks_per_cu, int64_t* out, int32_t cap)
+{
+    return guarded([&]() -> int32_t {
+        const cp::BatchSize bs = hook_batch_size(max_sequence_size, max_sequences_per_poa, band_width,
+                                                 max_nodes_per_window, max_nodes_per_window_banded);
+        const gwamd::poa::PoaTuning tune = gwamd::poa::read_poa_tuning();
+        int score_bits = 0, size_bits = 0;
+        const gwamd::poa::Dims d =
+            cp::plan_batch(bs, banded != 0, msa ? cp::OutputType::msa : cp::OutputType::consensus, int16_t(gap),
+                           int16_t(mismatch), int16_t(match), tune, score_bits, size_bits);
+        const gwamd::poa::PoaCapacity c =
+            gwamd::poa::plan_capacity({cus, blocks_per_cu}, d, cp::ref_sizes(bs, banded != 0), size_bits / 8,
+                                      score_bits / 8, msa != 0, max_mem, tune.slots);
+        const gwamd::poa::PoaLayout lay =
+            gwamd::poa::plan_layout(d, size_bits / 8, score_bits / 8, msa != 0, c.max_poas, c.slots);
+        const int64_t v[] = {c.max_poas, c.slots, c.resident, c.scorebuf_alloc, c.window_bytes, c.slot_bytes,
+                             GWAMD_POA_SLAB_ARRAYS(GWAMD_SLAB_VALUE) lay.scores, lay.slab_bytes, lay.codes_bytes,
+                             lay.seqs_bytes, lay.wts_bytes, lay.len_bytes, lay.off_bytes, lay.win_bytes,
+                             lay.order_off, lay.head_off, lay.device_bytes()};
+        const int32_t n = int32_t(sizeof(v) / sizeof(v[0]));
+        if (!out || cap < n)
+            return -1;
+        std::copy(v, v + n, out);
+        return n;
+    });
+}
+#undef GWAMD_SLAB_NAME
+#undef GWAMD_SLAB_VALUE
+
+// The queue order of `n` windows (plan_window_order): `windows` holds a
+// (first read, read count) pair per window, `seq_len` the read lengths.
+// Writes the order when there is one (n entries) and returns the WindowOrder kind.
+int32_t gwamd_internal_poa_window_order(const int32_t* windows, const int32_t* seq_len, int32_t n, int32_t cus,
+                                        int32_t slots, int32_t persistent, int32_t* order)
+{
+    return guarded([&]() -> int32_t {
+        static_assert(sizeof(gwamd::poa::WindowDesc) == 2 * sizeof(int32_t), "WindowDesc is two int32");
+        std::vector<int32_t> o;
+        const auto kind = gwamd::poa::plan_window_order(reinterpret_cast<const gwamd::poa::WindowDesc*>(windows),
+                                                        seq_len, n, cus, slots, persistent != 0, o);
+        std::copy(o.begin(), o.end(), order);
+        return int32_t(kind);
+    });
+}
 
 static size_t query_free_memory(uint64_t given)
 {

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "host_common.hpp"
 #include "poa_wave.hpp"
 #include "poa_order.hpp"
 
@@ -1892,11 +1893,14 @@ __global__ void __launch_bounds__(1024) topsort_levels_test_kernel(WinGraph<Size
         *ok = r ? 1 : 0;
 }
 
+using gwamd::host::DevBuf; // the launchers below own their device arrays and events (host_common.hpp)
+
 template <typename SizeT>
 int topsort_levels_test(int n, int n_prev, int n_hint, const uint16_t* in_cnt, const int32_t* in_e,
                         const uint16_t* out_cnt, const int32_t* out_e, int32_t* hint, const int32_t* order_prev,
                         int threads, int scratch, int32_t* sorted, int reps = 0, double* ms = nullptr,
                         uint64_t* prof_out = nullptr)
+try
 {
     const size_t ne = size_t(n) * kMaxEdges;
     std::vector<SizeT> ie(ne), oe(ne), hi(n, SizeT(0));
@@ -1907,23 +1911,6 @@ int topsort_levels_test(int n, int n_prev, int n_hint, const uint16_t* in_cnt, c
     }
     for (int v = 0; hint && v < n; v++)
         hi[v] = SizeT(hint[v]);
-    uint16_t *d_ic = nullptr, *d_oc = nullptr;
-    SizeT *d_ie = nullptr, *d_oe = nullptr, *d_sorted = nullptr, *d_pos = nullptr, *d_hint = nullptr;
-    int* d_ok   = nullptr;
-    uint64_t* d_prof = nullptr;
-    int ok      = 0;
-    auto fin    = [&](int r) {
-        (void)hipFree(d_ic);
-        (void)hipFree(d_oc);
-        (void)hipFree(d_ie);
-        (void)hipFree(d_oe);
-        (void)hipFree(d_sorted);
-        (void)hipFree(d_pos);
-        (void)hipFree(d_hint);
-        (void)hipFree(d_ok);
-        (void)hipFree(d_prof);
-        return r;
-    };
     if (n <= 0 || threads < 64 || threads > 1024 || threads % 64 || scratch < 0 || scratch > 163840 ||
         (n_hint > 0 && !hint) || n_prev < 0 || n_prev > n || (n_prev > 0 && !order_prev))
         return -2;
@@ -1940,68 +1927,72 @@ int topsort_levels_test(int n, int n_prev, int n_hint, const uint16_t* in_cnt, c
             so[q]   = SizeT(v);
         }
     }
-    if (hipMalloc(&d_ic, n * 2) || hipMalloc(&d_oc, n * 2) || hipMalloc(&d_ie, ne * sizeof(SizeT)) ||
-        hipMalloc(&d_oe, ne * sizeof(SizeT)) || hipMalloc(&d_sorted, n * sizeof(SizeT)) ||
-        hipMalloc(&d_pos, n * sizeof(SizeT)) || hipMalloc(&d_hint, n * sizeof(SizeT)) ||
-        hipMalloc(&d_ok, sizeof(int)) || hipMalloc(&d_prof, 10 * sizeof(uint64_t)) ||
-        hipMemset(d_prof, 0, 10 * sizeof(uint64_t)))
-        return fin(-1);
-    if (hipMemcpy(d_ic, in_cnt, n * 2, hipMemcpyHostToDevice) || hipMemcpy(d_oc, out_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie, ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oe, oe.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_hint, hi.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_sorted, so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice))
-        return fin(-1);
+    const gwamd::host::Budget none;
+    DevBuf<uint16_t> d_ic(n, none), d_oc(n, none);
+    DevBuf<SizeT> d_ie(ne, none), d_oe(ne, none), d_sorted(n, none), d_pos(n, none), d_hint(n, none);
+    DevBuf<int> d_ok(1, none);
+    DevBuf<uint64_t> d_prof(10, none);
+    int ok = 0;
+    if (hipMemset(d_prof.data(), 0, 10 * sizeof(uint64_t)))
+        return -1;
+    if (hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oc.data(), out_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ie.data(), ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oe.data(), oe.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_hint.data(), hi.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_sorted.data(), so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice))
+        return -1;
     WinGraph<SizeT> g{};
-    g.in_cnt    = d_ic;
-    g.out_cnt   = d_oc;
-    g.in_e      = d_ie;
-    g.out_e     = d_oe;
-    g.sorted    = d_sorted;
-    g.pos       = d_pos;
+    g.in_cnt    = d_ic.data();
+    g.out_cnt   = d_oc.data();
+    g.in_e      = d_ie.data();
+    g.out_e     = d_oe.data();
+    g.sorted    = d_sorted.data();
+    g.pos       = d_pos.data();
     g.max_nodes = n;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&topsort_levels_test_kernel<SizeT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, scratch))
-        return fin(-1);
+        return -1;
     hipLaunchKernelGGL(topsort_levels_test_kernel<SizeT>, dim3(1), dim3(threads), size_t(scratch), 0, g, n, n_prev,
-                       scratch, d_hint, n_hint, d_ok, nullptr);
-    if (hipGetLastError() || hipDeviceSynchronize() || hipMemcpy(&ok, d_ok, sizeof(int), hipMemcpyDeviceToHost))
-        return fin(-1);
+                       scratch, d_hint.data(), n_hint, d_ok.data(), nullptr);
+    if (hipGetLastError() || hipDeviceSynchronize() ||
+        hipMemcpy(&ok, d_ok.data(), sizeof(int), hipMemcpyDeviceToHost))
+        return -1;
     if (reps > 0)
     {
         // timing mode: the same sort `reps` times (the graph, previous order and
         // hints are inputs only; the outputs are rewritten identically)
-        hipEvent_t e0, e1;
-        if (hipEventCreate(&e0) || hipEventCreate(&e1))
-            return fin(-1);
+        const gwamd::host::OwnedEvent e0, e1;
         (void)hipEventRecord(e0, 0);
         for (int k = 0; k < reps; k++)
         {
-            if (hipMemcpy(d_sorted, so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice))
-                return fin(-1);
+            if (hipMemcpy(d_sorted.data(), so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice))
+                return -1;
             hipLaunchKernelGGL(topsort_levels_test_kernel<SizeT>, dim3(1), dim3(threads), size_t(scratch), 0, g, n,
-                               n_prev, scratch, d_hint, n_hint, d_ok, d_prof);
+                               n_prev, scratch, d_hint.data(), n_hint, d_ok.data(), d_prof.data());
         }
         (void)hipEventRecord(e1, 0);
         float t = 0.f;
         if (hipEventSynchronize(e1) || hipEventElapsedTime(&t, e0, e1))
-            return fin(-1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+            return -1;
         if (ms)
             *ms = double(t) / reps;
-        if (prof_out && hipMemcpy(prof_out, d_prof, 10 * sizeof(uint64_t), hipMemcpyDeviceToHost))
-            return fin(-1);
+        if (prof_out && hipMemcpy(prof_out, d_prof.data(), 10 * sizeof(uint64_t), hipMemcpyDeviceToHost))
+            return -1;
     }
     std::vector<SizeT> s(n);
-    if (hipMemcpy(s.data(), d_sorted, n * sizeof(SizeT), hipMemcpyDeviceToHost) ||
-        hipMemcpy(hi.data(), d_hint, n * sizeof(SizeT), hipMemcpyDeviceToHost))
-        return fin(-1);
+    if (hipMemcpy(s.data(), d_sorted.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost) ||
+        hipMemcpy(hi.data(), d_hint.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost))
+        return -1;
     for (int q = 0; q < n; q++)
         sorted[q] = int32_t(s[q]);
     for (int v = 0; hint && v < n; v++)
         hint[v] = int32_t(hi[v]);
-    return fin(ok);
+    return ok;
+}
+catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
+{
+    return -1;
 }
 
 // Test hook: order_splice_core on one order and one path by one workgroup.
@@ -2036,6 +2027,7 @@ __global__ void __launch_bounds__(1024) order_splice_test_kernel(int16_t* sorted
 // Returns order_splice_core's value, -1 on a HIP error, -2 on bad arguments.
 int order_splice_test(int V, int n, int L, int32_t* sorted, int32_t* pos, const int32_t* curr, const uint8_t* kind,
                       int threads)
+try
 {
     if (V <= 0 || n < V || n > 32767 || L <= 0 || L > 32767 || threads < 64 || threads > 1024 || threads % 64)
         return -2;
@@ -2059,38 +2051,37 @@ int order_splice_test(int V, int n, int L, int32_t* sorted, int32_t* pos, const 
                          size_t(L) + 16;
     if (lds_b > 65536)
         return -2;
-    int16_t *d_so = nullptr, *d_po = nullptr;
-    uint16_t* d_cu = nullptr;
-    uint8_t* d_ki  = nullptr;
-    int* d_out     = nullptr;
-    int out        = -1;
-    auto fin       = [&](int r) {
-        (void)hipFree(d_so);
-        (void)hipFree(d_po);
-        (void)hipFree(d_cu);
-        (void)hipFree(d_ki);
-        (void)hipFree(d_out);
-        return r;
-    };
-    if (hipMalloc(&d_so, n * 2) || hipMalloc(&d_po, n * 2) || hipMalloc(&d_cu, L * 2) || hipMalloc(&d_ki, L) ||
-        hipMalloc(&d_out, sizeof(int)) || hipMemcpy(d_so, so.data(), n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_po, po.data(), n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_cu, cu.data(), L * 2, hipMemcpyHostToDevice) || hipMemcpy(d_ki, kind, L, hipMemcpyHostToDevice))
-        return fin(-1);
+    const gwamd::host::Budget none;
+    DevBuf<int16_t> d_so(n, none), d_po(n, none);
+    DevBuf<uint16_t> d_cu(L, none);
+    DevBuf<uint8_t> d_ki(L, none);
+    DevBuf<int> d_out(1, none);
+    int out = -1;
+    if (hipMemcpy(d_so.data(), so.data(), n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_po.data(), po.data(), n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_cu.data(), cu.data(), L * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ki.data(), kind, L, hipMemcpyHostToDevice))
+        return -1;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&order_splice_test_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)))
-        return fin(-1);
-    hipLaunchKernelGGL(order_splice_test_kernel, dim3(1), dim3(threads), lds_b, 0, d_so, d_po, V, L, d_cu, d_ki, d_out);
-    if (hipGetLastError() || hipDeviceSynchronize() || hipMemcpy(&out, d_out, sizeof(int), hipMemcpyDeviceToHost) ||
-        hipMemcpy(so.data(), d_so, n * 2, hipMemcpyDeviceToHost) ||
-        hipMemcpy(po.data(), d_po, n * 2, hipMemcpyDeviceToHost))
-        return fin(-1);
+        return -1;
+    hipLaunchKernelGGL(order_splice_test_kernel, dim3(1), dim3(threads), lds_b, 0, d_so.data(), d_po.data(), V, L,
+                       d_cu.data(), d_ki.data(), d_out.data());
+    if (hipGetLastError() || hipDeviceSynchronize() ||
+        hipMemcpy(&out, d_out.data(), sizeof(int), hipMemcpyDeviceToHost) ||
+        hipMemcpy(so.data(), d_so.data(), n * 2, hipMemcpyDeviceToHost) ||
+        hipMemcpy(po.data(), d_po.data(), n * 2, hipMemcpyDeviceToHost))
+        return -1;
     for (int q = 0; q < n; q++)
     {
         sorted[q] = so[q];
         pos[q]    = po[q];
     }
-    return fin(out);
+    return out;
+}
+catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
+{
+    return -1;
 }
 
 // Test hook: the row program of one graph and order built by one wave
@@ -2137,6 +2128,7 @@ __global__ void __launch_bounds__(512) row_program_test_kernel(WinGraph<SizeT> g
 int row_program_test(int n, const uint8_t* base, const uint16_t* in_cnt, const uint16_t* out_cnt, const int32_t* in_e,
                      const int32_t* sorted, int xl_cap, int ring_rows, int threads, uint32_t* rec_out,
                      uint16_t* xl_out)
+try
 {
     using SizeT = int16_t;
     if (n <= 0 || n > 8192 || xl_cap < 64 || xl_cap % 8 || threads < 64 || threads > 512 || threads % 64 ||
@@ -2159,48 +2151,40 @@ int row_program_test(int n, const uint8_t* base, const uint16_t* in_cnt, const u
                          4 * size_t(nblk) + 16;
     if (lds_b > 163840)
         return -2;
-    uint8_t* d_base = nullptr;
-    uint16_t *d_ic = nullptr, *d_oc = nullptr, *d_xl = nullptr;
-    SizeT *d_ie = nullptr, *d_so = nullptr, *d_po = nullptr;
-    uint32_t* d_rec = nullptr;
-    auto fin = [&](int r) {
-        (void)hipFree(d_base);
-        (void)hipFree(d_ic);
-        (void)hipFree(d_oc);
-        (void)hipFree(d_xl);
-        (void)hipFree(d_ie);
-        (void)hipFree(d_so);
-        (void)hipFree(d_po);
-        (void)hipFree(d_rec);
-        return r;
-    };
-    if (hipMalloc(&d_base, n) || hipMalloc(&d_ic, n * 2) || hipMalloc(&d_oc, n * 2) ||
-        hipMalloc(&d_xl, 2 * nxl * 2) || hipMalloc(&d_ie, ne * 2) || hipMalloc(&d_so, n * 2) ||
-        hipMalloc(&d_po, n * 2) || hipMalloc(&d_rec, 2 * nrec * 4) ||
-        hipMemcpy(d_base, base, n, hipMemcpyHostToDevice) || hipMemcpy(d_ic, in_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oc, out_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie, ie.data(), ne * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_so, so.data(), n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_po, po.data(), n * 2, hipMemcpyHostToDevice))
-        return fin(-1);
+    const gwamd::host::Budget none;
+    DevBuf<uint8_t> d_base(n, none);
+    DevBuf<uint16_t> d_ic(n, none), d_oc(n, none), d_xl(2 * nxl, none);
+    DevBuf<SizeT> d_ie(ne, none), d_so(n, none), d_po(n, none);
+    DevBuf<uint32_t> d_rec(2 * nrec, none);
+    if (hipMemcpy(d_base.data(), base, n, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oc.data(), out_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ie.data(), ie.data(), ne * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_so.data(), so.data(), n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_po.data(), po.data(), n * 2, hipMemcpyHostToDevice))
+        return -1;
     WinGraph<SizeT> g{};
-    g.base      = d_base;
-    g.in_cnt    = d_ic;
-    g.out_cnt   = d_oc;
-    g.in_e      = d_ie;
-    g.sorted    = d_so;
-    g.pos       = d_po;
+    g.base      = d_base.data();
+    g.in_cnt    = d_ic.data();
+    g.out_cnt   = d_oc.data();
+    g.in_e      = d_ie.data();
+    g.sorted    = d_so.data();
+    g.pos       = d_po.data();
     g.max_nodes = n;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&row_program_test_kernel<SizeT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)))
-        return fin(-1);
-    hipLaunchKernelGGL(row_program_test_kernel<SizeT>, dim3(1), dim3(threads), lds_b, 0, g, n, xl_cap, ring_rows, d_rec,
-                       d_xl);
+        return -1;
+    hipLaunchKernelGGL(row_program_test_kernel<SizeT>, dim3(1), dim3(threads), lds_b, 0, g, n, xl_cap, ring_rows,
+                       d_rec.data(), d_xl.data());
     if (hipGetLastError() || hipDeviceSynchronize() ||
-        hipMemcpy(rec_out, d_rec, 2 * nrec * 4, hipMemcpyDeviceToHost) ||
-        hipMemcpy(xl_out, d_xl, 2 * nxl * 2, hipMemcpyDeviceToHost))
-        return fin(-1);
-    return fin(0);
+        hipMemcpy(rec_out, d_rec.data(), 2 * nrec * 4, hipMemcpyDeviceToHost) ||
+        hipMemcpy(xl_out, d_xl.data(), 2 * nxl * 2, hipMemcpyDeviceToHost))
+        return -1;
+    return 0;
+}
+catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
+{
+    return -1;
 }
 
 // Test hook: the racon DFS sort (topsort_racon_lds) of one graph by one wave,
@@ -2231,6 +2215,7 @@ template <typename SizeT>
 int topsort_racon_test(int n, const uint16_t* in_cnt, const int32_t* in_e, const uint16_t* aln_cnt,
                        const int32_t* aln, int scratch, int v1, int32_t* sorted, int32_t* mpos, int* ncols, int reps,
                        double* ms)
+try
 {
     if (n <= 0 || n > 65535 || scratch < 0 || scratch > 163840 - 64)
         return -2;
@@ -2240,71 +2225,53 @@ int topsort_racon_test(int n, const uint16_t* in_cnt, const int32_t* in_e, const
         ie[i] = SizeT(in_e[i]);
     for (size_t i = 0; i < na; i++)
         al[i] = SizeT(aln[i]);
-    uint16_t *d_ic = nullptr, *d_ac = nullptr;
-    SizeT *d_ie = nullptr, *d_al = nullptr, *d_sorted = nullptr, *d_pos = nullptr, *d_mpos = nullptr;
-    int32_t* d_heads = nullptr;
-    int* d_out       = nullptr;
-    auto fin         = [&](int r) {
-        (void)hipFree(d_ic);
-        (void)hipFree(d_ac);
-        (void)hipFree(d_ie);
-        (void)hipFree(d_al);
-        (void)hipFree(d_sorted);
-        (void)hipFree(d_pos);
-        (void)hipFree(d_mpos);
-        (void)hipFree(d_heads);
-        (void)hipFree(d_out);
-        return r;
-    };
-    if (hipMalloc(&d_ic, n * 2) || hipMalloc(&d_ac, n * 2) || hipMalloc(&d_ie, ne * sizeof(SizeT)) ||
-        hipMalloc(&d_al, na * sizeof(SizeT)) || hipMalloc(&d_sorted, n * sizeof(SizeT)) ||
-        hipMalloc(&d_pos, n * sizeof(SizeT)) || hipMalloc(&d_mpos, n * sizeof(SizeT)) ||
-        hipMalloc(&d_heads, n * sizeof(int32_t)) || hipMalloc(&d_out, 2 * sizeof(int)))
-        return fin(-1);
-    if (hipMemcpy(d_ic, in_cnt, n * 2, hipMemcpyHostToDevice) || hipMemcpy(d_ac, aln_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie, ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_al, al.data(), na * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemset(d_sorted, 0xff, n * sizeof(SizeT)) || hipMemset(d_mpos, 0xff, n * sizeof(SizeT)))
-        return fin(-1);
+    const gwamd::host::Budget none;
+    DevBuf<uint16_t> d_ic(n, none), d_ac(n, none);
+    DevBuf<SizeT> d_ie(ne, none), d_al(na, none), d_sorted(n, none), d_pos(n, none), d_mpos(n, none);
+    DevBuf<int32_t> d_heads(n, none);
+    DevBuf<int> d_out(2, none);
+    if (hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ac.data(), aln_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ie.data(), ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_al.data(), al.data(), na * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemset(d_sorted.data(), 0xff, n * sizeof(SizeT)) || hipMemset(d_mpos.data(), 0xff, n * sizeof(SizeT)))
+        return -1;
     WinGraph<SizeT> g{};
-    g.in_cnt    = d_ic;
-    g.aln_cnt   = d_ac;
-    g.in_e      = d_ie;
-    g.aln       = d_al;
-    g.sorted    = d_sorted;
-    g.pos       = d_pos;
+    g.in_cnt    = d_ic.data();
+    g.aln_cnt   = d_ac.data();
+    g.in_e      = d_ie.data();
+    g.aln       = d_al.data();
+    g.sorted    = d_sorted.data();
+    g.pos       = d_pos.data();
     g.max_nodes = n;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&topsort_racon_test_kernel<SizeT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, scratch))
-        return fin(-1);
-    int32_t* hp = v1 ? nullptr : d_heads;
+        return -1;
+    int32_t* hp = v1 ? nullptr : d_heads.data();
     hipLaunchKernelGGL(topsort_racon_test_kernel<SizeT>, dim3(1), dim3(64), size_t(scratch), 0, g, n, scratch, hp,
-                       d_mpos, d_out);
+                       d_mpos.data(), d_out.data());
     int out[2] = {0, 0};
-    if (hipGetLastError() || hipDeviceSynchronize() || hipMemcpy(out, d_out, sizeof(out), hipMemcpyDeviceToHost))
-        return fin(-1);
+    if (hipGetLastError() || hipDeviceSynchronize() ||
+        hipMemcpy(out, d_out.data(), sizeof(out), hipMemcpyDeviceToHost))
+        return -1;
     if (reps > 0)
     {
-        hipEvent_t e0, e1;
-        if (hipEventCreate(&e0) || hipEventCreate(&e1))
-            return fin(-1);
+        const gwamd::host::OwnedEvent e0, e1;
         (void)hipEventRecord(e0, 0);
         for (int k = 0; k < reps; k++)
             hipLaunchKernelGGL(topsort_racon_test_kernel<SizeT>, dim3(1), dim3(64), size_t(scratch), 0, g, n,
-                               scratch, hp, d_mpos, d_out);
+                               scratch, hp, d_mpos.data(), d_out.data());
         (void)hipEventRecord(e1, 0);
         float t = 0.f;
         if (hipEventSynchronize(e1) || hipEventElapsedTime(&t, e0, e1))
-            return fin(-1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
+            return -1;
         if (ms)
             *ms = double(t) / reps;
     }
     std::vector<SizeT> s(n), mp(n);
-    if (hipMemcpy(s.data(), d_sorted, n * sizeof(SizeT), hipMemcpyDeviceToHost) ||
-        hipMemcpy(mp.data(), d_mpos, n * sizeof(SizeT), hipMemcpyDeviceToHost))
-        return fin(-1);
+    if (hipMemcpy(s.data(), d_sorted.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost) ||
+        hipMemcpy(mp.data(), d_mpos.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost))
+        return -1;
     for (int q = 0; q < n; q++)
     {
         sorted[q] = int32_t(s[q]);
@@ -2313,7 +2280,11 @@ int topsort_racon_test(int n, const uint16_t* in_cnt, const int32_t* in_e, const
     }
     if (ncols)
         *ncols = out[1];
-    return fin(out[0]);
+    return out[0];
+}
+catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
+{
+    return -1;
 }
 
 // Test hook: the consensus of one graph by one wave, as finish_window runs it
@@ -2344,6 +2315,7 @@ int consensus_test(int n, const uint8_t* base, const int32_t* sorted, const int3
                    const int32_t* in_e, const uint16_t* in_w, const uint16_t* out_cnt, const int32_t* out_e,
                    const uint16_t* aln_cnt, const int32_t* aln, const uint16_t* cov, int max_cons, int force_hbm,
                    int scratch, int* status, int* len, uint8_t* cons_out, uint16_t* cov_out)
+try
 {
     if (n <= 0 || n > 32767 || max_cons <= 0 || scratch < 0 || scratch > 163840 - 64)
         return -2;
@@ -2361,77 +2333,60 @@ int consensus_test(int n, const uint8_t* base, const int32_t* sorted, const int3
         so[q] = SizeT(sorted[q]);
         po[q] = SizeT(pos[q]);
     }
-    uint8_t *d_base = nullptr, *d_cons = nullptr;
-    uint16_t *d_ic = nullptr, *d_oc = nullptr, *d_ac = nullptr, *d_cv = nullptr, *d_iw = nullptr, *d_ccov = nullptr;
-    SizeT *d_ie = nullptr, *d_oe = nullptr, *d_al = nullptr, *d_sorted = nullptr, *d_pos = nullptr, *d_cpred = nullptr;
-    int32_t* d_cscore = nullptr;
-    int* d_out        = nullptr;
-    auto fin          = [&](int r) {
-        (void)hipFree(d_base);
-        (void)hipFree(d_cons);
-        (void)hipFree(d_ic);
-        (void)hipFree(d_oc);
-        (void)hipFree(d_ac);
-        (void)hipFree(d_cv);
-        (void)hipFree(d_iw);
-        (void)hipFree(d_ccov);
-        (void)hipFree(d_ie);
-        (void)hipFree(d_oe);
-        (void)hipFree(d_al);
-        (void)hipFree(d_sorted);
-        (void)hipFree(d_pos);
-        (void)hipFree(d_cpred);
-        (void)hipFree(d_cscore);
-        (void)hipFree(d_out);
-        return r;
-    };
     const size_t mc = size_t(max_cons);
-    if (hipMalloc(&d_base, n) || hipMalloc(&d_cons, mc + 1) || hipMalloc(&d_ic, n * 2) || hipMalloc(&d_oc, n * 2) ||
-        hipMalloc(&d_ac, n * 2) || hipMalloc(&d_cv, n * 2) || hipMalloc(&d_iw, ne * 2) ||
-        hipMalloc(&d_ccov, (mc + 1) * 2) || hipMalloc(&d_ie, ne * sizeof(SizeT)) ||
-        hipMalloc(&d_oe, ne * sizeof(SizeT)) || hipMalloc(&d_al, na * sizeof(SizeT)) ||
-        hipMalloc(&d_sorted, n * sizeof(SizeT)) || hipMalloc(&d_pos, n * sizeof(SizeT)) ||
-        hipMalloc(&d_cpred, n * sizeof(SizeT)) || hipMalloc(&d_cscore, n * 4) || hipMalloc(&d_out, 3 * sizeof(int)))
-        return fin(-1);
-    if (hipMemcpy(d_base, base, n, hipMemcpyHostToDevice) || hipMemcpy(d_ic, in_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oc, out_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ac, aln_cnt, n * 2, hipMemcpyHostToDevice) || hipMemcpy(d_cv, cov, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_iw, in_w, ne * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie, ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oe, oe.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_al, al.data(), na * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_sorted, so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_pos, po.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) || hipMemset(d_cons, 0, mc + 1) ||
-        hipMemset(d_ccov, 0, (mc + 1) * 2))
-        return fin(-1);
+    const gwamd::host::Budget none;
+    DevBuf<uint8_t> d_base(n, none), d_cons(mc + 1, none);
+    DevBuf<uint16_t> d_ic(n, none), d_oc(n, none), d_ac(n, none), d_cv(n, none), d_iw(ne, none), d_ccov(mc + 1, none);
+    DevBuf<SizeT> d_ie(ne, none), d_oe(ne, none), d_al(na, none), d_sorted(n, none), d_pos(n, none), d_cpred(n, none);
+    DevBuf<int32_t> d_cscore(n, none);
+    DevBuf<int> d_out(3, none);
+    if (hipMemcpy(d_base.data(), base, n, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oc.data(), out_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ac.data(), aln_cnt, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_cv.data(), cov, n * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_iw.data(), in_w, ne * 2, hipMemcpyHostToDevice) ||
+        hipMemcpy(d_ie.data(), ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_oe.data(), oe.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_al.data(), al.data(), na * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_sorted.data(), so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemcpy(d_pos.data(), po.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
+        hipMemset(d_cons.data(), 0, mc + 1) ||
+        hipMemset(d_ccov.data(), 0, (mc + 1) * 2))
+        return -1;
     WinGraph<SizeT> g{};
-    g.base      = d_base;
-    g.in_cnt    = d_ic;
-    g.out_cnt   = d_oc;
-    g.aln_cnt   = d_ac;
-    g.cov       = d_cv;
-    g.in_w      = d_iw;
-    g.in_e      = d_ie;
-    g.out_e     = d_oe;
-    g.aln       = d_al;
-    g.sorted    = d_sorted;
-    g.pos       = d_pos;
+    g.base      = d_base.data();
+    g.in_cnt    = d_ic.data();
+    g.out_cnt   = d_oc.data();
+    g.aln_cnt   = d_ac.data();
+    g.cov       = d_cv.data();
+    g.in_w      = d_iw.data();
+    g.in_e      = d_ie.data();
+    g.out_e     = d_oe.data();
+    g.aln       = d_al.data();
+    g.sorted    = d_sorted.data();
+    g.pos       = d_pos.data();
     g.max_nodes = n;
     // (at least one LDS word, so the kernel's dynamic array exists)
     const int lds_bytes = std::max(scratch, 16);
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&consensus_test_kernel<SizeT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes))
-        return fin(-1);
+        return -1;
     hipLaunchKernelGGL(consensus_test_kernel<SizeT>, dim3(1), dim3(64), size_t(lds_bytes), 0, g, n, scratch, force_hbm,
-                       d_cscore, d_cpred, d_cons, d_ccov, max_cons, d_out);
+                       d_cscore.data(), d_cpred.data(), d_cons.data(), d_ccov.data(), max_cons, d_out.data());
     int out[3] = {0, 0, 0};
-    if (hipGetLastError() || hipDeviceSynchronize() || hipMemcpy(out, d_out, sizeof(out), hipMemcpyDeviceToHost) ||
-        hipMemcpy(cons_out, d_cons, mc, hipMemcpyDeviceToHost) ||
-        hipMemcpy(cov_out, d_ccov, mc * 2, hipMemcpyDeviceToHost))
-        return fin(-1);
+    if (hipGetLastError() || hipDeviceSynchronize() ||
+        hipMemcpy(out, d_out.data(), sizeof(out), hipMemcpyDeviceToHost) ||
+        hipMemcpy(cons_out, d_cons.data(), mc, hipMemcpyDeviceToHost) ||
+        hipMemcpy(cov_out, d_ccov.data(), mc * 2, hipMemcpyDeviceToHost))
+        return -1;
     *status = out[0];
     *len    = out[1];
-    return fin(out[2]);
+    return out[2];
+}
+catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
+{
+    return -1;
 }
 
 } // namespace poa

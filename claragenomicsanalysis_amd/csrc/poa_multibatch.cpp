@@ -4,7 +4,7 @@
 // Reference: cudapoa/benchmarks/multi_batch.hpp:30-215.  One host thread per
 // batch, each batch on its own non-blocking HIP stream; windows are handed out
 // under one mutex in window order; results are stored by window index.  The
-// batches' kernels use a persistent grid (poa_batch.cpp plan_launch_order), so
+// batches' kernels use a persistent grid (poa_plan.cpp plan_window_order), so
 // a kernel queued on another stream fills the CUs that the running kernel's
 // last windows leave idle.
 #include <claraparabricks/genomeworks/cudapoa/multi_batch.hpp>
@@ -21,6 +21,7 @@
 #include <exception>
 #include <mutex>
 #include <numeric>
+#include <optional>
 #include <stdexcept>
 #include <thread>
 
@@ -31,7 +32,14 @@ namespace genomeworks
 namespace cudapoa
 {
 
+using gwamd::host::OwnedEvent;
+using gwamd::host::OwnedStream;
 using gwamd::host::ScopedDevice;
+
+struct MultiBatch::Streams
+{
+    std::vector<OwnedStream> v;
+};
 
 MultiBatch::MultiBatch(int32_t num_batches, const std::string& filename, int32_t total_windows)
 {
@@ -72,22 +80,21 @@ void MultiBatch::create(int32_t num_batches, int32_t device_id, size_t mem_per_b
         GWAMD_HIP_CHECK(hipMemGetInfo(&free_mem, &total));
         mem_per_batch = size_t(0.9 * double(free_mem) / num_batches);
     }
+    streams_.reset(new Streams);
+    streams_->v.reserve(size_t(num_batches));
     for (int32_t b = 0; b < num_batches; b++)
     {
-        hipStream_t s = nullptr;
-        GWAMD_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        streams_.push_back(s);
-        batches_.emplace_back(create_batch(device_id_, s, mem_per_batch, output_mask, batch_size, gap_score,
-                                           mismatch_score, match_score, banded));
+        streams_->v.emplace_back();
+        batches_.emplace_back(create_batch(device_id_, streams_->v.back(), mem_per_batch, output_mask, batch_size,
+                                           gap_score, mismatch_score, match_score, banded));
     }
 }
 
+// the batches go first, then (as members) their streams, on the batches' device
 MultiBatch::~MultiBatch()
 {
     batches_.clear();
     (void)hipSetDevice(device_id_);
-    for (void* s : streams_)
-        (void)hipStreamDestroy(static_cast<hipStream_t>(s));
 }
 
 void MultiBatch::set_groups(const std::vector<Group>& groups) { groups_ = groups; }
@@ -124,38 +131,31 @@ void MultiBatch::process_batches()
     // Launch timing (set_launch_timing): one start/stop event pair per batch
     // and a reference event, so every launch becomes an interval on one clock.
     const size_t nb = batches_.size();
-    std::vector<hipEvent_t> ev_start(nb, nullptr), ev_stop(nb, nullptr);
-    hipEvent_t ev_ref = nullptr;
-    struct EventGuard
+    std::vector<OwnedEvent> ev_start, ev_stop;
+    std::optional<OwnedEvent> ev_ref;
+    struct EventGuard // the batches must not keep events that end with this call
     {
-        std::vector<hipEvent_t>* a;
-        std::vector<hipEvent_t>* b;
-        hipEvent_t* r;
         std::vector<std::unique_ptr<Batch>>* batches;
         ~EventGuard()
         {
             for (auto& bt : *batches)
                 detail::set_launch_events(bt.get(), nullptr, nullptr);
-            for (auto* v : {a, b})
-                for (hipEvent_t e : *v)
-                    if (e)
-                        (void)hipEventDestroy(e);
-            if (*r)
-                (void)hipEventDestroy(*r);
         }
-    } guard_events{&ev_start, &ev_stop, &ev_ref, &batches_};
+    } guard_events{&batches_};
     if (time_launches_)
     {
         ScopedDevice dev(device_id_);
+        ev_start.reserve(nb);
+        ev_stop.reserve(nb);
         for (size_t b = 0; b < nb; b++)
         {
-            GWAMD_HIP_CHECK(hipEventCreate(&ev_start[b]));
-            GWAMD_HIP_CHECK(hipEventCreate(&ev_stop[b]));
+            ev_start.emplace_back();
+            ev_stop.emplace_back();
             detail::set_launch_events(batches_[b].get(), ev_start[b], ev_stop[b]);
         }
-        GWAMD_HIP_CHECK(hipEventCreate(&ev_ref));
-        GWAMD_HIP_CHECK(hipEventRecord(ev_ref, static_cast<hipStream_t>(streams_[0])));
-        GWAMD_HIP_CHECK(hipEventSynchronize(ev_ref));
+        ev_ref.emplace();
+        GWAMD_HIP_CHECK(hipEventRecord(*ev_ref, streams_->v[0]));
+        GWAMD_HIP_CHECK(hipEventSynchronize(*ev_ref));
     }
     std::mutex mutex_launches;
 
@@ -233,8 +233,8 @@ void MultiBatch::process_batches()
             if (time_launches_)
             {
                 LaunchRecord rec;
-                GWAMD_HIP_CHECK(hipEventElapsedTime(&rec.start_ms, ev_ref, ev_start[b]));
-                GWAMD_HIP_CHECK(hipEventElapsedTime(&rec.stop_ms, ev_ref, ev_stop[b]));
+                GWAMD_HIP_CHECK(hipEventElapsedTime(&rec.start_ms, *ev_ref, ev_start[b]));
+                GWAMD_HIP_CHECK(hipEventElapsedTime(&rec.stop_ms, *ev_ref, ev_stop[b]));
                 rec.cells   = detail::last_launch_cells(batch);
                 rec.windows = n;
                 rec.batch   = int32_t(b);

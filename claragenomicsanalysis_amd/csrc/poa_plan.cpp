@@ -1,13 +1,19 @@
 // The POA kernel plan: which kernel a batch of given capacities runs and the
 // layout of its LDS image and HBM side buffers, as a function of the
-// capacities and the tuning switches alone.  No HIP in here, so the plan can
-// be examined (and sanitized) on the host: gwamd_internal_poa_plan.
+// capacities and the tuning switches alone; then how many windows and scratch
+// slots the batch gets for its memory (plan_capacity), where every device
+// array lies (plan_layout) and the order its windows are queued in
+// (plan_window_order).  No HIP in here, so the plan can be examined (and
+// sanitized) on the host: gwamd_internal_poa_plan, gwamd_internal_poa_capacity,
+// gwamd_internal_poa_window_order.
 #include "poa_plan.hpp"
 
 #include <algorithm>
 #include <cstdint>
 #include <iterator>
 #include <stdexcept>
+#include <string>
+#include <utility>
 
 namespace gwamd
 {
@@ -239,6 +245,202 @@ void plan_kernels(Dims& dims, bool banded, const Scores& sc, int score_bits, int
         plan_lds_layout(dims, banded, size_bits, score_bits, tune);
     plan_band_kernel(dims, banded, sc.gap, score_bits, tune);
     dims.diag = tune.diag;
+}
+
+namespace
+{
+
+inline int64_t align8(int64_t v) { return (v + 7) & ~int64_t(7); }
+inline int64_t align16(int64_t v) { return (v + 15) & ~int64_t(15); }
+
+// Graph, inputs and outputs of one window: an estimate for the capacity, made
+// before the layout existed and kept as it is because max_poas follows from it
+// (it has a flat 32 B where the slab has the phase, cells, final_nodes and
+// order_stats arrays).
+int64_t window_bytes(const Dims& d, int sz, bool msa)
+{
+    const int64_t mn = d.max_nodes, E = kMaxEdges, S = d.max_seqs;
+    int64_t b        = 0;
+    b += align8(mn) + 4 * align8(mn * 2) + align8(mn * E * 2);   // base, counts, coverage, in_w
+    b += 3 * align8(mn * E * sz) + 2 * align8(mn * sz);           // in_e, out_e, aln, sorted, pos
+    b += align8(d.max_consensus) + align8(int64_t(d.max_consensus) * 2) + 32; // outputs
+    b += int64_t(S) * d.max_seq_len * 2 + S * 12;                 // inputs
+    if (msa)
+        b += align8(mn * E * S * 2) + align8(mn * E * 2) + align8(S * sz) + align8(S * int64_t(d.max_consensus));
+    return b;
+}
+
+// Forward-pass / traceback / consensus scratch of one slot.
+int64_t slot_bytes(const Dims& d, int sz, int sbytes)
+{
+    const int64_t mn = d.max_nodes;
+    int64_t b        = 0;
+    b += 2 * align8(int64_t(d.aln_cap) * sz);                 // ag, ar
+    b += int64_t(d.score_rows) * d.score_stride * sbytes;     // scores (LDS kernel: spill rows)
+    if (d.lds_kernel)
+        b += d.aux_stride; // traceback codes, row program, predecessor lists, carries
+    b += align8(mn * 4) + align8(mn * 4 * sz);                // cscore, cpred
+    return b;
+}
+
+// Non-score bytes of the reference slab for P windows
+// (allocate_block.hpp:121-285, each buffer aligned to 8 B).
+int64_t reference_fixed_slab(const RefSizes& rs, int64_t P, int sz, bool msa, bool cons)
+{
+    const int64_t S = rs.seqs, E = kMaxEdges, nodes = rs.nodes, gdim = rs.graph_dim;
+    int64_t o       = 0;
+    o += align8(P * rs.consensus);
+    o += cons ? align8(P * rs.consensus * 2) : 0;
+    o += msa ? align8(P * rs.consensus * S) : 0;
+    o += 2 * align8(P * S * rs.seq_len);
+    o += align8(P * S * sz) + align8(P * 32);
+    o += msa ? align8(P * S * sz) : 0;
+    o += 2 * align8(P * gdim * sz); // alignment graph / read
+    o += align8(P * nodes) + align8(P * nodes * E * sz) + align8(P * nodes * 2);
+    o += align8(P * nodes * E * sz) + align8(P * nodes * 2);
+    o += align8(P * nodes * E * sz) + align8(P * nodes * 2);
+    o += 2 * align8(P * nodes * E * 2);
+    o += 2 * align8(P * nodes * sz) + align8(P * nodes * 2);
+    o += cons ? align8(P * nodes * 4) + align8(P * nodes * sz) : 0;
+    o += 2 * align8(P * nodes) + align8(P * nodes * sz) + align8(P * nodes * 2);
+    o += msa ? align8(P * nodes * E * S * 2) + align8(P * nodes * E * 2) + align8(P * nodes * sz) : 0;
+    return o;
+}
+
+} // namespace
+
+// sizes of SizeT/ScoreT are the chosen types
+int64_t reference_device_bytes_per_poa(const RefSizes& rs, bool msa, int size_bytes)
+{
+    const int64_t gdim = rs.graph_dim, nodes = rs.nodes;
+    const int64_t E = kMaxEdges, A = kMaxAlignments, S = rs.seqs;
+    int64_t b = 0;
+    b += rs.consensus;                                            // consensus
+    b += !msa ? rs.consensus * 2 : 0;                             // coverage
+    b += msa ? rs.consensus * S : 0;                              // msa
+    b += S * rs.seq_len * 2;                                      // sequences + weights
+    b += S * size_bytes;                                          // sequence lengths
+    b += 32;                                                      // WindowDetails
+    b += msa ? S * size_bytes : 0;                                // sequence_begin_nodes_ids
+    b += nodes;                                                   // nodes
+    b += nodes * A * size_bytes + nodes * 2;                      // node_alignments (+count)
+    b += nodes * E * size_bytes + nodes * 2;                      // incoming edges (+count)
+    b += nodes * E * size_bytes + nodes * 2;                      // outgoing edges (+count)
+    b += nodes * E * 2 * 2;                                       // in/out edge weights
+    b += nodes * size_bytes * 2 + nodes * 2;                      // sorted, node map, local count
+    b += !msa ? nodes * 4 + nodes * size_bytes : 0;               // consensus scores / predecessors
+    b += nodes + nodes + nodes * size_bytes;                      // marks, check, nodes_to_visit
+    b += nodes * 2;                                               // node coverage
+    b += msa ? nodes * E * S * 2 + nodes * E * 2 + nodes * size_bytes : 0; // edge coverage, msa pos
+    b += gdim * size_bytes * 2;                                   // alignment graph/read
+    return b;
+}
+
+PoaCapacity plan_capacity(const PoaDeviceFacts& facts, const Dims& dims, const RefSizes& rs, int size_bytes,
+                          int score_bytes, bool msa, int64_t max_mem, int tune_slots)
+{
+    // BatchBlock ctor (allocate_block.hpp:51-91)
+    const int64_t per_poa = reference_device_bytes_per_poa(rs, msa, size_bytes);
+    if (max_mem < per_poa)
+    {
+        throw std::runtime_error(std::string("Require at least ") + std::to_string(per_poa) +
+                                 " bytes of device memory per CUDAPOA batch to process correctly.");
+    }
+    const int64_t ref_score_matrix = rs.seq_dim * rs.graph_dim * score_bytes;
+    int64_t max_poas               = max_mem / (per_poa + ref_score_matrix);
+
+    // this build's footprint: graph + inputs + outputs per window, and the
+    // forward/traceback scratch per slot.  The LDS and banded kernels run
+    // a persistent grid of as many workgroups as are resident at once, so
+    // they need only that many slots however many windows the batch holds.
+    PoaCapacity c;
+    c.window_bytes   = window_bytes(dims, size_bytes, msa);
+    c.slot_bytes     = slot_bytes(dims, size_bytes, score_bytes);
+    int64_t own_cap  = max_mem / (c.window_bytes + c.slot_bytes); // a slot per window
+    int64_t resident = 0;
+    if (dims.lds_kernel)
+    {
+        resident = int64_t(facts.blocks_per_cu) * facts.cus;
+        if (tune_slots > 0) // diagnostic: a smaller persistent grid
+            resident = std::min<int64_t>(resident > 0 ? resident : INT32_MAX, tune_slots);
+        if (resident > 0 && own_cap > resident)
+            own_cap = std::max(own_cap, (max_mem - resident * c.slot_bytes) / c.window_bytes);
+    }
+    max_poas = std::min<int64_t>(max_poas, own_cap);
+    if (max_poas < 1)
+        throw std::runtime_error("Require more device memory per CUDAPOA batch to process correctly.");
+    c.max_poas = int32_t(std::min<int64_t>(max_poas, INT32_MAX));
+    c.slots    = resident > 0 ? int32_t(std::min<int64_t>(resident, c.max_poas)) : c.max_poas;
+    c.resident = resident > 0 ? int32_t(resident) : 0;
+
+    // score budget (allocate_block.hpp:196-201): what the reference's slab
+    // leaves for the variable-width score matrices
+    c.scorebuf_alloc =
+        std::max<int64_t>(0, max_mem - reference_fixed_slab(rs, c.max_poas, size_bytes, msa, dims.want_consensus != 0));
+    return c;
+}
+
+PoaLayout plan_layout(const Dims& d, int sz, int sbytes, bool msa, int32_t max_poas, int32_t slots)
+{
+    const int64_t P = max_poas, Z = slots, mn = d.max_nodes, E = kMaxEdges, S = d.max_seqs;
+    PoaLayout l;
+    int64_t off = 0;
+#define GWAMD_F(name, bytes)                                                                                  \
+    if (const int64_t b = align8(bytes))                                                                      \
+        l.name = off, off += b;
+    GWAMD_POA_SLAB_ARRAYS(GWAMD_F)
+#undef GWAMD_F
+    l.scores      = (off + 255) & ~int64_t(255);
+    l.slab_bytes  = l.scores + Z * int64_t(d.score_rows) * d.score_stride * sbytes;
+    l.codes_bytes = d.lds_kernel ? Z * d.aux_stride : 0;
+    // inputs (allocate_block.hpp:84: max_poas * max_seqs * max_seq bytes)
+    l.seqs_bytes = l.wts_bytes = P * S * d.max_seq_len + 64;
+    l.len_bytes  = P * S * 4 + 8;
+    l.off_bytes  = P * S * 8 + 8;
+    // head_off + 4 <= P * 12 + 34 (two round-ups of at most 15), inside P * 12 + 64
+    l.order_off = align16(P * int64_t(sizeof(WindowDesc)));
+    l.head_off  = align16(l.order_off + P * 4);
+    l.win_bytes = P * int64_t(sizeof(WindowDesc) + 4) + 64;
+    return l;
+}
+
+WindowOrder plan_window_order(const WindowDesc* wd, const int32_t* ln, int n, int cus, int slots,
+                              bool persistent_kernel, std::vector<int32_t>& order)
+{
+    const bool persistent = persistent_kernel && n > slots;
+    if (!persistent && (cus <= 0 || n <= cus))
+        return kNoOrder;
+    std::vector<std::pair<int64_t, int32_t>> cost(static_cast<size_t>(n));
+    for (int w = 0; w < n; w++)
+    {
+        int64_t sum = 0, mx = 0;
+        for (int s = 0; s < wd[w].num_seqs; s++)
+        {
+            const int64_t l = ln[wd[w].first_seq + s];
+            mx              = std::max(mx, l);
+            if (s > 0)
+                sum += l;
+        }
+        cost[size_t(w)] = {-sum * mx, w}; // heaviest first, ties by window
+    }
+    std::sort(cost.begin(), cost.end());
+    order.resize(size_t(n));
+    const int m = persistent ? slots : n; // positions placed statically
+    for (int k = 0; k < m; k++)
+    {
+        if (cus <= 0)
+        {
+            order[size_t(k)] = cost[size_t(k)].second;
+            continue;
+        }
+        const int t = k / cus, pos = k % cus;
+        const int r = std::min(cus, m - t * cus); // workgroups in this round
+        const int j = (t % 2 == 0) ? pos : r - 1 - pos;
+        order[size_t(t * cus + j)] = cost[size_t(k)].second;
+    }
+    for (int k = m; k < n; k++)
+        order[size_t(k)] = cost[size_t(k)].second;
+    return persistent ? kOrderAndHead : kOrder;
 }
 
 } // namespace poa

@@ -107,7 +107,8 @@ private:
                 bool banded);
 
     int32_t device_id_ = 0;
-    std::vector<void*> streams_; // hipStream_t, one per batch
+    struct Streams;                    // one owned non-blocking stream per batch (poa_multibatch.cpp)
+    std::unique_ptr<Streams> streams_; // declared before the batches: they are destroyed first
     std::vector<std::unique_ptr<Batch>> batches_;
     std::vector<std::vector<std::string>> owned_windows_; // reference constructor only
     std::vector<Group> groups_;

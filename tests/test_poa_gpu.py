@@ -522,7 +522,7 @@ def test_serialize_graph_case(banded):
                                                             max_consensus=2048, max_seqs=500).msa)
 
 
-# Persistent grid and launch order (poa_batch.cpp plan_launch_order): with
+# Persistent grid and launch order (poa_plan.cpp plan_window_order): with
 # GWAMD_POA_SLOTS the batch gets fewer scratch slots than windows, so every
 # workgroup dequeues several windows (heaviest first) and reuses its slot's
 # scratch; GWAMD_LAUNCH_ORDER_CUS plans the snake order for a 2-CU device, so
@@ -770,3 +770,39 @@ def test_full_int32_persistent_grid(spoa, monkeypatch):
             assert (st[i], cons[i], cov[i]) == (r.status, r.consensus, r.coverage), (rep, i)
             expect = {(src, v): wt for v, ins in enumerate(r.graph["in"]) for (src, wt) in ins}
             assert {(u, v): graphs[i].weight(u, v) for (u, v) in graphs[i].edges} == expect, (rep, i)
+
+
+@pytest.mark.parametrize("case", ["full", "banded", "msa", "int32", "v1", "slots3"])
+def test_capacity_is_what_the_batch_built(case, monkeypatch):
+    # the capacity and layout the CPU tests pin (tests/test_poa_capacity.py),
+    # asked with this device's facts, are the ones the constructor acted on
+    import torch
+    from test_poa_capacity import ENV_NAMES, _args, _lib, capacity
+    for k in ENV_NAMES:  # no switches but the case's (restored after the test)
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.delenv("GWAMD_LAUNCH_ORDER_CUS", raising=False)
+    env = {"GWAMD_DIAG": "1"}
+    if case == "v1":
+        env["GWAMD_POA_KERNEL"] = "v1"
+    if case == "slots3":
+        env["GWAMD_POA_SLOTS"] = "3"
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    ms = 1600 if case == "int32" else 256
+    banded, msa, mem = case == "banded", case == "msa", 1 << 30
+    b = CudaPoaBatch(8, ms, mem, output_type="msa" if msa else "consensus", cuda_banded_alignment=banded,
+                     alignment_band_width=128 if banded else 256)
+    assert b.get_types()[0] == (32 if case == "int32" else 16)
+    device_bytes, max_poas = b.get_capacity()
+    slots, resident = b.get_grid()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if case == "v1":
+        assert resident == 0 and b.kernel_variant() == 1
+    elif case == "slots3":
+        assert (slots, resident) == (3, 3)
+    else:
+        assert resident > 0 and resident % cus == 0
+    p = capacity(_lib(), env, _args(ms, banded=int(banded), bw=128 if banded else 256, msa=int(msa), reads=8) +
+                 [mem, cus, resident // cus])
+    assert "error" not in p, p
+    assert (max_poas, slots, resident, device_bytes) == (p["max_poas"], p["slots"], p["resident"], p["device_bytes"])

@@ -246,8 +246,10 @@ class CudaAlignerBatch:
         qp, ql, tp, tl = C.c_void_p(), C.c_int32(), C.c_void_p(), C.c_int32()
         _check(self._lib.gwamd_aligner_get_sequences(self._handle, i, C.byref(qp), C.byref(ql), C.byref(tp),
                                                      C.byref(tl)))
-        q = C.string_at(qp, ql.value).decode() if ql.value else ""
-        t = C.string_at(tp, tl.value).decode() if tl.value else ""
+        # latin-1: one character per stored byte, as the states count them, and
+        # lossless for any byte (sequences may hold non-ASCII bytes); ASCII as before
+        q = C.string_at(qp, ql.value).decode("latin-1") if ql.value else ""
+        t = C.string_at(tp, tl.value).decode("latin-1") if tl.value else ""
         return q, t
 
     def reset(self):

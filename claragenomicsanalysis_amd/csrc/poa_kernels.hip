@@ -20,9 +20,9 @@
 #include <type_traits>
 #include <utility>
 
-#include "host_common.hpp"
 #include "poa_wave.hpp"
 #include "poa_order.hpp"
+#include "poa_rowprog.hpp" // the LDS kernel's row program (build_row_program)
 
 namespace gwamd
 {
@@ -190,331 +190,8 @@ __global__ void __launch_bounds__(kWave) poa_window_kernel(Buffers b, Dims d, Sc
 //    128x128 tiles staged in LDS;
 //  * the per-read row program (base, predecessor rows, sink/spill flags) is
 //    built in LDS once per read, so the row loop touches HBM only for the
-//    code stores.
+//    code stores (poa_rowprog.hpp).
 // ===========================================================================
-
-constexpr uint32_t kRecEscape = 63; // np field: predecessor rows read from the graph in HBM
-
-
-struct RowProg
-{
-    const uint32_t* rec;
-    const uint16_t* xl;
-    int ring_mask;
-};
-
-// k-th predecessor row of row r (0 = the virtual row 0)
-template <typename SizeT>
-__device__ __forceinline__ int prog_pred(const RowProg& P, WinGraph<SizeT> g, int r, uint32_t rec, int k)
-{
-    g = as_global(g);
-    const int np = (rec >> 8) & 63;
-    if (np == 0)
-        return 0; // source node: the virtual row 0
-    if (np == 1)
-        return r - int(rec >> 16);
-    if (np == int(kRecEscape))
-    {
-        uint32_t t = uint32_t(pred_row(g, int(g.sorted[r - 1]), k));
-        asm volatile("" : "+v"(t)); // wait here, not where the paths join
-        return int(t);
-    }
-    return int(P.xl[(rec >> 16) + k]);
-}
-
-template <typename SizeT>
-__device__ __forceinline__ int prog_np(WinGraph<SizeT> g, int r, uint32_t rec)
-{
-    g = as_global(g);
-    const int np = (rec >> 8) & 63;
-    return np == int(kRecEscape) ? int(g.in_cnt[int(g.sorted[r - 1])]) : np;
-}
-
-// Row program for rows 1..V (built after every topological sort).  The graph
-// lives in HBM, so the loads are batched for memory-level parallelism: each
-// lane takes kRP rows per pass and every dependent level (node, its counts,
-// its first two predecessors' node ids, their rows) is issued for all of them
-// before the next level waits.  A row spills when a successor reads it from
-// ring_rows or more rows later; that is marked from the successor's side
-// (row s, predecessor row p: s - p >= ring_rows) into byte flags in `flags`
-// (V + 2 bytes of free LDS), so no out-edge lists are read.
-// Sinks: the rows of the first kSinkCap sinks are left in sinks[0..), their
-// number (all of them, capped at 65535) in sinks[kSinkCap], and every listed
-// sink row spills, so that E(sink, L) can be read back after the forward pass
-// (the tie check of a spliced row order, poa_order.hpp).
-// The base of forward-pass row r from its record (build_row_program): bits
-// 0-6, or the graph's own byte when they hold 0x7f, which stands for 0x7f and
-// for every byte >= 0x80 (the reference compares whole bytes, and bit 7 of
-// the record is the general-path flag)
-template <typename SizeT>
-__device__ __forceinline__ int row_base(WinGraph<SizeT> g, uint32_t rec, int r)
-{
-    const int b = int(rec & 0x7fu);
-    return b == 0x7f ? uniform(int(g.base[g.sorted[r - 1]])) : b;
-}
-
-constexpr int kRowProgRP  = 4;                 // rows per lane and block
-constexpr int kRowProgBlk = kRowProgRP * kWave;  // rows per block: one wave's pass
-
-// One block of the row program: rows r0 .. r0 + kRowProgBlk - 1 (up to V) by
-// one wave.  xbase / nsink: the predecessor-list entries and the sinks of the
-// rows before r0 on entry, of the rows through this block on return.
-template <typename SizeT>
-__device__ __forceinline__ void row_program_block(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl, int xl_cap,
-                                                  int ring_rows, int lane, GWAMD_LDS uint8_t* flags,
-                                                  GWAMD_LDS uint16_t* sinks, int r0, int& xbase, int& nsink)
-{
-    constexpr int kRP = kRowProgRP;
-    {
-        int node[kRP], np[kRP], base[kRP], oc[kRP], e0[kRP], e1[kRP], p0[kRP], p1[kRP];
-#pragma unroll
-        for (int u = 0; u < kRP; u++)
-        {
-            const int r = min(r0 + u * kWave + lane, V);
-            node[u]     = int(g.sorted[r - 1]);
-        }
-#pragma unroll
-        for (int u = 0; u < kRP; u++)
-        {
-            np[u]   = int(g.in_cnt[node[u]]);
-            base[u] = int(g.base[node[u]]);
-            oc[u]   = int(g.out_cnt[node[u]]);
-            e0[u]   = int(g.in_e[node[u] * kMaxEdges]);
-            e1[u]   = int(g.in_e[node[u] * kMaxEdges + 1]);
-        }
-#pragma unroll
-        for (int u = 0; u < kRP; u++)
-        {
-            // slots beyond in_cnt hold stale ids: clamp to a valid node
-            p0[u] = int(g.pos[np[u] >= 1 ? e0[u] : 0]) + 1;
-            p1[u] = int(g.pos[np[u] >= 2 ? e1[u] : 0]) + 1;
-        }
-#pragma unroll
-        for (int u = 0; u < kRP; u++)
-        {
-            const int r      = r0 + u * kWave + lane;
-            const bool valid = r <= V;
-            const int n      = valid ? np[u] : 0;
-            int total        = 0;
-            const int excl   = wave_excl_sum(n >= 2 ? n : 0, lane, total);
-            {
-                const bool sink   = valid && oc[u] == 0;
-                const uint64_t sm = __builtin_amdgcn_ballot_w64(sink);
-                const int si      = nsink + __popcll(sm & ((1ull << lane) - 1));
-                if (sink && si < kSinkCap)
-                {
-                    sinks[si] = uint16_t(r);
-                    flags[r]  = 1;
-                }
-                nsink += __popcll(sm);
-            }
-            if (valid)
-            {
-                // bits 0-6: the base, 0x7f standing for 0x7f and for every
-                // byte >= 0x80 (the forward passes read such rows' base back
-                // from the graph, row_base); bit 7: the forward pass must take
-                // its general path (nw_forward_lds_v2): a source, a
-                // predecessor beyond the ring, an escaped list or a base
-                // other than ACGT
-                const uint32_t ub = uint32_t(base[u]);
-                uint32_t v        = (ub >= 0x7fu ? 0x7fu : ub) | (uint32_t(oc[u] == 0 ? 1 : 0) << 14);
-                bool slow = n == 0 || !((ub & 0xc0u) == 0x40u && ((0x10008aull >> (ub & 0x3fu)) & 1u));
-                if (n == 1)
-                {
-                    v |= (1u << 8) | (uint32_t(r - p0[u]) << 16);
-                    if (r - p0[u] >= ring_rows)
-                    {
-                        flags[p0[u]] = 1;
-                        slow         = true;
-                    }
-                }
-                else if (n >= 2)
-                {
-                    const int off  = xbase + excl;
-                    const bool fit = off + n <= xl_cap;
-                    for (int k = 0; k < n; k++)
-                    {
-                        const int pk = k == 0 ? p0[u] : (k == 1 ? p1[u] : pred_row(g, node[u], k));
-                        if (fit)
-                            xl[off + k] = uint16_t(pk);
-                        if (r - pk >= ring_rows)
-                        {
-                            flags[pk] = 1;
-                            slow      = true;
-                        }
-                    }
-                    v |= fit ? (uint32_t(n) << 8) | (uint32_t(off) << 16) : (kRecEscape << 8);
-                    slow = slow || !fit;
-                }
-                rec[r] = v | (slow ? 0x80u : 0u);
-            }
-            xbase += total;
-        }
-    }
-}
-
-// The row program by one wave, block after block with a running list offset:
-// the form the records, lists and marks are defined by.  Before a forward
-// pass the kernel builds it on every wave (build_row_program below, byte for
-// byte the same: tests/test_poa_order_splice.py compares the two); this one
-// rebuilds it on the two rare paths that lose it to a sort's scratch (a sink
-// tie that takes a Kahn sort, more sinks than the tie check holds).
-template <typename SizeT>
-__device__ void build_row_program_wave0(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl, int xl_cap,
-                                        int ring_rows, int lane, GWAMD_LDS uint8_t* flags,
-                                        GWAMD_LDS uint16_t* sinks)
-{
-    g = as_global(g);
-    for (int r = lane; r <= V + 1; r += kWave)
-        flags[r] = 0;
-    wave_sync();
-    int xbase = 0;
-    int nsink = 0;
-    for (int r0 = 1; r0 <= V; r0 += kRowProgBlk)
-        row_program_block<SizeT>(g, V, rec, xl, xl_cap, ring_rows, lane, flags, sinks, r0, xbase, nsink);
-    if (lane == 0)
-        sinks[kSinkCap] = uint16_t(min(nsink, 65535));
-    wave_sync();
-    for (int r = lane + 1; r <= V; r += kWave)
-        if (flags[r])
-            rec[r] |= 1u << 15;
-    wave_sync();
-}
-
-// The row program on every wave of the workgroup (nthr threads, a multiple of
-// kWave; called by all of them with uniform arguments): wave w takes blocks w,
-// w + nwv, ...  A block's list offset and sink index depend on the blocks
-// before it, so a first pass counts each block's list entries and sinks (node
-// -> in- and out-degree, the loads of up to kCB blocks per wave in flight
-// together) into one LDS word per block behind the flags, and a block then
-// starts from the sum over the blocks before it.  Spill flags are plain LDS
-// byte stores, as before; the bit-15 pass over them runs on every thread.
-// flags: V + 2 bytes, then (V + kRowProgBlk - 1) / kRowProgBlk words at the
-// next 16-byte boundary.  Workgroup barriers: 2 (after the counts, after the
-// blocks); the caller's follows the last stores.
-template <typename SizeT>
-__device__ __forceinline__ void build_row_program_core(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl,
-                                                       int xl_cap, int ring_rows,
-                                  int tid, int nthr, GWAMD_LDS uint8_t* flags, GWAMD_LDS uint16_t* sinks)
-{
-    g = as_global(g);
-    constexpr int kRP = kRowProgRP, kCB = 4;
-    const int lane = tid & (kWave - 1);
-    const int wv   = uniform(tid / kWave);
-    const int nwv  = nthr / kWave;
-    const int nblk = (V + kRowProgBlk - 1) / kRowProgBlk;
-    GWAMD_LDS int* blk = (GWAMD_LDS int*)(flags + ((V + 2 + 15) & ~15));
-    for (int r = tid; r <= V + 1; r += nthr)
-        flags[r] = 0;
-    // per block: list entries | sinks << 20 (at most 256 x 50 and 256)
-    for (int b0 = wv; b0 < nblk; b0 += nwv * kCB)
-    {
-        int node[kCB][kRP], ic[kCB][kRP], oc[kCB][kRP];
-#pragma unroll
-        for (int j = 0; j < kCB; j++)
-#pragma unroll
-            for (int u = 0; u < kRP; u++)
-            {
-                const int r = 1 + (b0 + j * nwv) * kRowProgBlk + u * kWave + lane;
-                node[j][u]  = int(g.sorted[min(r, V) - 1]);
-            }
-#pragma unroll
-        for (int j = 0; j < kCB; j++)
-#pragma unroll
-            for (int u = 0; u < kRP; u++)
-            {
-                ic[j][u] = int(g.in_cnt[node[j][u]]);
-                oc[j][u] = int(g.out_cnt[node[j][u]]);
-            }
-#pragma unroll
-        for (int j = 0; j < kCB; j++)
-        {
-            const int b = b0 + j * nwv;
-            int c       = 0;
-#pragma unroll
-            for (int u = 0; u < kRP; u++)
-            {
-                const int r = 1 + b * kRowProgBlk + u * kWave + lane;
-                if (b < nblk && r <= V)
-                    c += (ic[j][u] >= 2 ? ic[j][u] : 0) + (oc[j][u] == 0 ? 1 << 20 : 0);
-            }
-            int total = 0;
-            (void)wave_excl_sum(c, lane, total);
-            if (lane == 0 && b < nblk)
-                blk[b] = total;
-        }
-    }
-    __syncthreads();
-    int xbase = 0, nsink = 0, bnext = 0;
-    for (int b = wv; b < nblk; b += nwv)
-    {
-        for (int q = bnext; q < b; q++)
-        {
-            const int c = uniform(blk[q]);
-            xbase += c & 0xfffff;
-            nsink += c >> 20;
-        }
-        bnext = b + 1; // (the block's own counts are added as it is built)
-        row_program_block<SizeT>(g, V, rec, xl, xl_cap, ring_rows, lane, flags, sinks, 1 + b * kRowProgBlk, xbase,
-                                 nsink);
-    }
-    if (tid == 0)
-    {
-        int ns = 0;
-        for (int q = 0; q < nblk; q++)
-            ns += blk[q] >> 20;
-        sinks[kSinkCap] = uint16_t(min(ns, 65535));
-    }
-    __syncthreads();
-    for (int r = tid + 1; r <= V; r += nthr)
-        if (flags[r])
-            rec[r] |= 1u << 15;
-}
-
-// build_row_program_core out of line with plain arguments, for the test
-// kernel.  (Inlined into a kernel, ROCm 7.2.0's backend stops on this file
-// with "Illegal instruction detected ... V_CMP_NE_U32_e32 0,
-// $src_shared_base".)
-template <typename SizeT>
-__device__ __noinline__ void build_row_program_args(WinGraph<SizeT> g, int V, uint32_t* rec, uint16_t* xl, int xl_cap,
-                                                    int ring_rows, int tid, int nthr, GWAMD_LDS uint8_t* flags,
-                                                    GWAMD_LDS uint16_t* sinks)
-{
-    build_row_program_core<SizeT>(g, V, rec, xl, xl_cap, ring_rows, tid, nthr, flags, sinks);
-}
-
-// build_row_program_core for poa_window_kernel_lds: window w_ with V_ rows,
-// `lds` the start of the LDS image; records, lists, sink words and flags at
-// the offsets of Dims.  Called by every thread of the workgroup.  Out of
-// line with the batch's pointers read from the kernel's own kernarg segment,
-// as add_alignment_waves; kInst: one instantiation per calling kernel.  One
-// call site per kernel: with this routine also at the two rebuilds after a
-// sort (build_row_program_wave0 there), config B's kernel came out at 256
-// VGPRs + 1 AGPR, one wave per SIMD and half the resident workgroups.
-template <int NW, int kInst = 0>
-__device__ __noinline__ void build_row_program(LdsKernelArgsPtr ka_, int w_, int V_, GWAMD_LDS uint8_t* lds)
-{
-    using SizeT               = int16_t;
-    const uint64_t kav        = uint64_t(uintptr_t(ka_));
-    const LdsKernelArgsPtr ka = (LdsKernelArgsPtr)(uintptr_t(
-        (uint64_t(uint32_t(uniform(int(uint32_t(kav >> 32))))) << 32) | uint32_t(uniform(int(uint32_t(kav))))));
-    const size_t w  = size_t(uniform(w_));
-    const size_t mn = size_t(ka->d.max_nodes);
-    lds             = (GWAMD_LDS uint8_t*)(uintptr_t)(uint32_t)uniform(int((uint32_t)(uintptr_t)lds));
-    WinGraph<SizeT> g{};
-    g.base      = ka->b.base + w * mn;
-    g.in_cnt    = ka->b.in_cnt + w * mn;
-    g.out_cnt   = ka->b.out_cnt + w * mn;
-    g.in_e      = static_cast<SizeT*>(ka->b.in_e) + w * mn * kMaxEdges;
-    g.sorted    = static_cast<SizeT*>(ka->b.sorted) + w * mn;
-    g.pos       = static_cast<SizeT*>(ka->b.pos) + w * mn;
-    g.max_nodes = int(mn);
-    const int xcap = ka->d.lds_xl_cap - kSinkWords;
-    build_row_program_core<SizeT>(g, uniform(V_), (uint32_t*)(lds + ka->d.lds_rec_off),
-                                  (uint16_t*)(lds + ka->d.lds_xl_off), xcap, ka->d.lds_ring_rows, int(threadIdx.x),
-                                  NW * kWave, lds + ka->d.lds_ring_off,
-                                  (GWAMD_LDS uint16_t*)(lds + ka->d.lds_xl_off) + xcap);
-}
 
 // ---------------------------------------------------------------------------
 // Packed 16-bit forward pass.  E values are int16, two cells per 32-bit
@@ -1870,639 +1547,8 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
     }
 }
 
-// Test hook: the level-keyed Kahn sort (topsort_levels) of one graph by one
-// workgroup, for the known-answer and random-DAG tests against the FIFO sort.
-template <typename SizeT>
-__global__ void __launch_bounds__(1024) topsort_levels_test_kernel(WinGraph<SizeT> g, int n, int n_prev, int scratch,
-                                                                   SizeT* hint, int n_hint, int* ok, uint64_t* prof)
-{
-    extern __shared__ __align__(16) uint8_t lds[];
-#ifdef GWAMD_TOPSORT_PROFILE
-    uint64_t p[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bool r = topsort_levels<SizeT>(g, n, n_prev, (GWAMD_LDS uint8_t*)(lds), scratch, int(threadIdx.x),
-                                         int(blockDim.x), hint, n_hint, p);
-    if (threadIdx.x == 0 && prof)
-        for (int k = 0; k < 10; k++)
-            prof[k] += p[k];
-#else
-    const bool r = topsort_levels<SizeT>(g, n, n_prev, (GWAMD_LDS uint8_t*)(lds), scratch, int(threadIdx.x),
-                                         int(blockDim.x), hint, n_hint);
-    (void)prof;
-#endif
-    if (threadIdx.x == 0)
-        *ok = r ? 1 : 0;
-}
-
-using gwamd::host::DevBuf; // the launchers below own their device arrays and events (host_common.hpp)
-
-template <typename SizeT>
-int topsort_levels_test(int n, int n_prev, int n_hint, const uint16_t* in_cnt, const int32_t* in_e,
-                        const uint16_t* out_cnt, const int32_t* out_e, int32_t* hint, const int32_t* order_prev,
-                        int threads, int scratch, int32_t* sorted, int reps = 0, double* ms = nullptr,
-                        uint64_t* prof_out = nullptr)
-try
-{
-    const size_t ne = size_t(n) * kMaxEdges;
-    std::vector<SizeT> ie(ne), oe(ne), hi(n, SizeT(0));
-    for (size_t i = 0; i < ne; i++)
-    {
-        ie[i] = SizeT(in_e[i]);
-        oe[i] = SizeT(out_e[i]);
-    }
-    for (int v = 0; hint && v < n; v++)
-        hi[v] = SizeT(hint[v]);
-    if (n <= 0 || threads < 64 || threads > 1024 || threads % 64 || scratch < 0 || scratch > 163840 ||
-        (n_hint > 0 && !hint) || n_prev < 0 || n_prev > n || (n_prev > 0 && !order_prev))
-        return -2;
-    // the previous order: a permutation of the first n_prev nodes
-    std::vector<SizeT> so(n, SizeT(0));
-    {
-        std::vector<char> seen(n_prev, 0);
-        for (int q = 0; q < n_prev; q++)
-        {
-            const int v = order_prev[q];
-            if (v < 0 || v >= n_prev || seen[v])
-                return -2;
-            seen[v] = 1;
-            so[q]   = SizeT(v);
-        }
-    }
-    const gwamd::host::Budget none;
-    DevBuf<uint16_t> d_ic(n, none), d_oc(n, none);
-    DevBuf<SizeT> d_ie(ne, none), d_oe(ne, none), d_sorted(n, none), d_pos(n, none), d_hint(n, none);
-    DevBuf<int> d_ok(1, none);
-    DevBuf<uint64_t> d_prof(10, none);
-    int ok = 0;
-    if (hipMemset(d_prof.data(), 0, 10 * sizeof(uint64_t)))
-        return -1;
-    if (hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oc.data(), out_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie.data(), ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oe.data(), oe.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_hint.data(), hi.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_sorted.data(), so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice))
-        return -1;
-    WinGraph<SizeT> g{};
-    g.in_cnt    = d_ic.data();
-    g.out_cnt   = d_oc.data();
-    g.in_e      = d_ie.data();
-    g.out_e     = d_oe.data();
-    g.sorted    = d_sorted.data();
-    g.pos       = d_pos.data();
-    g.max_nodes = n;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&topsort_levels_test_kernel<SizeT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, scratch))
-        return -1;
-    hipLaunchKernelGGL(topsort_levels_test_kernel<SizeT>, dim3(1), dim3(threads), size_t(scratch), 0, g, n, n_prev,
-                       scratch, d_hint.data(), n_hint, d_ok.data(), nullptr);
-    if (hipGetLastError() || hipDeviceSynchronize() ||
-        hipMemcpy(&ok, d_ok.data(), sizeof(int), hipMemcpyDeviceToHost))
-        return -1;
-    if (reps > 0)
-    {
-        // timing mode: the same sort `reps` times (the graph, previous order and
-        // hints are inputs only; the outputs are rewritten identically)
-        const gwamd::host::OwnedEvent e0, e1;
-        (void)hipEventRecord(e0, 0);
-        for (int k = 0; k < reps; k++)
-        {
-            if (hipMemcpy(d_sorted.data(), so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice))
-                return -1;
-            hipLaunchKernelGGL(topsort_levels_test_kernel<SizeT>, dim3(1), dim3(threads), size_t(scratch), 0, g, n,
-                               n_prev, scratch, d_hint.data(), n_hint, d_ok.data(), d_prof.data());
-        }
-        (void)hipEventRecord(e1, 0);
-        float t = 0.f;
-        if (hipEventSynchronize(e1) || hipEventElapsedTime(&t, e0, e1))
-            return -1;
-        if (ms)
-            *ms = double(t) / reps;
-        if (prof_out && hipMemcpy(prof_out, d_prof.data(), 10 * sizeof(uint64_t), hipMemcpyDeviceToHost))
-            return -1;
-    }
-    std::vector<SizeT> s(n);
-    if (hipMemcpy(s.data(), d_sorted.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost) ||
-        hipMemcpy(hi.data(), d_hint.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost))
-        return -1;
-    for (int q = 0; q < n; q++)
-        sorted[q] = int32_t(s[q]);
-    for (int v = 0; hint && v < n; v++)
-        hint[v] = int32_t(hi[v]);
-    return ok;
-}
-catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
-{
-    return -1;
-}
-
-// Test hook: order_splice_core on one order and one path by one workgroup.
-// LDS: curr | key | cnt | stage (u16), kind (u8), one control word.
-__global__ void __launch_bounds__(1024) order_splice_test_kernel(int16_t* sorted, int16_t* pos, int V, int L,
-                                                                 const uint16_t* curr_g, const uint8_t* kind_g,
-                                                                 int* out)
-{
-    extern __shared__ __align__(16) uint8_t lds[];
-    const int Lp             = (L + 8) & ~7;
-    GWAMD_LDS uint8_t* a     = (GWAMD_LDS uint8_t*)(lds);
-    GWAMD_LDS uint16_t* curr = (GWAMD_LDS uint16_t*)(a);
-    GWAMD_LDS uint16_t* key  = curr + Lp;
-    GWAMD_LDS uint16_t* cnt  = key + Lp;
-    GWAMD_LDS uint16_t* stg  = cnt + ((V + 1 + L + 8) & ~7);
-    GWAMD_LDS int* ctl       = (GWAMD_LDS int*)(stg + ((V + 8) & ~7));
-    GWAMD_LDS uint8_t* kind  = (GWAMD_LDS uint8_t*)(ctl + 4);
-    for (int i = int(threadIdx.x); i < L; i += int(blockDim.x))
-    {
-        curr[i] = curr_g[i];
-        kind[i] = kind_g[i];
-    }
-    __syncthreads();
-    const int r = order_splice_core<int16_t>(glb_of(sorted), glb_of(pos), V, L, curr, kind, key, cnt, stg, ctl,
-                                             int(threadIdx.x), int(blockDim.x));
-    if (threadIdx.x == 0)
-        *out = r;
-}
-
-// sorted: in V entries (a permutation of 0..V-1), out n entries; pos: out n
-// entries; curr / kind: L entries; n: node count with the path's new nodes.
-// Returns order_splice_core's value, -1 on a HIP error, -2 on bad arguments.
-int order_splice_test(int V, int n, int L, int32_t* sorted, int32_t* pos, const int32_t* curr, const uint8_t* kind,
-                      int threads)
-try
-{
-    if (V <= 0 || n < V || n > 32767 || L <= 0 || L > 32767 || threads < 64 || threads > 1024 || threads % 64)
-        return -2;
-    std::vector<int16_t> so(n, int16_t(-1)), po(n, int16_t(-1));
-    std::vector<uint16_t> cu(L);
-    for (int q = 0; q < V; q++)
-    {
-        if (sorted[q] < 0 || sorted[q] >= V || po[sorted[q]] >= 0)
-            return -2;
-        so[q]         = int16_t(sorted[q]);
-        po[sorted[q]] = int16_t(q);
-    }
-    for (int i = 0; i < L; i++)
-    {
-        const bool isnew = (kind[i] & 3) >= 2;
-        if (curr[i] < 0 || curr[i] >= n || (isnew != (curr[i] >= V)))
-            return -2;
-        cu[i] = uint16_t(curr[i]);
-    }
-    const size_t lds_b = 2 * (2 * size_t((L + 8) & ~7) + size_t((V + 1 + L + 8) & ~7) + size_t((V + 8) & ~7)) + 16 +
-                         size_t(L) + 16;
-    if (lds_b > 65536)
-        return -2;
-    const gwamd::host::Budget none;
-    DevBuf<int16_t> d_so(n, none), d_po(n, none);
-    DevBuf<uint16_t> d_cu(L, none);
-    DevBuf<uint8_t> d_ki(L, none);
-    DevBuf<int> d_out(1, none);
-    int out = -1;
-    if (hipMemcpy(d_so.data(), so.data(), n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_po.data(), po.data(), n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_cu.data(), cu.data(), L * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ki.data(), kind, L, hipMemcpyHostToDevice))
-        return -1;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&order_splice_test_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)))
-        return -1;
-    hipLaunchKernelGGL(order_splice_test_kernel, dim3(1), dim3(threads), lds_b, 0, d_so.data(), d_po.data(), V, L,
-                       d_cu.data(), d_ki.data(), d_out.data());
-    if (hipGetLastError() || hipDeviceSynchronize() ||
-        hipMemcpy(&out, d_out.data(), sizeof(int), hipMemcpyDeviceToHost) ||
-        hipMemcpy(so.data(), d_so.data(), n * 2, hipMemcpyDeviceToHost) ||
-        hipMemcpy(po.data(), d_po.data(), n * 2, hipMemcpyDeviceToHost))
-        return -1;
-    for (int q = 0; q < n; q++)
-    {
-        sorted[q] = so[q];
-        pos[q]    = po[q];
-    }
-    return out;
-}
-catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
-{
-    return -1;
-}
-
-// Test hook: the row program of one graph and order built by one wave
-// (build_row_program_wave0) and then by every wave of the workgroup
-// (build_row_program_args), each into cleared LDS, both copied out: records
-// [V + 2] u32, then lists and sink words [xl_cap + kSinkWords] u16.
-template <typename SizeT>
-__global__ void __launch_bounds__(512) row_program_test_kernel(WinGraph<SizeT> g, int V, int xl_cap, int ring_rows,
-                                                               uint32_t* rec_out, uint16_t* xl_out)
-{
-    extern __shared__ __align__(16) uint8_t lds[];
-    const int nrec   = V + 2, nxl = xl_cap + kSinkWords;
-    uint32_t* rec    = reinterpret_cast<uint32_t*>(lds);
-    uint16_t* xl     = reinterpret_cast<uint16_t*>(lds + ((4 * nrec + 15) & ~15));
-    GWAMD_LDS uint8_t* flags = (GWAMD_LDS uint8_t*)(lds) + ((4 * nrec + 15) & ~15) + ((2 * nxl + 15) & ~15);
-    GWAMD_LDS uint16_t* sinks = (GWAMD_LDS uint16_t*)(xl) + xl_cap;
-    const int tid = int(threadIdx.x), nthr = int(blockDim.x);
-    for (int which = 0; which < 2; which++)
-    {
-        for (int i = tid; i < nrec; i += nthr)
-            rec[i] = 0;
-        for (int i = tid; i < nxl; i += nthr)
-            xl[i] = 0;
-        __syncthreads();
-        if (which == 0)
-        {
-            if (tid < kWave)
-                build_row_program_wave0<SizeT>(g, V, rec, xl, xl_cap, ring_rows, tid, flags, sinks);
-        }
-        else
-            build_row_program_args<SizeT>(g, V, rec, xl, xl_cap, ring_rows, tid, nthr, flags, sinks);
-        __syncthreads();
-        for (int i = tid; i < nrec; i += nthr)
-            rec_out[which * nrec + i] = rec[i];
-        for (int i = tid; i < nxl; i += nthr)
-            xl_out[which * nxl + i] = xl[i];
-        __syncthreads();
-    }
-}
-
-// sorted: a topological order of the n nodes.  rec_out: 2 x (n + 2) words,
-// xl_out: 2 x (xl_cap + kSinkWords) entries (the one-wave build first).
-// Returns 0, -1 on a HIP error, -2 on bad arguments.
-int row_program_test(int n, const uint8_t* base, const uint16_t* in_cnt, const uint16_t* out_cnt, const int32_t* in_e,
-                     const int32_t* sorted, int xl_cap, int ring_rows, int threads, uint32_t* rec_out,
-                     uint16_t* xl_out)
-try
-{
-    using SizeT = int16_t;
-    if (n <= 0 || n > 8192 || xl_cap < 64 || xl_cap % 8 || threads < 64 || threads > 512 || threads % 64 ||
-        ring_rows < 1)
-        return -2;
-    const size_t ne = size_t(n) * kMaxEdges;
-    std::vector<SizeT> ie(ne), so(n), po(n, SizeT(-1));
-    for (size_t i = 0; i < ne; i++)
-        ie[i] = SizeT(in_e[i]);
-    for (int q = 0; q < n; q++)
-    {
-        if (sorted[q] < 0 || sorted[q] >= n || po[sorted[q]] >= 0)
-            return -2;
-        so[q]         = SizeT(sorted[q]);
-        po[sorted[q]] = SizeT(q);
-    }
-    const int nrec = n + 2, nxl = xl_cap + kSinkWords;
-    const int nblk = (n + kRowProgBlk - 1) / kRowProgBlk;
-    const size_t lds_b = size_t((4 * nrec + 15) & ~15) + size_t((2 * nxl + 15) & ~15) + size_t((n + 2 + 15) & ~15) +
-                         4 * size_t(nblk) + 16;
-    if (lds_b > 163840)
-        return -2;
-    const gwamd::host::Budget none;
-    DevBuf<uint8_t> d_base(n, none);
-    DevBuf<uint16_t> d_ic(n, none), d_oc(n, none), d_xl(2 * nxl, none);
-    DevBuf<SizeT> d_ie(ne, none), d_so(n, none), d_po(n, none);
-    DevBuf<uint32_t> d_rec(2 * nrec, none);
-    if (hipMemcpy(d_base.data(), base, n, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oc.data(), out_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie.data(), ie.data(), ne * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_so.data(), so.data(), n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_po.data(), po.data(), n * 2, hipMemcpyHostToDevice))
-        return -1;
-    WinGraph<SizeT> g{};
-    g.base      = d_base.data();
-    g.in_cnt    = d_ic.data();
-    g.out_cnt   = d_oc.data();
-    g.in_e      = d_ie.data();
-    g.sorted    = d_so.data();
-    g.pos       = d_po.data();
-    g.max_nodes = n;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&row_program_test_kernel<SizeT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)))
-        return -1;
-    hipLaunchKernelGGL(row_program_test_kernel<SizeT>, dim3(1), dim3(threads), lds_b, 0, g, n, xl_cap, ring_rows,
-                       d_rec.data(), d_xl.data());
-    if (hipGetLastError() || hipDeviceSynchronize() ||
-        hipMemcpy(rec_out, d_rec.data(), 2 * nrec * 4, hipMemcpyDeviceToHost) ||
-        hipMemcpy(xl_out, d_xl.data(), 2 * nxl * 2, hipMemcpyDeviceToHost))
-        return -1;
-    return 0;
-}
-catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
-{
-    return -1;
-}
-
-// Test hook: the racon DFS sort (topsort_racon_lds) of one graph by one wave,
-// with the group heads in HBM (heads != nullptr: racon_dfs_csr) or the
-// round-5 step (heads == nullptr).
-template <typename SizeT>
-__global__ void __launch_bounds__(64) topsort_racon_test_kernel(WinGraph<SizeT> g, int n, int scratch, int32_t* heads,
-                                                               SizeT* mpos, int* out)
-{
-    extern __shared__ __align__(16) uint8_t lds[];
-    // a static word first, as in the kernels: the dynamic scratch then does
-    // not start at LDS address 0 (a null scratch pointer means "no scratch")
-    __shared__ int keep[4];
-    if (threadIdx.x < 4)
-        keep[threadIdx.x] = n;
-    __syncthreads();
-    int cols     = 0;
-    const bool r = topsort_racon_lds<SizeT>(g, n, (GWAMD_LDS uint8_t*)(lds), scratch, int(threadIdx.x), mpos, &cols,
-                                            heads);
-    if (threadIdx.x == 0)
-    {
-        out[0] = r && keep[3] == n ? 1 : 0;
-        out[1] = cols;
-    }
-}
-
-template <typename SizeT>
-int topsort_racon_test(int n, const uint16_t* in_cnt, const int32_t* in_e, const uint16_t* aln_cnt,
-                       const int32_t* aln, int scratch, int v1, int32_t* sorted, int32_t* mpos, int* ncols, int reps,
-                       double* ms)
-try
-{
-    if (n <= 0 || n > 65535 || scratch < 0 || scratch > 163840 - 64)
-        return -2;
-    const size_t ne = size_t(n) * kMaxEdges, na = size_t(n) * kMaxAlignments;
-    std::vector<SizeT> ie(ne), al(na);
-    for (size_t i = 0; i < ne; i++)
-        ie[i] = SizeT(in_e[i]);
-    for (size_t i = 0; i < na; i++)
-        al[i] = SizeT(aln[i]);
-    const gwamd::host::Budget none;
-    DevBuf<uint16_t> d_ic(n, none), d_ac(n, none);
-    DevBuf<SizeT> d_ie(ne, none), d_al(na, none), d_sorted(n, none), d_pos(n, none), d_mpos(n, none);
-    DevBuf<int32_t> d_heads(n, none);
-    DevBuf<int> d_out(2, none);
-    if (hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ac.data(), aln_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie.data(), ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_al.data(), al.data(), na * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemset(d_sorted.data(), 0xff, n * sizeof(SizeT)) || hipMemset(d_mpos.data(), 0xff, n * sizeof(SizeT)))
-        return -1;
-    WinGraph<SizeT> g{};
-    g.in_cnt    = d_ic.data();
-    g.aln_cnt   = d_ac.data();
-    g.in_e      = d_ie.data();
-    g.aln       = d_al.data();
-    g.sorted    = d_sorted.data();
-    g.pos       = d_pos.data();
-    g.max_nodes = n;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&topsort_racon_test_kernel<SizeT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, scratch))
-        return -1;
-    int32_t* hp = v1 ? nullptr : d_heads.data();
-    hipLaunchKernelGGL(topsort_racon_test_kernel<SizeT>, dim3(1), dim3(64), size_t(scratch), 0, g, n, scratch, hp,
-                       d_mpos.data(), d_out.data());
-    int out[2] = {0, 0};
-    if (hipGetLastError() || hipDeviceSynchronize() ||
-        hipMemcpy(out, d_out.data(), sizeof(out), hipMemcpyDeviceToHost))
-        return -1;
-    if (reps > 0)
-    {
-        const gwamd::host::OwnedEvent e0, e1;
-        (void)hipEventRecord(e0, 0);
-        for (int k = 0; k < reps; k++)
-            hipLaunchKernelGGL(topsort_racon_test_kernel<SizeT>, dim3(1), dim3(64), size_t(scratch), 0, g, n,
-                               scratch, hp, d_mpos.data(), d_out.data());
-        (void)hipEventRecord(e1, 0);
-        float t = 0.f;
-        if (hipEventSynchronize(e1) || hipEventElapsedTime(&t, e0, e1))
-            return -1;
-        if (ms)
-            *ms = double(t) / reps;
-    }
-    std::vector<SizeT> s(n), mp(n);
-    if (hipMemcpy(s.data(), d_sorted.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost) ||
-        hipMemcpy(mp.data(), d_mpos.data(), n * sizeof(SizeT), hipMemcpyDeviceToHost))
-        return -1;
-    for (int q = 0; q < n; q++)
-    {
-        sorted[q] = int32_t(s[q]);
-        if (mpos)
-            mpos[q] = int32_t(mp[q]);
-    }
-    if (ncols)
-        *ncols = out[1];
-    return out[0];
-}
-catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
-{
-    return -1;
-}
-
-// Test hook: the consensus of one graph by one wave, as finish_window runs it
-// (consensus_window: the LDS path when the graph fits `scratch` bytes, else
-// consensus_raw on lane 0).
-template <typename SizeT>
-__global__ void __launch_bounds__(64) consensus_test_kernel(WinGraph<SizeT> g, int n, int scratch, int force_hbm,
-                                                           int32_t* cscore, SizeT* cpred, uint8_t* cons,
-                                                           uint16_t* cov, int max_cons, int* out)
-{
-    extern __shared__ __align__(16) uint8_t lds[];
-    __shared__ int sh[2];
-    int len = 0, st = kSuccess;
-    const int path = consensus_window<SizeT>(g, n, cscore, cpred, cons, cov, max_cons, (GWAMD_LDS uint8_t*)(lds),
-                                             scratch, force_hbm != 0, int(threadIdx.x), sh[0], sh[1], len, st);
-    if (threadIdx.x == 0)
-    {
-        if (len < max_cons)
-            cons[len] = 0;
-        out[0] = st;
-        out[1] = len;
-        out[2] = path;
-    }
-}
-
-template <typename SizeT>
-int consensus_test(int n, const uint8_t* base, const int32_t* sorted, const int32_t* pos, const uint16_t* in_cnt,
-                   const int32_t* in_e, const uint16_t* in_w, const uint16_t* out_cnt, const int32_t* out_e,
-                   const uint16_t* aln_cnt, const int32_t* aln, const uint16_t* cov, int max_cons, int force_hbm,
-                   int scratch, int* status, int* len, uint8_t* cons_out, uint16_t* cov_out)
-try
-{
-    if (n <= 0 || n > 32767 || max_cons <= 0 || scratch < 0 || scratch > 163840 - 64)
-        return -2;
-    const size_t ne = size_t(n) * kMaxEdges, na = size_t(n) * kMaxAlignments;
-    std::vector<SizeT> ie(ne), oe(ne), al(na), so(n), po(n);
-    for (size_t i = 0; i < ne; i++)
-    {
-        ie[i] = SizeT(in_e[i]);
-        oe[i] = SizeT(out_e[i]);
-    }
-    for (size_t i = 0; i < na; i++)
-        al[i] = SizeT(aln[i]);
-    for (int q = 0; q < n; q++)
-    {
-        so[q] = SizeT(sorted[q]);
-        po[q] = SizeT(pos[q]);
-    }
-    const size_t mc = size_t(max_cons);
-    const gwamd::host::Budget none;
-    DevBuf<uint8_t> d_base(n, none), d_cons(mc + 1, none);
-    DevBuf<uint16_t> d_ic(n, none), d_oc(n, none), d_ac(n, none), d_cv(n, none), d_iw(ne, none), d_ccov(mc + 1, none);
-    DevBuf<SizeT> d_ie(ne, none), d_oe(ne, none), d_al(na, none), d_sorted(n, none), d_pos(n, none), d_cpred(n, none);
-    DevBuf<int32_t> d_cscore(n, none);
-    DevBuf<int> d_out(3, none);
-    if (hipMemcpy(d_base.data(), base, n, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ic.data(), in_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oc.data(), out_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ac.data(), aln_cnt, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_cv.data(), cov, n * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_iw.data(), in_w, ne * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(d_ie.data(), ie.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_oe.data(), oe.data(), ne * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_al.data(), al.data(), na * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_sorted.data(), so.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemcpy(d_pos.data(), po.data(), n * sizeof(SizeT), hipMemcpyHostToDevice) ||
-        hipMemset(d_cons.data(), 0, mc + 1) ||
-        hipMemset(d_ccov.data(), 0, (mc + 1) * 2))
-        return -1;
-    WinGraph<SizeT> g{};
-    g.base      = d_base.data();
-    g.in_cnt    = d_ic.data();
-    g.out_cnt   = d_oc.data();
-    g.aln_cnt   = d_ac.data();
-    g.cov       = d_cv.data();
-    g.in_w      = d_iw.data();
-    g.in_e      = d_ie.data();
-    g.out_e     = d_oe.data();
-    g.aln       = d_al.data();
-    g.sorted    = d_sorted.data();
-    g.pos       = d_pos.data();
-    g.max_nodes = n;
-    // (at least one LDS word, so the kernel's dynamic array exists)
-    const int lds_bytes = std::max(scratch, 16);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&consensus_test_kernel<SizeT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes))
-        return -1;
-    hipLaunchKernelGGL(consensus_test_kernel<SizeT>, dim3(1), dim3(64), size_t(lds_bytes), 0, g, n, scratch, force_hbm,
-                       d_cscore.data(), d_cpred.data(), d_cons.data(), d_ccov.data(), max_cons, d_out.data());
-    int out[3] = {0, 0, 0};
-    if (hipGetLastError() || hipDeviceSynchronize() ||
-        hipMemcpy(out, d_out.data(), sizeof(out), hipMemcpyDeviceToHost) ||
-        hipMemcpy(cons_out, d_cons.data(), mc, hipMemcpyDeviceToHost) ||
-        hipMemcpy(cov_out, d_ccov.data(), mc * 2, hipMemcpyDeviceToHost))
-        return -1;
-    *status = out[0];
-    *len    = out[1];
-    return out[2];
-}
-catch (const std::runtime_error&) // an allocation or an event the owners (host_common.hpp) could not make
-{
-    return -1;
-}
-
 } // namespace poa
 } // namespace gwamd
-
-// Test hook (tests/test_poa_consensus.py): the consensus of one graph given as
-// the reference's fixed-slot arrays (kMaxEdges / kMaxAlignments slots per
-// node), by one wave with `scratch` bytes of LDS offered to the wave-wide path
-// (consensus_lds); force_hbm keeps consensus_raw.  cons_out / cov_out hold
-// max_cons entries and receive the consensus in host order.  Returns 1 when
-// the LDS path ran, 0 for the HBM path, negative on a HIP error or bad
-// arguments.
-extern "C" int gwamd_internal_consensus(int size_bits, int n, const uint8_t* base, const int32_t* sorted,
-                                        const int32_t* pos, const uint16_t* in_cnt, const int32_t* in_e,
-                                        const uint16_t* in_w, const uint16_t* out_cnt, const int32_t* out_e,
-                                        const uint16_t* aln_cnt, const int32_t* aln, const uint16_t* cov, int max_cons,
-                                        int force_hbm, int scratch, int* status, int* len, uint8_t* cons_out,
-                                        uint16_t* cov_out)
-{
-    if (size_bits == 16)
-        return gwamd::poa::consensus_test<int16_t>(n, base, sorted, pos, in_cnt, in_e, in_w, out_cnt, out_e, aln_cnt,
-                                                   aln, cov, max_cons, force_hbm, scratch, status, len, cons_out,
-                                                   cov_out);
-    return gwamd::poa::consensus_test<int32_t>(n, base, sorted, pos, in_cnt, in_e, in_w, out_cnt, out_e, aln_cnt, aln,
-                                               cov, max_cons, force_hbm, scratch, status, len, cons_out, cov_out);
-}
-
-// The fit rule of the wave-wide consensus: LDS bytes of the compact graph of
-// n nodes and m in-edges, and whether it runs with `scratch` bytes offered.
-extern "C" long long gwamd_internal_consensus_lds_bytes(int n, int m)
-{
-    return gwamd::poa::consensus_lds_bytes(n, m);
-}
-extern "C" int gwamd_internal_consensus_lds_fits(int n, int m, int scratch)
-{
-    return gwamd::poa::consensus_lds_fits(n, m, scratch) ? 1 : 0;
-}
-
-// Test hook (tests/test_poa_topsort.py, scripts/racon_bench.py): the racon
-// DFS sort (cudapoa_topsort.cuh:94-189) of one graph given as fixed-slot
-// in-edge and aligned-node arrays (kMaxEdges / kMaxAlignments slots), by one
-// wave with `scratch` bytes of LDS; v1 selects the round-5 DFS step.  Writes
-// the order, the MSA column of every node and the column count.  Returns 1
-// when the LDS sort ran, 0 when it declined (the kernels then run the HBM
-// sort), negative on a HIP error or bad arguments.  reps > 0: that many more
-// sorts, *ms = the mean time per sort.
-extern "C" int gwamd_internal_topsort_racon(int size_bits, int n, const uint16_t* in_cnt, const int32_t* in_e,
-                                            const uint16_t* aln_cnt, const int32_t* aln, int scratch, int v1,
-                                            int32_t* sorted, int32_t* mpos, int* ncols, int reps, double* ms)
-{
-    if (size_bits == 16)
-        return gwamd::poa::topsort_racon_test<int16_t>(n, in_cnt, in_e, aln_cnt, aln, scratch, v1, sorted, mpos,
-                                                       ncols, reps, ms);
-    return gwamd::poa::topsort_racon_test<int32_t>(n, in_cnt, in_e, aln_cnt, aln, scratch, v1, sorted, mpos, ncols,
-                                                   reps, ms);
-}
-
-// Test hook (tests/test_poa_order_splice.py): the LDS kernel's row program of
-// one graph (fixed-slot in-edge lists, base bytes, degrees) under the order
-// `sorted`, built by one wave and by every wave of a workgroup of `threads`
-// threads; see row_program_test for the outputs.
-extern "C" int gwamd_internal_row_program(int n, const uint8_t* base, const uint16_t* in_cnt, const uint16_t* out_cnt,
-                                          const int32_t* in_e, const int32_t* sorted, int xl_cap, int ring_rows,
-                                          int threads, uint32_t* rec_out, uint16_t* xl_out)
-{
-    return gwamd::poa::row_program_test(n, base, in_cnt, out_cnt, in_e, sorted, xl_cap, ring_rows, threads, rec_out,
-                                        xl_out);
-}
-
-// Test hook (tests/test_poa_order_splice.py): order_splice_core on the order
-// sorted[0..V) and the path curr / kind [L] by one workgroup of `threads`
-// threads; sorted and pos come back with n entries.  Returns 0 spliced, 1 / 2
-// declined (order check / no old node; nothing written), negative on errors.
-extern "C" int gwamd_internal_order_splice(int V, int n, int L, int32_t* sorted, int32_t* pos, const int32_t* curr,
-                                           const uint8_t* kind, int threads)
-{
-    return gwamd::poa::order_splice_test(V, n, L, sorted, pos, curr, kind, threads);
-}
-
-// Test hook (tests/test_poa_topsort.py): topsort_levels of one graph given as
-// the reference's fixed-slot edge arrays (kMaxEdges slots per node), with the
-// previous read's order of the first n_prev nodes (order_prev: a permutation
-// of 0..n_prev-1, may be null when n_prev is 0) and critical-predecessor
-// hints for the first n_hint nodes (hint may be null when n_hint is 0; it
-// receives the final c(v)).  Returns 1 when the level sort produced sorted[],
-// 0 when it declined (the kernels then run the FIFO sort), negative on a HIP
-// error or bad arguments.
-// Timing mode of the same hook (scripts/topsort_bench.py): after the checked
-// run, `reps` more sorts; *ms gets the mean time per sort (HIP events around
-// launches of one workgroup, copies of the previous order included) and
-// prof[10] the section cycles, anchors and iterations of GWAMD_TOPSORT_PROFILE
-// builds.
-extern "C" int gwamd_internal_topsort_levels_timed(int size_bits, int n, int n_prev, int n_hint,
-                                                   const uint16_t* in_cnt, const int32_t* in_e,
-                                                   const uint16_t* out_cnt, const int32_t* out_e, int32_t* hint,
-                                                   const int32_t* order_prev, int threads, int scratch,
-                                                   int32_t* sorted, int reps, double* ms, uint64_t* prof)
-{
-    if (size_bits == 16)
-        return gwamd::poa::topsort_levels_test<int16_t>(n, n_prev, n_hint, in_cnt, in_e, out_cnt, out_e, hint,
-                                                        order_prev, threads, scratch, sorted, reps, ms, prof);
-    return gwamd::poa::topsort_levels_test<int32_t>(n, n_prev, n_hint, in_cnt, in_e, out_cnt, out_e, hint, order_prev,
-                                                    threads, scratch, sorted, reps, ms, prof);
-}
-
-extern "C" int gwamd_internal_topsort_levels(int size_bits, int n, int n_prev, int n_hint, const uint16_t* in_cnt,
-                                             const int32_t* in_e, const uint16_t* out_cnt, const int32_t* out_e,
-                                             int32_t* hint, const int32_t* order_prev, int threads, int scratch,
-                                             int32_t* sorted)
-{
-    if (size_bits == 16)
-        return gwamd::poa::topsort_levels_test<int16_t>(n, n_prev, n_hint, in_cnt, in_e, out_cnt, out_e, hint,
-                                                        order_prev, threads, scratch, sorted);
-    return gwamd::poa::topsort_levels_test<int32_t>(n, n_prev, n_hint, in_cnt, in_e, out_cnt, out_e, hint, order_prev,
-                                                    threads, scratch, sorted);
-}
 
 // ---------------------------------------------------------------------------
 // Kernel table and launch.  gwamd_internal_poa_kernel resolves a plan to its

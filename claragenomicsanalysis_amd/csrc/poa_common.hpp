@@ -10,6 +10,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "poa_handover.hpp"
+
 namespace gwamd
 {
 namespace poa
@@ -190,10 +192,15 @@ constexpr int kTbRankBytes = 7 * 144 + 128 * 4;
 // Small shared region of the LDS kernel (kShBytes(waves) at Dims::lds_sh_off):
 // control ints, per-wave channel progress, the end-row slot, the per-span
 // boundary column ([waves][ring rows] int16) and the span-to-span carry
-// channels ([waves-1][kChanRows] tagged words).
-constexpr int kShProg    = 16;
+// channels ([waves-1][kChanRows] words).  The channels of nw_forward_lds_pk
+// carry tagged words (row << 16 | carry), one row at a time; those of
+// nw_forward_lds_v2 carry blocks of plain carries behind a head word per
+// channel (poa_handover.hpp), and that pass keeps no boundary column.
+constexpr int kShProg    = 16; // [wave] rows taken from the wave's input channel
 constexpr int kShEnd     = 32;
+constexpr int kShHead    = 48; // [wave] rows posted to the wave's output channel (block hand-over)
 constexpr int kShBnd     = 64;
+constexpr int kMaxRingRows16 = 8; // ring rows of the 16-bit pass (poa_plan.cpp)
 constexpr int kShChan    = 128;
 constexpr int kChanRows  = 64;
 constexpr int kMaxWaves  = 4;

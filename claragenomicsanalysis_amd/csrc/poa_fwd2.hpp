@@ -26,6 +26,19 @@
 // forward pass whose helpers (RowProg, load_row_pk, diag_src, pk_*) it uses.
 #pragma once
 
+// Rows per hand-over of carries between neighbouring waves (poa_handover.hpp);
+// 0: the per-row tagged channel of nw_forward_lds_pk, for A/B builds.
+#ifndef GWAMD_HAND_BLOCK
+#define GWAMD_HAND_BLOCK 16
+#endif
+constexpr int kHandBlock = GWAMD_HAND_BLOCK;
+
+// v with lane `sel` replaced by the wave-uniform x.  A compare and a select:
+// this compiler has no builtin for v_writelane, and inline assembly for it
+// has to put the lane select into m0, a register the compiler reserves and
+// does not accept on a clobber list.
+__device__ __forceinline__ int write_lane(int v, int x, int sel, int lane) { return lane == sel ? x : v; }
+
 // 0 <= score <= 255 for both substitution scores in the E domain
 __device__ __forceinline__ bool fwd2_ok(const Scores sc)
 {
@@ -96,14 +109,16 @@ __device__ __forceinline__ void load_row_lds(const GWAMD_LDS int16_t* p, uint32_
     prev = uint32_t(uint16_t(p[0]));
 }
 
-template <int CPL, int NW, bool FIRST, bool FEED, typename SizeT>
+template <int CPL, int NW, bool FIRST, bool FEED, int HB, typename SizeT>
 __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, int V, const uint8_t* read_f, int L,
                                           int16_t* ring_f, int ring_stride, int16_t* spill_f, int stride,
                                           uint8_t* codes_f, int code_stride, const Scores sc,
                                           GWAMD_LDS uint8_t* shb, int16_t* carry_f, int lane, int wave, int cb,
                                           bool to_hbm, bool from_hbm, bool owner, int xl_cap, int& best_row,
-                                          int& best_val)
+                                          int& best_val, FwdProf& fp)
 {
+    static_assert(HB == 0 || (hand_block_ok(HB) && HB + kMaxRingRows16 <= kHandSlots && kChanRows == kHandSlots),
+                  "a block and the ring's reach fit the 64 lanes of the carry register");
     g = as_global(g);
     GWAMD_LDS int16_t* ring          = lds_of(ring_f);
     const GWAMD_LDS uint8_t* read    = lds_of(read_f);
@@ -127,7 +142,8 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
     GWAMD_LDS uint32_t* chan             = (GWAMD_LDS uint32_t*)(shb + kShChan);
     volatile GWAMD_LDS uint32_t* chan_in  = chan + (wave - 1) * kChanRows; // wave > 0
     volatile GWAMD_LDS uint32_t* chan_out = chan + wave * kChanRows;       // wave < NW-1
-    volatile GWAMD_LDS int* prog_v        = (GWAMD_LDS int*)(shb + kShProg);
+    volatile GWAMD_LDS int* prog_v        = (GWAMD_LDS int*)(shb + kShProg); // [wave]: rows taken (tail)
+    volatile GWAMD_LDS int* head_v        = (GWAMD_LDS int*)(shb + kShHead); // [wave]: rows posted (head)
     const int jb     = cb + lane * CPL;
     const bool active = jb < L;
     const int ja     = active ? jb : 0; // address used by inactive lanes
@@ -154,7 +170,12 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
     for (int i = 0; i < NR; i++)
         Eprev[i] = 0;
     int cin_prev = 0;
-    int hbm_c    = 0;
+    // Carries by row, lane r & 63.  Received ones (wave > 0: from the channel;
+    // wave 0 of a later sweep: from HBM; never both), HB > 0: the block of the
+    // current row and the 64 - HB rows before it, which covers the ring's
+    // reach.  Posted ones (FEED, HB > 0): the block being filled.
+    int cv  = 0;
+    int pvr = 0;
     uint32_t rec_c = uint32_t(uniform(int(prec[1])));
     uint32_t rec_n = uint32_t(uniform(int(prec[min(2, V)])));
     // lanes k < np: predecessor rows of row r (rows with a list in LDS)
@@ -162,8 +183,49 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
     int pv_c = xls_at(min(int(rec_c >> 16), xl_last) + lane);
     GWAMD_GLB uint8_t* crow = codes + code_stride;
     GWAMD_GLB int16_t* srow = spill + stride;
+    GWAMD_FP_START(fp);
     for (int r = 1; r <= V; r++, crow += code_stride, srow += stride)
     {
+        if constexpr (HB > 0)
+        {
+            GWAMD_FP_MARK(fp, 4);
+            if (!FIRST && hand_opens(r, HB))
+            {
+                // the carries of this block of rows, into their lanes of cv
+                if (from_hbm)
+                {
+                    const int x = hand_lane_row(lane, r);
+                    uint32_t hc = x >= 1 && x <= V ? uint32_t(int(carry_hbm[x])) : 0u;
+                    settle_vm1(hc); // wait here, once per block, not at every row's readlane
+                    cv = hand_lane_in_block(lane, r, HB) ? int(hc) : cv;
+                }
+                else
+                {
+                    const int need = hand_need_head(r, V, HB);
+                    while (uniform(head_v[wave - 1]) < need)
+                    {
+                        GWAMD_FP_COUNT(fp, 4);
+                        __builtin_amdgcn_s_sleep(1);
+                    }
+                    const int w = int(chan_in[lane]);
+                    cv          = hand_lane_in_block(lane, r, HB) ? w : cv;
+                    if (lane == 0)
+                        prog_v[wave] = hand_new_tail(r, V, HB); // after the load, from the same wave
+                }
+            }
+            if (FEED && hand_opens(r, HB) && hand_must_wait(r))
+            {
+                // flow control: the consumer must have taken the block whose slots this one reuses
+                const int need = hand_free_tail(r, HB);
+                while (uniform(prog_v[wave + 1]) < need)
+                {
+                    GWAMD_FP_COUNT(fp, 5);
+                    __builtin_amdgcn_s_sleep(1);
+                }
+            }
+            GWAMD_FP_LAP(fp, 4);
+        }
+        GWAMD_FP_COUNT(fp, 7);
         const uint32_t rec = rec_c;
         // next rows: the record of row r+2, the predecessor list of row r+1
         const uint32_t rec_nn = prec[min(r + 2, V)];
@@ -180,6 +242,7 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
             for (int i = 0; i < NR; i++)
                 sig[i] = __builtin_amdgcn_perm(T[2 * i + 1], T[2 * i], bsel);
         }
+        GWAMD_FP_LAP(fp, 0);
         int cin = 0;
         // Rest of the row once dg, vt (and kd, kv) hold the maxima over the
         // predecessors: in-lane prefix, closure across lanes and spans,
@@ -200,6 +263,8 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
             const int incl = wave_incl_max_b(m);
             const int excl = __builtin_amdgcn_update_dpp(kNeg, incl, 0x138, 0xf, 0xf, false);
             const int wtot = __builtin_amdgcn_readlane(incl, kWave - 1);
+            GWAMD_FP_LAP(fp, 3);
+            GWAMD_FP_MARK(fp, 4);
             if (FIRST)
             {
                 cin = c0v + gap; // column 0
@@ -213,7 +278,9 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
             }
             else
             {
-                if (from_hbm)
+                if constexpr (HB > 0)
+                    cin = int(int16_t(__builtin_amdgcn_readlane(cv, hand_slot(r))));
+                else if (from_hbm)
                 {
                     // carry of this row from the previous sweep's last span
                     if (((r - 1) & (kWave - 1)) == 0)
@@ -221,9 +288,9 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                         const int x = r + lane;
                         uint32_t hc = x <= V ? uint32_t(int(carry_hbm[x])) : 0u;
                         settle_vm1(hc); // wait here, once per 64 rows, not at every row's readlane
-                        hbm_c = int(hc);
+                        cv = int(hc);
                     }
-                    cin = int(int16_t(__builtin_amdgcn_readlane(hbm_c, (r - 1) & (kWave - 1))));
+                    cin = int(int16_t(__builtin_amdgcn_readlane(cv, (r - 1) & (kWave - 1))));
                 }
                 else
                 {
@@ -231,6 +298,7 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                     uint32_t w = uint32_t(uniform(int(chan_in[r & (kChanRows - 1)])));
                     while ((w >> 16) != (uint32_t(r) & 0xffffu))
                     {
+                        GWAMD_FP_COUNT(fp, 4);
                         __builtin_amdgcn_s_sleep(1);
                         w = uint32_t(uniform(int(chan_in[r & (kChanRows - 1)])));
                     }
@@ -240,24 +308,34 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                 }
                 if (lane == 0)
                 {
-                    bnd[r & mask] = int16_t(cin);
+                    if constexpr (HB == 0)
+                        bnd[r & mask] = int16_t(cin);
                     if (spill_r)
                         srow[cb + kColShift] = int16_t(cin); // same value as the previous span's last cell
                 }
             }
             if (FEED)
             {
-                // flow control: the consumer must have taken row r-kChanRows+32
-                if ((r & 31) == 0 && r >= kChanRows)
+                if constexpr (HB > 0)
+                    pvr = write_lane(pvr, max(cin, wtot), hand_slot(r), lane);
+                else
                 {
-                    while (uniform(prog_v[wave + 1]) < r - 32)
-                        __builtin_amdgcn_s_sleep(1);
+                    // flow control: the consumer must have taken row r-kChanRows+32
+                    if ((r & 31) == 0 && r >= kChanRows)
+                    {
+                        while (uniform(prog_v[wave + 1]) < r - 32)
+                        {
+                            GWAMD_FP_COUNT(fp, 5);
+                            __builtin_amdgcn_s_sleep(1);
+                        }
+                    }
+                    if (lane == 0)
+                        chan_out[r & (kChanRows - 1)] = (uint32_t(r) << 16) | uint32_t(uint16_t(max(cin, wtot)));
                 }
-                if (lane == 0)
-                    chan_out[r & (kChanRows - 1)] = (uint32_t(r) << 16) | uint32_t(uint16_t(max(cin, wtot)));
             }
             if (to_hbm && lane == 0)
                 carry_hbm[r] = int16_t(max(cin, wtot));
+            GWAMD_FP_LAP(fp, 4);
             const uint32_t b2v = pk_bcast(max(excl, cin));
 #pragma unroll
             for (int i = 0; i < NR; i++)
@@ -308,6 +386,7 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                                                 reinterpret_cast<GWAMD_GLB uint32_t*>(crow + jb + kColShift + 1));
                 }
             }
+            GWAMD_FP_LAP(fp, 5);
             if ((rec & (1u << 14)) && owner)
             {
                 // sink row: E at the last column (column 0 for an empty read),
@@ -336,15 +415,20 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
             const int d = int(rec >> 16);
             uint32_t prev;
             if (d == 1)
+            {
+                GWAMD_FP_COUNT(fp, 0);
                 prev = uint32_t(__builtin_amdgcn_update_dpp(int(uint32_t(uint16_t(cin_prev))),
                                                             int(Eprev[NR - 1] >> 16), 0x138, 0xf, 0xf, false));
+            }
             else
             {
+                GWAMD_FP_COUNT(fp, 1);
                 const int ps = (r - d) & mask;
                 load_row_lds<NR>(ring + ps * ring_stride + ja + kColShift, Eprev, prev);
                 if (!FIRST)
                 {
-                    const uint32_t bv = uint32_t(uint16_t(bnd[ps]));
+                    const uint32_t bv = HB > 0 ? uint32_t(__builtin_amdgcn_readlane(cv, hand_slot(r - d))) & 0xffffu
+                                               : uint32_t(uint16_t(bnd[ps]));
                     prev              = lane == 0 ? bv : prev;
                 }
             }
@@ -357,6 +441,7 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                 dg[i] = pk_add(dg[i], sig[i]);
                 vt[i] = pk_add(Eprev[i], gap2);
             }
+            GWAMD_FP_LAP(fp, 1);
             finish(std::false_type{}, dg, vt, dg, vt, c0v, 0);
         }
         else
@@ -399,7 +484,8 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                     load_row_lds<NR>(ring + (p & mask) * ring_stride + ja + kColShift, Q, qprev);
                     if (!FIRST)
                     {
-                        const uint32_t bv = uint32_t(uint16_t(bnd[p & mask]));
+                        const uint32_t bv = HB > 0 ? uint32_t(__builtin_amdgcn_readlane(cv, hand_slot(p))) & 0xffffu
+                                                   : uint32_t(uint16_t(bnd[p & mask]));
                         qprev             = lane == 0 ? bv : qprev;
                     }
                 };
@@ -454,15 +540,23 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                             vt[i] = nv;
                         }
                     }
+                    GWAMD_FP_LAP(fp, 2);
                     finish(std::true_type{}, dg, vt, kd, kv, c0v, c0kv);
                 }
                 else
+                {
+                    GWAMD_FP_LAP(fp, 2);
                     finish(std::false_type{}, dg, vt, dg, vt, c0v, 0);
+                }
             };
             if (!(rec & 0x80u))
+            {
+                GWAMD_FP_COUNT(fp, 2);
                 rows_general(std::false_type{}, pv_c, np); // np >= 2, every predecessor in the ring
+            }
             else
             {
+                GWAMD_FP_COUNT(fp, 3);
                 // predecessor rows (sources: n = 1, row 0); lists through the
                 // typed LDS pointer (P's own is flat: its loads count in
                 // vmcnt, so a wait for them also waits for every code store)
@@ -495,11 +589,26 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                 rows_general(std::true_type{}, pv, uniform(n));
             }
         }
+        if constexpr (HB > 0)
+        {
+            if (FEED && hand_closes(r, V, HB))
+            {
+                GWAMD_FP_MARK(fp, 4);
+                // post the block (a partial one at row V): its carries, then the head, from the same wave
+                if (hand_lane_in_block(lane, r, HB))
+                    chan_out[lane] = uint32_t(pvr);
+                if (lane == 0)
+                    head_v[wave] = r;
+                GWAMD_FP_LAP(fp, 4);
+            }
+        }
         cin_prev = cin;
         rec_c    = rec_n;
         rec_n    = uint32_t(uniform(int(rec_nn)));
         pv_c     = pv_n;
+        GWAMD_FP_LAP(fp, 6);
     }
+    GWAMD_FP_STOP(fp);
 }
 
 // Drop-in for nw_forward_lds_pk (same arguments and result) when fwd2_ok(sc).
@@ -507,7 +616,7 @@ template <int CPL, int NW, typename SizeT>
 __device__ int nw_forward_lds_v2(WinGraph<SizeT> g, const RowProg& P, int V, const uint8_t* read, int L,
                                  int16_t* ring, int ring_stride, int16_t* spill, int stride, uint8_t* codes,
                                  int code_stride, const Scores sc, GWAMD_LDS uint8_t* shb, int16_t* carry_hbm,
-                                 int tid, int xl_cap)
+                                 int tid, int xl_cap, FwdProf& fp)
 {
     constexpr int kSpan = kWave * CPL;
     const int lane      = tid & (kWave - 1);
@@ -540,25 +649,22 @@ __device__ int nw_forward_lds_v2(WinGraph<SizeT> g, const RowProg& P, int V, con
         const bool owner    = span == own_span;
         if (!wact || V < 1)
             continue;
+        auto rows = [&](auto first_tag, auto feed_tag) __attribute__((always_inline)) {
+            fwd2_rows<CPL, NW, decltype(first_tag)::value, decltype(feed_tag)::value, kHandBlock>(
+                g, P, V, read, L, ring, ring_stride, spill, stride, codes, code_stride, sc, shb, carry_hbm, lane, wave,
+                cb, to_hbm, from_hbm, owner, xl_cap, best_row, best_val, fp);
+        };
         if (first)
         {
             if (feed)
-                fwd2_rows<CPL, NW, true, true>(g, P, V, read, L, ring, ring_stride, spill, stride, codes,
-                                               code_stride, sc, shb, carry_hbm, lane, wave, cb, to_hbm, from_hbm,
-                                               owner, xl_cap, best_row, best_val);
+                rows(std::true_type{}, std::true_type{});
             else
-                fwd2_rows<CPL, NW, true, false>(g, P, V, read, L, ring, ring_stride, spill, stride, codes,
-                                                code_stride, sc, shb, carry_hbm, lane, wave, cb, to_hbm,
-                                                from_hbm, owner, xl_cap, best_row, best_val);
+                rows(std::true_type{}, std::false_type{});
         }
         else if (feed)
-            fwd2_rows<CPL, NW, false, true>(g, P, V, read, L, ring, ring_stride, spill, stride, codes, code_stride,
-                                            sc, shb, carry_hbm, lane, wave, cb, to_hbm, from_hbm, owner, xl_cap,
-                                            best_row, best_val);
+            rows(std::false_type{}, std::true_type{});
         else
-            fwd2_rows<CPL, NW, false, false>(g, P, V, read, L, ring, ring_stride, spill, stride, codes,
-                                             code_stride, sc, shb, carry_hbm, lane, wave, cb, to_hbm, from_hbm,
-                                             owner, xl_cap, best_row, best_val);
+            rows(std::false_type{}, std::false_type{});
     } // sweeps
     if (nsweep > 1 || NW > 1)
     {

@@ -311,12 +311,51 @@ __device__ __forceinline__ void diag_src(const uint32_t (&P)[NR], uint32_t prev,
 
 // Diagnostic build only (-DGWAMD_FWD_PROFILE): shader-clock cycles of the
 // forward pass sections, stored in place of the backbone/add/topsort/output
-// phase slots.
+// phase slots.  With -DGWAMD_FWD_PROFILE_COUNTS as well the slots hold event
+// counts instead (rows by kind, poll misses), and no clock is read.  The
+// 16-bit scores take nw_forward_lds_v2 as in the default build
+// (GWAMD_POA_FWD=v1: the round-3 pass); its sections are listed in
+// scripts/gpu_fwdprof.sh.
 #ifdef GWAMD_FWD_PROFILE
 struct FwdProf
 {
     uint64_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t m    = 0;
+#ifdef GWAMD_FWD_PROFILE_COUNTS
+    __device__ void start() {}
+    template <int I>
+    __device__ void lap()
+    {
+    }
+    template <int I>
+    __device__ void count()
+    {
+        t[I] += 1;
+    }
+#elif defined(GWAMD_FWD_PROFILE_ONLY)
+    // one section of nw_forward_lds_v2 timed (slot GWAMD_FWD_PROFILE_ONLY,
+    // between its marks and its laps) and the whole row loop (slot 7): two
+    // clock reads per timed section instead of one per lap
+    uint64_t m0 = 0;
+    __device__ void start() { m0 = __builtin_amdgcn_s_memtime(); }
+    __device__ void stop() { t[7] += __builtin_amdgcn_s_memtime() - m0; }
+    template <int I>
+    __device__ void mark()
+    {
+        if (I == GWAMD_FWD_PROFILE_ONLY)
+            m = __builtin_amdgcn_s_memtime();
+    }
+    template <int I>
+    __device__ void lap()
+    {
+        if (I == GWAMD_FWD_PROFILE_ONLY)
+            t[I] += __builtin_amdgcn_s_memtime() - m;
+    }
+    template <int I>
+    __device__ void count()
+    {
+    }
+#else
     __device__ void start() { m = __builtin_amdgcn_s_memtime(); }
     template <int I>
     __device__ void lap()
@@ -325,15 +364,33 @@ struct FwdProf
         t[I] += x - m;
         m = x;
     }
+    template <int I>
+    __device__ void count()
+    {
+    }
+#endif
+#ifndef GWAMD_FWD_PROFILE_ONLY
+    __device__ void stop() {}
+    template <int I>
+    __device__ void mark()
+    {
+    }
+#endif
 };
 #define GWAMD_FP_START(fp) fp.start()
+#define GWAMD_FP_STOP(fp) fp.stop()
+#define GWAMD_FP_MARK(fp, I) fp.template mark<I>()
 #define GWAMD_FP_LAP(fp, I) fp.template lap<I>()
+#define GWAMD_FP_COUNT(fp, I) fp.template count<I>()
 #else
 struct FwdProf
 {
 };
 #define GWAMD_FP_START(fp)
+#define GWAMD_FP_STOP(fp)
+#define GWAMD_FP_MARK(fp, I)
 #define GWAMD_FP_LAP(fp, I)
+#define GWAMD_FP_COUNT(fp, I)
 #endif
 
 // Lane-parallel predecessor rows of row rr: lane k < n holds the row of
@@ -370,7 +427,10 @@ __device__ __forceinline__ int row_preds(const RowProg& P, WinGraph<SizeT> g, in
 // wave q needs from wave q-1 only the carry of each row (E_r[cb], the maximum
 // over every column left of its span), which wave q-1 posts into a tagged
 // LDS channel as soon as its row scan is done; wave q computes its own cells
-// of the row before it waits for that word.  The column-0 value of a row is
+// of the row before it waits for that word.  (This pass and nw_forward_lds_w:
+// one word per row.  nw_forward_lds_v2 hands the carries over in blocks of
+// kHandBlock rows, untagged, behind a head / tail pair in the same region, and
+// keeps them in a register instead of `bnd`: poa_handover.hpp.)  The column-0 value of a row is
 // the maximum of its predecessors' column-0 values, which lane 0 of wave 0
 // loads anyway as the diagonal source of column 1.  The diagonal source of a
 // span's first column for predecessor row p is the carry the wave received
@@ -1104,11 +1164,7 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
     FwdProf fp;
     // round-4 forward pass unless the scores do not fit its byte table (or
     // kDiagFwdV1, GWAMD_POA_FWD=v1 under GWAMD_DIAG, asks for round 3's)
-#ifdef GWAMD_FWD_PROFILE
-    const bool use_v2 = false;
-#else
     const bool use_v2 = !W && fwd2_ok(sc) && !(d.diag & kDiagFwdV1);
-#endif
     const WindowDesc wd = b.windows[w];
     const int nseq      = wd.num_seqs;
     int status          = kSuccess;
@@ -1244,7 +1300,7 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
             else if constexpr (CPL <= 16)
                 end_row = use_v2 ? nw_forward_lds_v2<CPL, NW, SizeT>(g, P, V, lread, L, ring, rstride, spill, rstride,
                                                                      codes, d.code_stride, sc, shb, carry, tid,
-                                                                     d.lds_xl_cap)
+                                                                     d.lds_xl_cap, fp)
                                  : nw_forward_lds_pk<CPL, NW, SizeT>(g, P, V, lread, L, ring, rstride, spill, rstride,
                                                                      codes, d.code_stride, sc, shb, carry, tid, fp);
             else

@@ -1063,15 +1063,7 @@ __device__ __forceinline__ int band_traceback(WinGraph<SizeT> g, BandAux X, int 
     int n = 0, loops = 0;
     const int bound = L + V + 2;
     int eg = 0, er = 0;
-    auto flush = [&](int upto) {
-        const int base = (upto - 1) & ~(kWave - 1);
-        const int k    = base + lane;
-        if (k < upto && k < aln_cap)
-        {
-            ag[k] = SizeT(eg > 0 ? int(g.sorted[eg - 1]) : -1);
-            ar[k] = SizeT(er);
-        }
-    };
+    auto flush = [&](int upto) { tb_flush<SizeT>(g.sorted, ag, ar, aln_cap, upto, lane, eg, er); };
     bool bad = false;
     // code tile: kBandTile rows of bw = 64*CPL code bytes from row ti0 on, and
     // their row records one per lane
@@ -1188,28 +1180,7 @@ __device__ __forceinline__ int band_traceback(WinGraph<SizeT> g, BandAux X, int 
                 walk_window_ranked<1>(wpk0, wpk1, G, ci, cj, cn, cl, bound, lane, eg, er,
                                       tile + kBandTile * bw + kWave * 16 + 512, flush);
             else
-            while (true)
-            {
-                const int idx     = G.index(ci, cj);
-                const uint32_t nx = uint32_t(idx < kWave ? __builtin_amdgcn_readlane(int(wpk0), idx)
-                                                         : __builtin_amdgcn_readlane(int(wpk1), idx - kWave));
-                if (nx == kSlow)
-                    break;
-                const int pi = int(nx >> 16), pj = int(nx & 0xffffu);
-                cl++;
-                if (lane == (cn & (kWave - 1)))
-                {
-                    eg = ci == pi ? -1 : ci;
-                    er = cj == pj ? -1 : cj - 1;
-                }
-                cn++;
-                if ((cn & (kWave - 1)) == 0)
-                    flush(cn);
-                ci = pi;
-                cj = pj;
-                if ((ci == 0 && cj == 0) || cl >= bound || ci < 1 || cj < 1 || G.index(ci, cj) < 0)
-                    break;
-            }
+                walk_window_scalar<1>(wpk0, wpk1, G, ci, cj, cn, cl, bound, lane, eg, er, nullptr, flush);
             if (cl != loops)
             {
                 G.follow(ci, cj);
@@ -1343,25 +1314,13 @@ __device__ __forceinline__ int band_traceback(WinGraph<SizeT> g, BandAux X, int 
     return n;
 }
 
-// Per-window pointers of the banded kernel (graph by window, scratch by slot).
-template <typename ScoreT, typename SizeT>
-__device__ __forceinline__ void band_window_ptrs(const Buffers& b, const Dims& d, int w, size_t slot, int rowsz,
-                                                 WinGraph<SizeT>& g, BandAux& X, ScoreT*& spill)
+// The banded kernel's own scratch of a slot: spill rows and the side buffer
+// (the graph and the rest: bind_window, bind_slot).
+template <typename ScoreT>
+__device__ __forceinline__ void band_window_ptrs(const Buffers& b, const Dims& d, size_t slot, int rowsz, BandAux& X,
+                                                 ScoreT*& spill)
 {
-    const size_t mn = size_t(d.max_nodes);
-    g.base      = b.base + w * mn;
-    g.in_cnt    = b.in_cnt + w * mn;
-    g.out_cnt   = b.out_cnt + w * mn;
-    g.aln_cnt   = b.aln_cnt + w * mn;
-    g.cov       = b.node_cov + w * mn;
-    g.in_w      = b.in_w + w * mn * kMaxEdges;
-    g.in_e      = static_cast<SizeT*>(b.in_e) + w * mn * kMaxEdges;
-    g.out_e     = static_cast<SizeT*>(b.out_e) + w * mn * kMaxEdges;
-    g.aln       = static_cast<SizeT*>(b.aln) + w * mn * kMaxAlignments;
-    g.sorted    = static_cast<SizeT*>(b.sorted) + w * mn;
-    g.pos       = static_cast<SizeT*>(b.pos) + w * mn;
-    g.max_nodes = d.max_nodes;
-    spill       = static_cast<ScoreT*>(b.scores) + slot * d.score_rows * size_t(rowsz);
+    spill        = static_cast<ScoreT*>(b.scores) + slot * d.score_rows * size_t(rowsz);
     uint8_t* aux = b.codes + slot * size_t(d.aux_stride);
     X.codes  = aux;
     X.reca   = reinterpret_cast<uint32_t*>(aux + d.aux_reca_off);
@@ -1397,10 +1356,32 @@ __device__ __forceinline__ AddScratch band_add_scratch(GWAMD_LDS uint8_t* work, 
     return AX;
 }
 
+// What wave 0 asks of the helper waves: one pass of one window on every wave
+// (Done: no more passes, the helper waves leave).
+struct BandJob
+{
+    enum Kind : int { Forward, LevelSort, AddPasses, Done } kind;
+    int window;
+    union
+    {
+        struct { int V, L; float gradient; } fwd;     // band_forward_ad: rows, read length, Band::gradient
+        struct { int nodes, prev_nodes, hint; } sort; // topsort_levels: nodes after / before the read, cpred entries
+        struct { int nodes, alen, L, read, V; } add;  // add_alignment_parallel_batched's order-free passes: nodes
+                                                      // before the read, path length, read length, read index,
+                                                      // rows before the read
+    };
+};
+
+__device__ __forceinline__ void post(BandJob& slot, const BandJob& job, int lane)
+{
+    if (lane == 0)
+        slot = job;
+}
+
 // One window per workgroup.  Wave 0 runs the whole window; with the
 // anti-diagonal pass (d.band_ad) the workgroup has kAdMaxWaves waves and waves
-// 1.. only join the forward passes: wave 0 posts each pass in sh_job and both
-// sides meet at two barriers around it (sh_job[0] < 0: no more passes).
+// 1.. only join the passes that wave 0 posts as a BandJob: both sides meet at
+// two barriers around each pass.
 template <typename ScoreT, typename SizeT, bool MSA, int CPL>
 __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Buffers b, Dims d, Scores sc)
 {
@@ -1409,9 +1390,7 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
     __shared__ int sh_status;
     __shared__ int sh_len;
     __shared__ AdShared ad_sh;
-    __shared__ int sh_job[8]; // window, V, L, gradient bits, job kind (0 forward pass, 1 topological sort:
-                              // window, node count, hint count, previous node count; 2 graph update:
-                              // window, node count, alignment length, L, -, read index, V)
+    __shared__ BandJob mailbox; // wave 0 to the helper waves
 
     __shared__ int sh_next;
     if (int(blockIdx.x) >= b.num_windows)
@@ -1437,51 +1416,48 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
         while (true)
         {
             __syncthreads(); // pass posted
-            const int w = sh_job[0];
-            if (w < 0)
+            const BandJob& job      = mailbox;
+            const size_t w          = size_t(job.window);
+            const WinGraph<SizeT> g = bind_window<SizeT>(b, d.max_nodes, w);
+            switch (job.kind)
+            {
+            case BandJob::LevelSort:
+                topsort_levels<SizeT>(g, job.sort.nodes, job.sort.prev_nodes, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off,
+                                      int(threadIdx.x), int(blockDim.x), bind_slot<SizeT>(b, d, slot).cpred,
+                                      job.sort.hint);
                 break;
-            WinGraph<SizeT> g;
-            BandAux X;
-            ScoreT* spill;
-            band_window_ptrs<ScoreT, SizeT>(b, d, w, slot, rowsz, g, X, spill);
-            if (sh_job[4] == 1)
+            case BandJob::AddPasses:
             {
-                // the level-keyed Kahn sort of this read (every wave)
-                topsort_levels<SizeT>(g, sh_job[1], sh_job[3], (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off,
-                                      int(threadIdx.x), int(blockDim.x),
-                                      static_cast<SizeT*>(b.cpred) + slot * size_t(d.max_nodes) * 4, sh_job[2]);
-                __syncthreads(); // pass done
-                continue;
-            }
-            if (sh_job[4] == 2)
-            {
-                // the order-free passes of the graph update (every wave)
-                const WindowDesc wd = b.windows[w];
-                const int s         = sh_job[5];
-                const int L         = sh_job[3];
-                const int V         = sh_job[6];
-                int nc              = sh_job[1];
-                const size_t mn     = size_t(d.max_nodes);
-                uint16_t* ecov      = MSA ? b.edge_cov + w * mn * kMaxEdges * d.max_seqs : nullptr;
-                uint16_t* ecovc     = MSA ? b.edge_cov_cnt + w * mn * kMaxEdges : nullptr;
-                SizeT* seq_begin    = MSA ? static_cast<SizeT*>(b.seq_begin) + size_t(w) * d.max_seqs : nullptr;
-                AddScratch AX       = band_add_scratch(work, shb, L, V);
+                const WindowDesc wd         = b.windows[w];
+                const int s                 = job.add.read;
+                int nc                      = job.add.nodes;
+                const SlotScratch<SizeT> sl = bind_slot<SizeT>(b, d, slot);
+                const WinMsa<SizeT> msa     = bind_window_msa<SizeT, MSA>(b, d, w);
+                AddScratch AX               = band_add_scratch(work, shb, job.add.L, job.add.V);
                 add_alignment_parallel_batched<SizeT, MSA, kBandAddAU>(
-                    g, nc, static_cast<SizeT*>(b.ag) + slot * d.aln_cap, static_cast<SizeT*>(b.ar) + slot * d.aln_cap,
-                    sh_job[2], L, lread, b.wts + b.seq_off[wd.first_seq + s], s, ecov, ecovc, seq_begin, d.max_seqs,
-                    AX, lane, nullptr, wave, nw);
-                __syncthreads(); // pass done
-                continue;
+                    g, nc, sl.ag, sl.ar, job.add.alen, job.add.L, lread, b.wts + b.seq_off[wd.first_seq + s], s,
+                    msa.ecov, msa.ecov_cnt, msa.seq_begin, d.max_seqs, AX, lane, nullptr, wave, nw);
+                break;
             }
-            Band B;
-            B.bw         = d.band_width;
-            B.stride     = d.band_width + kBandPad;
-            B.max_column = sh_job[2] + 1;
-            B.gradient   = __int_as_float(sh_job[3]);
-            BandProf bp;
-            if constexpr (CPL <= 4) // the anti-diagonal pass serves band widths 128 and 256
-                band_forward_ad<ScoreT, SizeT, CPL>(g, X, sh_job[1], (GWAMD_LDS const uint8_t*)(lread), sh_job[2], B,
-                                                    sc, ring, spill, rowsz, d.score_rows, lane, wave, nw, adsh, bp);
+            case BandJob::Forward:
+            {
+                BandAux X;
+                ScoreT* spill;
+                band_window_ptrs<ScoreT>(b, d, slot, rowsz, X, spill);
+                Band B;
+                B.bw         = d.band_width;
+                B.stride     = d.band_width + kBandPad;
+                B.max_column = job.fwd.L + 1;
+                B.gradient   = job.fwd.gradient;
+                BandProf bp;
+                if constexpr (CPL <= 4) // the anti-diagonal pass serves band widths 128 and 256
+                    band_forward_ad<ScoreT, SizeT, CPL>(g, X, job.fwd.V, (GWAMD_LDS const uint8_t*)(lread), job.fwd.L,
+                                                        B, sc, ring, spill, rowsz, d.score_rows, lane, wave, nw, adsh,
+                                                        bp);
+                break;
+            }
+            case BandJob::Done: return;
+            }
             __syncthreads(); // pass done
         }
         return;
@@ -1490,18 +1466,15 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
     for (int idx = blockIdx.x; idx < b.num_windows;)
     {
     const int w     = b.order ? b.order[idx] : idx;
-    const size_t mn = size_t(d.max_nodes);
-    WinGraph<SizeT> g;
+    const WinGraph<SizeT> g     = bind_window<SizeT>(b, d.max_nodes, size_t(w));
+    const SlotScratch<SizeT> sl = bind_slot<SizeT>(b, d, slot);
+    const WinMsa<SizeT> msa     = bind_window_msa<SizeT, MSA>(b, d, size_t(w));
     BandAux X;
     ScoreT* spill;
-    band_window_ptrs<ScoreT, SizeT>(b, d, w, slot, rowsz, g, X, spill);
-    SizeT* ag        = static_cast<SizeT*>(b.ag) + slot * d.aln_cap;
-    SizeT* ar        = static_cast<SizeT*>(b.ar) + slot * d.aln_cap;
-    int32_t* cscore  = b.cscore + slot * mn;
-    SizeT* cpred     = static_cast<SizeT*>(b.cpred) + slot * mn * 4;
-    uint16_t* ecov   = MSA ? b.edge_cov + w * mn * kMaxEdges * d.max_seqs : nullptr;
-    uint16_t* ecovc  = MSA ? b.edge_cov_cnt + w * mn * kMaxEdges : nullptr;
-    SizeT* seq_begin = MSA ? static_cast<SizeT*>(b.seq_begin) + size_t(w) * d.max_seqs : nullptr;
+    band_window_ptrs<ScoreT>(b, d, slot, rowsz, X, spill);
+    SizeT *ag = sl.ag, *ar = sl.ar, *cpred = sl.cpred, *seq_begin = msa.seq_begin;
+    int32_t* cscore = sl.cscore;
+    uint16_t *ecov = msa.ecov, *ecovc = msa.ecov_cnt;
 
     PhaseTimer ph;
     BandProf bp;
@@ -1557,14 +1530,11 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
                 band_ad_init<ScoreT, CPL>(ring, rowsz, d.band_width, int(band_min_value<ScoreT>(sc)), V, adsh, lane);
                 if (nw > 1)
                 {
-                    if (lane == 0)
-                    {
-                        sh_job[0] = w;
-                        sh_job[1] = V;
-                        sh_job[2] = L;
-                        sh_job[3] = __float_as_int(B.gradient);
-                        sh_job[4] = 0;
-                    }
+                    BandJob job;
+                    job.kind   = BandJob::Forward;
+                    job.window = w;
+                    job.fwd    = {V, L, B.gradient};
+                    post(mailbox, job, lane);
                     __syncthreads(); // pass posted
                 }
                 band_forward_ad<ScoreT, SizeT, CPL>(g, X, V, (GWAMD_LDS const uint8_t*)(lread), L, B, sc, ring, spill,
@@ -1607,16 +1577,11 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
                 AddScratch AX = band_add_scratch(work, shb, L, V);
                 if (nw > 1)
                 {
-                    if (lane == 0)
-                    {
-                        sh_job[0] = w;
-                        sh_job[1] = nc;
-                        sh_job[2] = alen;
-                        sh_job[3] = L;
-                        sh_job[4] = 2;
-                        sh_job[5] = s;
-                        sh_job[6] = V;
-                    }
+                    BandJob job;
+                    job.kind   = BandJob::AddPasses;
+                    job.window = w;
+                    job.add    = {nc, alen, L, s, V};
+                    post(mailbox, job, lane);
                     __syncthreads(); // pass posted
                 }
                 rc = add_alignment_parallel_batched<SizeT, MSA, kBandAddAU>(g, nc, ag, ar, alen, L, lread, wts_g, s,
@@ -1648,14 +1613,11 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
                 // (GWAMD_TOPSORT=fifo, kDiagTopsortFifo, keeps the FIFO below)
                 if (nw > 1)
                 {
-                    if (lane == 0)
-                    {
-                        sh_job[0] = w;
-                        sh_job[1] = nc;
-                        sh_job[2] = lv_hint;
-                        sh_job[3] = V;
-                        sh_job[4] = 1;
-                    }
+                    BandJob job;
+                    job.kind   = BandJob::LevelSort;
+                    job.window = w;
+                    job.sort   = {nc, V, lv_hint};
+                    post(mailbox, job, lane);
                     __syncthreads(); // pass posted
                 }
                 lv_done = topsort_levels<SizeT>(g, nc, V, (GWAMD_LDS uint8_t*)(lds), d.lds_sh_off, int(threadIdx.x),
@@ -1779,8 +1741,10 @@ __global__ void __launch_bounds__(kWave * kAdMaxWaves) poa_window_kernel_band(Bu
     }
     if (nw > 1)
     {
-        if (lane == 0)
-            sh_job[0] = -1;
+        BandJob job;
+        job.kind   = BandJob::Done;
+        job.window = 0;
+        post(mailbox, job, lane);
         __syncthreads(); // release the helper waves
     }
 }

@@ -61,6 +61,62 @@ __device__ __forceinline__ WinGraph<SizeT> as_global(WinGraph<SizeT> g)
     return g;
 }
 
+// Where a window's graph, its MSA arrays and a workgroup's scratch slot lie in
+// the batch's slab (the device side of GWAMD_POA_SLAB_ARRAYS, poa_plan.hpp):
+// the only functions that spell a per-window or per-slot stride.  BuffersT is
+// Buffers by value or the kernel's own kernarg copy (ka->b, address space 4).
+struct SlabOffset { size_t node, edge; }; // first node and edge slot of window (or slot) i
+__device__ __forceinline__ SlabOffset slab_offset(int max_nodes, size_t i)
+{
+    const size_t mn = size_t(max_nodes);
+    return {i * mn, i * mn * kMaxEdges};
+}
+
+template <typename SizeT, typename BuffersT>
+__device__ __forceinline__ WinGraph<SizeT> bind_window(const BuffersT& b, int max_nodes, size_t w)
+{
+    const SlabOffset o = slab_offset(max_nodes, w);
+    WinGraph<SizeT> g;
+    g.base      = b.base + o.node;
+    g.in_cnt    = b.in_cnt + o.node;
+    g.out_cnt   = b.out_cnt + o.node;
+    g.aln_cnt   = b.aln_cnt + o.node;
+    g.cov       = b.node_cov + o.node;
+    g.in_w      = b.in_w + o.edge;
+    g.in_e      = static_cast<SizeT*>(b.in_e) + o.edge;
+    g.out_e     = static_cast<SizeT*>(b.out_e) + o.edge;
+    g.aln       = static_cast<SizeT*>(b.aln) + o.node * kMaxAlignments;
+    g.sorted    = static_cast<SizeT*>(b.sorted) + o.node;
+    g.pos       = static_cast<SizeT*>(b.pos) + o.node;
+    g.max_nodes = max_nodes;
+    return g;
+}
+
+// MSA arrays of a window (null pointers in a consensus-only kernel)
+template <typename SizeT>
+struct WinMsa { uint16_t *ecov, *ecov_cnt; SizeT* seq_begin; };
+template <typename SizeT, bool MSA, typename BuffersT, typename DimsT>
+__device__ __forceinline__ WinMsa<SizeT> bind_window_msa(const BuffersT& b, const DimsT& d, size_t w)
+{
+    if (!MSA)
+        return {nullptr, nullptr, nullptr};
+    const SlabOffset o = slab_offset(d.max_nodes, w);
+    return {b.edge_cov + o.edge * d.max_seqs, b.edge_cov_cnt + o.edge,
+            static_cast<SizeT*>(b.seq_begin) + w * d.max_seqs};
+}
+
+// Scratch of a workgroup ("slot", Buffers): the alignment path and the
+// consensus scores / predecessors (cpred: also the racon stack, 4 per node)
+template <typename SizeT>
+struct SlotScratch { SizeT *ag, *ar; int32_t* cscore; SizeT* cpred; };
+template <typename SizeT, typename BuffersT, typename DimsT>
+__device__ __forceinline__ SlotScratch<SizeT> bind_slot(const BuffersT& b, const DimsT& d, size_t slot)
+{
+    const size_t node = slab_offset(d.max_nodes, slot).node;
+    return {static_cast<SizeT*>(b.ag) + slot * d.aln_cap, static_cast<SizeT*>(b.ar) + slot * d.aln_cap,
+            b.cscore + node, static_cast<SizeT*>(b.cpred) + node * 4};
+}
+
 __device__ __forceinline__ uint64_t now_ticks()
 {
     return __builtin_amdgcn_s_memrealtime();

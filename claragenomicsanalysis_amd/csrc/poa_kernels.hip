@@ -43,29 +43,13 @@ __global__ void __launch_bounds__(kWave) poa_window_kernel(Buffers b, Dims d, Sc
         return;
     const int lane = threadIdx.x;
 
-    const size_t mn = size_t(d.max_nodes);
-    WinGraph<SizeT> g;
-    g.base      = b.base + w * mn;
-    g.in_cnt    = b.in_cnt + w * mn;
-    g.out_cnt   = b.out_cnt + w * mn;
-    g.aln_cnt   = b.aln_cnt + w * mn;
-    g.cov       = b.node_cov + w * mn;
-    g.in_w      = b.in_w + w * mn * kMaxEdges;
-    g.in_e      = static_cast<SizeT*>(b.in_e) + w * mn * kMaxEdges;
-    g.out_e     = static_cast<SizeT*>(b.out_e) + w * mn * kMaxEdges;
-    g.aln       = static_cast<SizeT*>(b.aln) + w * mn * kMaxAlignments;
-    g.sorted    = static_cast<SizeT*>(b.sorted) + w * mn;
-    g.pos       = static_cast<SizeT*>(b.pos) + w * mn;
-    g.max_nodes = d.max_nodes;
-
-    SizeT* ag        = static_cast<SizeT*>(b.ag) + size_t(w) * d.aln_cap;
-    SizeT* ar        = static_cast<SizeT*>(b.ar) + size_t(w) * d.aln_cap;
-    ScoreT* S        = static_cast<ScoreT*>(b.scores) + size_t(w) * d.score_rows * size_t(d.score_stride);
-    int32_t* cscore  = b.cscore + w * mn;
-    SizeT* cpred     = static_cast<SizeT*>(b.cpred) + w * mn * 4; // also the racon stack
-    uint16_t* ecov   = MSA ? b.edge_cov + w * mn * kMaxEdges * d.max_seqs : nullptr;
-    uint16_t* ecovc  = MSA ? b.edge_cov_cnt + w * mn * kMaxEdges : nullptr;
-    SizeT* seq_begin = MSA ? static_cast<SizeT*>(b.seq_begin) + size_t(w) * d.max_seqs : nullptr;
+    const WinGraph<SizeT> g     = bind_window<SizeT>(b, d.max_nodes, size_t(w));
+    const SlotScratch<SizeT> sl = bind_slot<SizeT>(b, d, size_t(w)); // one slot per window here
+    const WinMsa<SizeT> msa     = bind_window_msa<SizeT, MSA>(b, d, size_t(w));
+    ScoreT* S       = static_cast<ScoreT*>(b.scores) + size_t(w) * d.score_rows * size_t(d.score_stride);
+    SizeT *ag = sl.ag, *ar = sl.ar, *cpred = sl.cpred, *seq_begin = msa.seq_begin;
+    int32_t* cscore = sl.cscore;
+    uint16_t *ecov = msa.ecov, *ecovc = msa.ecov_cnt;
 
     PhaseTimer ph;
     const WindowDesc wd = b.windows[w];
@@ -892,16 +876,7 @@ __device__ int traceback_codes(WinGraph<SizeT> g, const RowProg& P, int V, int L
     int n = 0, loops = 0;
     const int bound = L + V + 2;
     int eg = 0, er = 0; // lane (n & 63) holds pair n until it is stored
-    auto flush = [&](int upto) {
-        // pairs [upto & ~63, upto) are held by lanes 0 .. (upto-1) & 63
-        const int base = (upto - 1) & ~(kWave - 1);
-        const int k    = base + lane;
-        if (k < upto && k < aln_cap)
-        {
-            ag[k] = SizeT(eg > 0 ? int(g.sorted[eg - 1]) : -1);
-            ar[k] = SizeT(er);
-        }
-    };
+    auto flush = [&](int upto) { tb_flush<SizeT>(g.sorted, ag, ar, aln_cap, upto, lane, eg, er); };
     auto load_tile = [&](int ii, int cj) {
         ti0 = max(0, ii - (kTileRows - 1));
         tj0 = max(0, cj - (kTileCols - 16)) & ~15;
@@ -999,28 +974,7 @@ __device__ int traceback_codes(WinGraph<SizeT> g, const RowProg& P, int V, int L
                 walk_window_ranked<0>(wpk0, wpk1, G, ci, cj, cn, cl, bound, lane, eg, er,
                                       tile + kTileRows * kTileCols, flush);
             else
-            while (true)
-            {
-                const int idx     = G.index(ci, cj);
-                const uint32_t nx = uint32_t(idx < kWave ? __builtin_amdgcn_readlane(int(wpk0), idx)
-                                                         : __builtin_amdgcn_readlane(int(wpk1), idx - kWave));
-                if (nx == kSlow)
-                    break;
-                const int pi = int(nx >> 16), pj = int(nx & 0xffffu);
-                cl++;
-                if (lane == (cn & (kWave - 1)))
-                {
-                    eg = ci == pi ? -1 : ci;
-                    er = cj == pj ? -1 : cj - 1;
-                }
-                cn++;
-                if ((cn & (kWave - 1)) == 0)
-                    flush(cn);
-                ci = pi;
-                cj = pj;
-                if ((ci == 0 && cj == 0) || cl >= bound || ci < 1 || G.index(ci, cj) < 0)
-                    break;
-            }
+                walk_window_scalar<0>(wpk0, wpk1, G, ci, cj, cn, cl, bound, lane, eg, er, nullptr, flush);
             if (cl != loops)
             {
                 G.follow(ci, cj);
@@ -1131,34 +1085,18 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
     for (int idx = blockIdx.x; idx < b.num_windows;)
     {
     const int w     = b.order ? b.order[idx] : idx;
-    const size_t mn = size_t(d.max_nodes);
-    WinGraph<SizeT> g;
-    g.base      = b.base + w * mn;
-    g.in_cnt    = b.in_cnt + w * mn;
-    g.out_cnt   = b.out_cnt + w * mn;
-    g.aln_cnt   = b.aln_cnt + w * mn;
-    g.cov       = b.node_cov + w * mn;
-    g.in_w      = b.in_w + w * mn * kMaxEdges;
-    g.in_e      = static_cast<SizeT*>(b.in_e) + w * mn * kMaxEdges;
-    g.out_e     = static_cast<SizeT*>(b.out_e) + w * mn * kMaxEdges;
-    g.aln       = static_cast<SizeT*>(b.aln) + w * mn * kMaxAlignments;
-    g.sorted    = static_cast<SizeT*>(b.sorted) + w * mn;
-    g.pos       = static_cast<SizeT*>(b.pos) + w * mn;
-    g.max_nodes = d.max_nodes;
-
-    SizeT* ag        = static_cast<SizeT*>(b.ag) + slot * d.aln_cap;
-    SizeT* ar        = static_cast<SizeT*>(b.ar) + slot * d.aln_cap;
+    const WinGraph<SizeT> g     = bind_window<SizeT>(b, d.max_nodes, size_t(w));
+    const SlotScratch<SizeT> sl = bind_slot<SizeT>(b, d, slot);
+    const WinMsa<SizeT> msa     = bind_window_msa<SizeT, MSA>(b, d, size_t(w));
+    SizeT *ag = sl.ag, *ar = sl.ar, *cpred = sl.cpred, *seq_begin = msa.seq_begin;
+    int32_t* cscore = sl.cscore;
+    uint16_t *ecov = msa.ecov, *ecovc = msa.ecov_cnt;
     RowT* spill      = static_cast<RowT*>(b.scores) + slot * d.score_rows * size_t(rstride);
     uint8_t* codes   = b.codes + slot * size_t(d.aux_stride);
     uint32_t* rec    = reinterpret_cast<uint32_t*>(lds + d.lds_rec_off);
     uint16_t* xl     = reinterpret_cast<uint16_t*>(lds + d.lds_xl_off);
     RowT* carry      = reinterpret_cast<RowT*>(codes + d.aux_carry_off);
     RowProg P{rec, xl, d.lds_ring_rows - 1};
-    int32_t* cscore  = b.cscore + slot * mn;
-    SizeT* cpred     = static_cast<SizeT*>(b.cpred) + slot * mn * 4;
-    uint16_t* ecov   = MSA ? b.edge_cov + w * mn * kMaxEdges * d.max_seqs : nullptr;
-    uint16_t* ecovc  = MSA ? b.edge_cov_cnt + w * mn * kMaxEdges : nullptr;
-    SizeT* seq_begin = MSA ? static_cast<SizeT*>(b.seq_begin) + size_t(w) * d.max_seqs : nullptr;
 
     PhaseTimer ph;
     FwdProf fp;
@@ -1382,6 +1320,7 @@ __global__ void __launch_bounds__(kWave * NW, W ? (NW >= 8 ? 2 : 1) : (NW >= 4 ?
                 }
                 if (code == 2 && !order_kahn)
                 {
+                    const size_t mn    = size_t(d.max_nodes); // cpred: four arrays of max_nodes
                     WinGraph<SizeT> gk = g;
                     gk.sorted          = cpred + mn;
                     gk.pos             = cpred + 2 * mn;

@@ -219,17 +219,13 @@ template <int NW, int kInst = 0>
 __device__ __noinline__ int order_splice(LdsKernelArgsPtr ka_, int w_, int V_, int L_, GWAMD_LDS uint8_t* lds)
 {
     using SizeT               = int16_t;
-    const uint64_t kav        = uint64_t(uintptr_t(ka_));
-    const LdsKernelArgsPtr ka = (LdsKernelArgsPtr)(uintptr_t(
-        (uint64_t(uint32_t(uniform(int(uint32_t(kav >> 32))))) << 32) | uint32_t(uniform(int(uint32_t(kav))))));
-    const size_t w        = size_t(uniform(w_));
-    const size_t mn       = size_t(ka->d.max_nodes);
-    const int max_seq_len = ka->d.max_seq_len;
-    lds                   = (GWAMD_LDS uint8_t*)(uintptr_t)(uint32_t)uniform(int((uint32_t)(uintptr_t)lds));
-    const AddScratch X =
-        lds_add_scratch(lds + int(lds_read_bytes(max_seq_len)), max_seq_len, int(mn), true, nullptr);
-    return order_splice_core<SizeT>(glb_of(static_cast<SizeT*>(ka->b.sorted) + w * mn),
-                                    glb_of(static_cast<SizeT*>(ka->b.pos) + w * mn), uniform(V_), uniform(L_), X.curr,
+    const LdsKernelArgsPtr ka = uniform_kernarg(ka_);
+    const int mn              = ka->d.max_nodes;
+    const int max_seq_len     = ka->d.max_seq_len;
+    lds                       = uniform_lds(lds);
+    const WinGraph<SizeT> g   = bind_window<SizeT>(ka->b, mn, size_t(uniform(w_)));
+    const AddScratch X = lds_add_scratch(lds + int(lds_read_bytes(max_seq_len)), max_seq_len, mn, true, nullptr);
+    return order_splice_core<SizeT>(glb_of(g.sorted), glb_of(g.pos), uniform(V_), uniform(L_), X.curr,
                                     X.kind, X.gid, X.owner, (GWAMD_LDS uint16_t*)(lds + ka->d.lds_rec_off), X.sh,
                                     int(threadIdx.x), NW * kWave);
 }

@@ -315,21 +315,10 @@ template <int NW, int kInst = 0>
 __device__ __noinline__ void build_row_program(LdsKernelArgsPtr ka_, int w_, int V_, GWAMD_LDS uint8_t* lds)
 {
     using SizeT               = int16_t;
-    const uint64_t kav        = uint64_t(uintptr_t(ka_));
-    const LdsKernelArgsPtr ka = (LdsKernelArgsPtr)(uintptr_t(
-        (uint64_t(uint32_t(uniform(int(uint32_t(kav >> 32))))) << 32) | uint32_t(uniform(int(uint32_t(kav))))));
-    const size_t w  = size_t(uniform(w_));
-    const size_t mn = size_t(ka->d.max_nodes);
-    lds             = (GWAMD_LDS uint8_t*)(uintptr_t)(uint32_t)uniform(int((uint32_t)(uintptr_t)lds));
-    WinGraph<SizeT> g{};
-    g.base      = ka->b.base + w * mn;
-    g.in_cnt    = ka->b.in_cnt + w * mn;
-    g.out_cnt   = ka->b.out_cnt + w * mn;
-    g.in_e      = static_cast<SizeT*>(ka->b.in_e) + w * mn * kMaxEdges;
-    g.sorted    = static_cast<SizeT*>(ka->b.sorted) + w * mn;
-    g.pos       = static_cast<SizeT*>(ka->b.pos) + w * mn;
-    g.max_nodes = int(mn);
-    const int xcap = ka->d.lds_xl_cap - kSinkWords;
+    const LdsKernelArgsPtr ka = uniform_kernarg(ka_);
+    lds                       = uniform_lds(lds);
+    const WinGraph<SizeT> g   = bind_window<SizeT>(ka->b, ka->d.max_nodes, size_t(uniform(w_)));
+    const int xcap            = ka->d.lds_xl_cap - kSinkWords;
     build_row_program_core<SizeT>(g, uniform(V_), (uint32_t*)(lds + ka->d.lds_rec_off),
                                   (uint16_t*)(lds + ka->d.lds_xl_off), xcap, ka->d.lds_ring_rows, int(threadIdx.x),
                                   NW * kWave, lds + ka->d.lds_ring_off,

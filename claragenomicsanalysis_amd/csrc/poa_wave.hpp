@@ -989,6 +989,18 @@ __device__ __forceinline__ LdsKernelArgsPtr lds_kernel_args()
 {
     return (LdsKernelArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
 }
+// (a routine kept out of line receives them in vector registers: these give
+// the wave-uniform kernarg address and LDS base back as scalars)
+__device__ __forceinline__ LdsKernelArgsPtr uniform_kernarg(LdsKernelArgsPtr ka_)
+{
+    const uint64_t kav = uint64_t(uintptr_t(ka_));
+    return (LdsKernelArgsPtr)(uintptr_t((uint64_t(uint32_t(uniform(int(uint32_t(kav >> 32))))) << 32) |
+                                        uint32_t(uniform(int(uint32_t(kav))))));
+}
+__device__ __forceinline__ GWAMD_LDS uint8_t* uniform_lds(GWAMD_LDS uint8_t* lds)
+{
+    return (GWAMD_LDS uint8_t*)(uintptr_t)(uint32_t)uniform(int((uint32_t)(uintptr_t)lds));
+}
 
 // The graph update of the LDS kernel on every wave of its workgroup:
 // add_alignment_parallel_batched with wv = this wave, nwv = NW, on the scratch
@@ -1016,42 +1028,29 @@ __device__ __noinline__ int add_alignment_waves(LdsKernelArgsPtr ka_, int w_, in
                                                 int node_count, int alen, int L, GWAMD_LDS uint8_t* lds)
 {
     using SizeT = int16_t;
-    // (arguments arrive in vector registers; the address is the same in every lane)
-    const uint64_t kav        = uint64_t(uintptr_t(ka_));
-    const LdsKernelArgsPtr ka = (LdsKernelArgsPtr)(uintptr_t(
-        (uint64_t(uint32_t(uniform(int(uint32_t(kav >> 32))))) << 32) | uint32_t(uniform(int(uint32_t(kav))))));
+    const LdsKernelArgsPtr ka = uniform_kernarg(ka_);
     const int tid     = int(threadIdx.x);
     const int lane    = tid & (kWave - 1);
     const int wv      = NW > 1 ? uniform(tid / kWave) : 0;
     const size_t w    = size_t(uniform(w_));
     const size_t slot = size_t(uniform(slot_));
     const int s       = uniform(s_);
-    const size_t mn   = size_t(ka->d.max_nodes);
+    const int mn      = ka->d.max_nodes;
     const int max_seq_len = ka->d.max_seq_len;
     const int max_seqs    = ka->d.max_seqs;
     const int64_t woff    = (int64_t(uniform(int(wts_off >> 32))) << 32) | uint32_t(uniform(int(uint32_t(wts_off))));
-    WinGraph<SizeT> g;
-    g.base      = ka->b.base + w * mn;
-    g.in_cnt    = ka->b.in_cnt + w * mn;
-    g.out_cnt   = ka->b.out_cnt + w * mn;
-    g.aln_cnt   = ka->b.aln_cnt + w * mn;
-    g.cov       = ka->b.node_cov + w * mn;
-    g.in_w      = ka->b.in_w + w * mn * kMaxEdges;
-    g.in_e      = static_cast<SizeT*>(ka->b.in_e) + w * mn * kMaxEdges;
-    g.out_e     = static_cast<SizeT*>(ka->b.out_e) + w * mn * kMaxEdges;
-    g.aln       = static_cast<SizeT*>(ka->b.aln) + w * mn * kMaxAlignments;
-    g.sorted    = nullptr;
-    g.pos       = nullptr;
-    g.max_nodes = int(mn);
-    const SizeT* ag  = glb(static_cast<const SizeT*>(ka->b.ag) + slot * ka->d.aln_cap);
-    const SizeT* ar  = glb(static_cast<const SizeT*>(ka->b.ar) + slot * ka->d.aln_cap);
+    const WinGraph<SizeT> g     = bind_window<SizeT>(ka->b, mn, w); // (sorted and pos: not used)
+    const SlotScratch<SizeT> sl = bind_slot<SizeT>(ka->b, ka->d, slot);
+    const WinMsa<SizeT> msa     = bind_window_msa<SizeT, MSA>(ka->b, ka->d, w);
+    const SizeT* ag  = glb(static_cast<const SizeT*>(sl.ag));
+    const SizeT* ar  = glb(static_cast<const SizeT*>(sl.ar));
     const int8_t* wt = glb(ka->b.wts + woff);
-    uint16_t* ecov   = MSA ? glb(ka->b.edge_cov + w * mn * kMaxEdges * max_seqs) : nullptr;
-    uint16_t* ecovc  = MSA ? glb(ka->b.edge_cov_cnt + w * mn * kMaxEdges) : nullptr;
-    SizeT* seq_begin = MSA ? glb(static_cast<SizeT*>(ka->b.seq_begin) + w * max_seqs) : nullptr;
-    lds              = (GWAMD_LDS uint8_t*)(uintptr_t)(uint32_t)uniform(int((uint32_t)(uintptr_t)lds));
+    uint16_t* ecov   = glb(msa.ecov);
+    uint16_t* ecovc  = glb(msa.ecov_cnt);
+    SizeT* seq_begin = glb(msa.seq_begin);
+    lds              = uniform_lds(lds);
     const AddScratch X =
-        lds_add_scratch(lds + int(lds_read_bytes(max_seq_len)), max_seq_len, int(mn), true, nullptr);
+        lds_add_scratch(lds + int(lds_read_bytes(max_seq_len)), max_seq_len, mn, true, nullptr);
     int nc       = uniform(node_count);
     const int rc = add_alignment_parallel_batched<SizeT, MSA, 4>(g, nc, ag, ar, uniform(alen), uniform(L),
                                                                  (const uint8_t*)(lds), wt, s, ecov, ecovc,
@@ -2776,6 +2775,56 @@ __device__ __forceinline__ void walk_window_ranked(uint32_t wpk0, uint32_t wpk1,
     cj             = __builtin_amdgcn_readlane(pj, last);
     cn += steps;
     cl += steps;
+}
+
+// The scalar walk of the same window, same arguments (no scratch): one cell
+// per iteration, every value wave-uniform (SGPRs).  Stops at a kSlow cell, at
+// (0, 0), at the loop bound and where the path leaves the window or goes
+// below row 1 / column kCmin.  (kCmin == 0: no column test; the LDS kernel's
+// decode_cell never gives a move to a column < 0.)
+template <int kCmin, typename Flush>
+__device__ __forceinline__ void walk_window_scalar(uint32_t wpk0, uint32_t wpk1, const TbWin& G, int& ci, int& cj,
+                                                   int& cn, int& cl, int bound, int lane, int& eg, int& er,
+                                                   GWAMD_LDS uint8_t*, Flush&& flush)
+{
+    constexpr uint32_t kSlow = 0xffffffffu;
+    while (true)
+    {
+        const int idx     = G.index(ci, cj);
+        const uint32_t nx = uint32_t(idx < kWave ? __builtin_amdgcn_readlane(int(wpk0), idx)
+                                                 : __builtin_amdgcn_readlane(int(wpk1), idx - kWave));
+        if (nx == kSlow)
+            break;
+        const int pi = int(nx >> 16), pj = int(nx & 0xffffu);
+        cl++;
+        if (lane == (cn & (kWave - 1)))
+        {
+            eg = ci == pi ? -1 : ci;
+            er = cj == pj ? -1 : cj - 1;
+        }
+        cn++;
+        if ((cn & (kWave - 1)) == 0)
+            flush(cn);
+        ci = pi;
+        cj = pj;
+        if ((ci == 0 && cj == 0) || cl >= bound || ci < 1 || (kCmin > 0 && cj < kCmin) || G.index(ci, cj) < 0)
+            break;
+    }
+}
+
+// Stores the traceback pairs [(upto - 1) & ~63, upto), held by lanes 0 ..
+// (upto - 1) & 63: eg a graph row (a node id at the store; 0 or less: none).
+template <typename SizeT, typename SortedP, typename PairP>
+__device__ __forceinline__ void tb_flush(SortedP sorted, PairP ag, PairP ar, int aln_cap, int upto, int lane, int eg,
+                                         int er)
+{
+    const int base = (upto - 1) & ~(kWave - 1);
+    const int k    = base + lane;
+    if (k < upto && k < aln_cap)
+    {
+        ag[k] = SizeT(eg > 0 ? int(sorted[eg - 1]) : -1);
+        ar[k] = SizeT(er);
+    }
 }
 
 } // namespace poa

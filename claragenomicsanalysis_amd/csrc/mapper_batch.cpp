@@ -9,15 +9,19 @@
 #include <claraparabricks/genomeworks/cudamapper/matcher.hpp>
 #include <claraparabricks/genomeworks/cudamapper/overlapper_triggered.hpp>
 
-#include "../../include/gwamd_cudamapper.h"
 #include "allocator_handle.hpp"
-#include "mapper_common.hpp"
+#include "mapper_capi.hpp"
 
 #include <cstddef>
 #include <cstring>
 #include <vector>
 
 namespace gm = gwamd::mapper;
+using gm::allocator_is_null;
+using gm::check_read_lengths;
+using gm::clear_overlap_outputs;
+using gm::guarded_map;
+using gm::hand_over;
 
 namespace
 {
@@ -38,18 +42,6 @@ void check_index_arguments(int64_t num_reads, int64_t first_read_id, int64_t pas
         throw std::invalid_argument("read range [" + std::to_string(first_read_id) + ", " +
                                     std::to_string(past_the_last_read_id) + ") is not within the " +
                                     std::to_string(num_reads) + " reads");
-}
-
-void check_read_lengths(const int64_t* offsets, int64_t n)
-{
-    for (int64_t i = 0; i < n; i++)
-    {
-        if (offsets[i] < 0 || offsets[i] > offsets[i + 1])
-            throw std::invalid_argument("read offsets must be non-decreasing");
-        // a position and the direction share 32 bits of the sort payload
-        if (offsets[i + 1] - offsets[i] >= (int64_t(1) << 31))
-            throw std::invalid_argument("reads must be shorter than 2^31 bases");
-    }
 }
 
 gm::OverlapParams check_overlap_parameters(int64_t min_residues, int64_t min_overlap_len,
@@ -335,26 +327,6 @@ static_assert(sizeof(gwamd_anchor) == sizeof(gm::AnchorRecord), "gwamd_anchor mu
 namespace
 {
 
-template <typename F>
-int32_t guarded_map(F&& f)
-{
-    try
-    {
-        gwamd::host::last_error().clear();
-        return f();
-    }
-    catch (const std::invalid_argument& e)
-    {
-        gwamd::host::last_error() = e.what();
-        return GWAMD_E_INVALID_ARGUMENT;
-    }
-    catch (const std::exception& e)
-    {
-        gwamd::host::last_error() = e.what();
-        return std::string(e.what()).rfind("HIP error", 0) == 0 ? GWAMD_E_HIP : GWAMD_E_RUNTIME;
-    }
-}
-
 int32_t index_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t first_read_id,
                      int32_t past_the_last_read_id, int32_t kmer_size, int32_t window_size,
                      int32_t hash_representations, double filtering_parameter, int32_t device_id,
@@ -429,29 +401,6 @@ static_assert(sizeof(gwamd_overlap) == sizeof(gm::OverlapRecord) && sizeof(gwamd
                   offsetof(gwamd_overlap, overlap_complete) == offsetof(gm::OverlapRecord, overlap_complete),
               "gwamd_overlap must match cudamapper::Overlap");
 
-void clear_overlap_outputs(gwamd_overlap** overlaps, int64_t* num_overlaps, int64_t* num_anchors = nullptr)
-{
-    if (overlaps)
-        *overlaps = nullptr;
-    if (num_overlaps)
-        *num_overlaps = 0;
-    if (num_anchors)
-        *num_anchors = 0;
-}
-
-template <typename Record>
-void hand_over(const std::vector<Record>& records, gwamd_overlap** overlaps, int64_t* num_overlaps)
-{
-    static_assert(sizeof(Record) == sizeof(gwamd_overlap), "records are copied as bytes");
-    if (records.empty())
-        return;
-    std::unique_ptr<gwamd_overlap[]> h(new gwamd_overlap[records.size()]);
-    std::memcpy(static_cast<void*>(h.get()), static_cast<const void*>(records.data()),
-                records.size() * sizeof(gwamd_overlap));
-    *num_overlaps = int64_t(records.size());
-    *overlaps     = h.release();
-}
-
 int32_t overlaps_of_anchors(const gwamd_anchor* anchors, int64_t n, int64_t min_residues, int64_t min_overlap_len,
                             int64_t min_bases_per_residue, float min_overlap_fraction, int32_t device_id,
                             const gm::Budget& budget, gwamd_overlap** overlaps, int64_t* num_overlaps)
@@ -508,13 +457,6 @@ int32_t match_overlaps(const gwamd_index* query_index, const gwamd_index* target
             *num_anchors = int64_t(d.size());
         return int32_t(0);
     });
-}
-
-int32_t allocator_is_null(gwamd_overlap** overlaps, int64_t* num_overlaps, int64_t* num_anchors = nullptr)
-{
-    clear_overlap_outputs(overlaps, num_overlaps, num_anchors);
-    gwamd::host::last_error() = "allocator is NULL";
-    return GWAMD_E_INVALID_ARGUMENT;
 }
 
 template <typename T>

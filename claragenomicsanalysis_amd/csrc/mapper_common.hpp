@@ -1,6 +1,6 @@
-// Host-side declarations shared by the minimizer index, the matcher and the
-// overlapper (mapper_index.hip, mapper_match.hip, mapper_overlap.hip,
-// mapper_batch.cpp).
+// Host-side declarations shared by the minimizer index, the matcher, the
+// overlapper and the end rescue (mapper_index.hip, mapper_match.hip, mapper_overlap.hip,
+// mapper_rescue.hip, mapper_batch.cpp, mapper_rescue_host.cpp).
 #pragma once
 
 #include "host_common.hpp"
@@ -100,6 +100,25 @@ constexpr int kOverlapTile = 2048; // anchors per workgroup of the chain-flag ke
 // 2^31 or more; the parameters are validated by the caller.
 void get_overlaps(std::vector<OverlapRecord>& out, const AnchorRecord* anchors, int64_t n, const OverlapParams& params,
                   const Budget& budget, hipStream_t stream, OverlapCounts* counts = nullptr);
+
+constexpr int kMaxRescueExtension = 128; // bytes of one window in LDS (mapper_rescue.hip)
+constexpr int kRescueRounds       = 3;   // max_rescue_rounds, overlapper.cpp:336
+constexpr int kRescueKmer         = 15;  // the kmer_size extend_overlap_by_sequence_similarity passes
+
+// The reads of one side in host memory: read i is bases[offsets[i], offsets[i + 1])
+struct ReadSet
+{
+    const char* bases      = nullptr;
+    const int64_t* offsets = nullptr; // num_reads + 1 entries
+    int64_t num_reads      = 0;
+};
+
+// Overlapper::rescue_overlap_ends on n > 0 host overlaps, in place: kRescueRounds
+// rounds of extend_overlap_by_sequence_similarity(extension, required_similarity)
+// per overlap.  Two sides with the same pointers are uploaded once.  Arguments
+// are validated by the caller: ids, positions and the extension are in range.
+void rescue_overlap_ends(OverlapRecord* overlaps, int64_t n, const ReadSet& query, const ReadSet& target,
+                         int extension, float required_similarity, const Budget& budget, hipStream_t stream);
 
 } // namespace mapper
 } // namespace gwamd

@@ -1,5 +1,5 @@
-"""Minimizer index, anchor matcher, overlapper, overlap alignment and PAF
-output of cudamapper over the C ABI (include/gwamd_cudamapper.h; reference
+"""Minimizer index, anchor matcher, overlapper, overlap-end rescue, overlap
+alignment and PAF output of cudamapper over the C ABI (include/gwamd_cudamapper.h; reference
 cudamapper/include/.../index.hpp, matcher.hpp, overlapper.hpp,
 cudamapper/src/main.cu:48-175 and cudamapper/src/cudamapper_utils.cpp:30-112).
 
@@ -7,6 +7,8 @@ Index builds the (k,w)-minimizer index of a range of reads on the GPU,
 match_anchors pairs the sketch elements of two indices that share a
 representation, and get_overlaps chains sorted anchors into Overlap records
 (match_overlaps does both without bringing the anchors to the host).
+rescue_overlap_ends pushes the ends of overlaps out towards the read ends on
+the GPU; extend_overlap_by_sequence_similarity is one round of it on the host.
 
 Overlaps are aligned with the MI355X global aligner (Hirschberg-Myers, the
 aligner create_aligner returns); a Reverse ('-') overlap aligns the query
@@ -99,6 +101,14 @@ def _declare(L):
     L.gwamd_post_process_overlaps.argtypes = [vp, i64, i32, P(vp), P(i64)]
     L.gwamd_overlaps_free.restype = None
     L.gwamd_overlaps_free.argtypes = [vp]
+    rescue_args = [C.c_char_p, vp, i32, C.c_char_p, vp, i32, vp, i64, i32, C.c_float, i32]
+    L.gwamd_rescue_overlap_ends.restype = i32
+    L.gwamd_rescue_overlap_ends.argtypes = rescue_args + [P(vp), P(i64)]
+    L.gwamd_rescue_overlap_ends_with_allocator.restype = i32
+    L.gwamd_rescue_overlap_ends_with_allocator.argtypes = rescue_args + [vp, P(vp), P(i64)]
+    L.gwamd_extend_overlap_by_sequence_similarity.restype = i32
+    L.gwamd_extend_overlap_by_sequence_similarity.argtypes = [P(Overlap), C.c_char_p, i64, C.c_char_p, i64, i32,
+                                                              C.c_float]
 
 
 def _check(rc):
@@ -290,15 +300,16 @@ def _filter_args(min_residues, min_overlap_len, min_bases_per_residue, min_overl
     return [int(min_residues), int(min_overlap_len), int(min_bases_per_residue), float(min_overlap_fraction)]
 
 
+def _copy(overlap):
+    c = Overlap.__new__(Overlap)
+    C.memmove(C.byref(c), C.byref(overlap), C.sizeof(Overlap))
+    return c
+
+
 def _take_overlaps(L, p, n):
     try:
         arr = (Overlap * n.value).from_address(p.value) if n.value else []
-        out = []
-        for o in arr:
-            c = Overlap.__new__(Overlap)
-            C.memmove(C.byref(c), C.byref(o), C.sizeof(Overlap))
-            out.append(c)
-        return out
+        return [_copy(o) for o in arr]
     finally:
         L.gwamd_overlaps_free(p)
 
@@ -358,3 +369,45 @@ def post_process_overlaps(overlaps, drop_fused_overlaps=False):
     p, n = C.c_void_p(), C.c_int64()
     _check(L.gwamd_post_process_overlaps(arr, len(overlaps), int(bool(drop_fused_overlaps)), C.byref(p), C.byref(n)))
     return _take_overlaps(L, p, n)
+
+
+def rescue_overlap_ends(overlaps, query_reads, target_reads, extension=100, required_similarity=0.9, device_id=0,
+                        allocator=None):
+    """Overlaps with their ends pushed out towards the read ends
+    (Overlapper::rescue_overlap_ends, overlapper.cpp:295-365) on the GPU, one
+    wave per overlap: three rounds of extend_overlap_by_sequence_similarity, a
+    Reverse overlap against the reverse complement of its target.
+
+    query_reads / target_reads: sequences indexed by the overlaps' read ids;
+    one object given for both is uploaded once.  Unlike the reference, which
+    runs every round with 100 and 0.9 whatever it is given, extension (0..128)
+    and required_similarity are honoured.  Returns a new list of Overlap.
+    ValueError for a read id or a position beyond its read, a strand other
+    than '+' and '-', an extension out of range and a NaN similarity."""
+    L = load_library()
+    qb, qo = _pack(query_reads)
+    tb, to = (qb, qo) if target_reads is query_reads else _pack(target_reads)
+    arr = _overlap_array(overlaps)
+    p, n = C.c_void_p(), C.c_int64()
+    args = [qb, qo, len(query_reads), tb, to, len(target_reads), arr, len(overlaps), int(extension),
+            float(required_similarity), int(device_id)]
+    if allocator is not None:
+        _check(L.gwamd_rescue_overlap_ends_with_allocator(*args, allocator._handle, C.byref(p), C.byref(n)))
+    else:
+        _check(L.gwamd_rescue_overlap_ends(*args, C.byref(p), C.byref(n)))
+    return _take_overlaps(L, p, n)
+
+
+def extend_overlap_by_sequence_similarity(overlap, query, target, extension, required_similarity):
+    """One round of end rescue on one overlap, on the host
+    (details::overlapper::extend_overlap_by_sequence_similarity,
+    overlapper.cpp:254-293): a copy of the overlap with each end moved out by
+    min(extension, room on both reads) bases where the windows there are at
+    least required_similarity similar.  The strand is not looked at."""
+    L = load_library()
+    o = _copy(overlap if isinstance(overlap, Overlap) else Overlap(*overlap))
+    q = query.encode() if isinstance(query, str) else bytes(query)
+    t = target.encode() if isinstance(target, str) else bytes(target)
+    _check(L.gwamd_extend_overlap_by_sequence_similarity(C.byref(o), q, len(q), t, len(t), int(extension),
+                                                         float(required_similarity)))
+    return o

@@ -1,10 +1,18 @@
 // Overlapper of cudamapper on the MI355X (reference
 // cudamapper/include/claraparabricks/genomeworks/cudamapper/overlapper.hpp:60-107).
-// get_overlaps and post_process_overlaps are provided; rescue_overlap_ends is
-// not, and filter_overlaps is declared but never defined in the reference.
+// get_overlaps, post_process_overlaps, rescue_overlap_ends and
+// details::overlapper::extend_overlap_by_sequence_similarity are provided;
+// filter_overlaps is declared but never defined in the reference.
+//
+// One divergence in the rescue: the reference complements a Reverse overlap's
+// target through a 26-entry table indexed by (byte - 'A') (overlapper.cpp:94-109),
+// which is undefined for a byte outside 'A'..'Z'; here such a byte is left as
+// it is, like every letter other than A, C, G and T.
 #pragma once
 
 #include <claraparabricks/genomeworks/cudamapper/types.hpp>
+#include <claraparabricks/genomeworks/io/fasta_parser.hpp>
+#include <claraparabricks/genomeworks/types.hpp>
 #include <claraparabricks/genomeworks/utils/device_buffer.hpp>
 
 #include <cstdint>
@@ -16,6 +24,27 @@ namespace genomeworks
 {
 namespace cudamapper
 {
+
+namespace details
+{
+namespace overlapper
+{
+
+/// One round of end rescue on the host (overlapper.cpp:254-293).  The head
+/// window is the min(query start, target start, extension) bases before the
+/// overlap on both reads, the tail window the min(extension, bases left on
+/// either read) after it.  An end moves out by its whole window when the
+/// windows' similarity is at least required_similarity, both float32.  The
+/// similarity is the multiset Jaccard index of the windows' substrings
+/// s[i, min(L, 2i + 15)), i = 0 .. L - 15, as the reference cuts them
+/// (cudamapper_utils.cpp:114-170); a window shorter than 15 is one string, so
+/// two empty windows are similar.  The positions must lie within the sequences.
+void extend_overlap_by_sequence_similarity(Overlap& overlap, gw_string_view_t& query_sequence,
+                                           gw_string_view_t& target_sequence, std::int32_t extension,
+                                           float required_similarity);
+
+} // namespace overlapper
+} // namespace details
 
 class Overlapper
 {
@@ -39,6 +68,18 @@ public:
     /// or short beside the overlaps); drop_fused_overlaps removes the overlaps
     /// that went into a fusion.
     static void post_process_overlaps(std::vector<Overlap>& overlaps, bool drop_fused_overlaps = false);
+
+    /// Pushes the ends of every overlap out towards the read ends, in place and
+    /// on the GPU (the current device): three rounds of
+    /// extend_overlap_by_sequence_similarity per overlap, a Reverse overlap
+    /// against the reverse complement of its target.  As in the reference
+    /// (overlapper.cpp:345) every round runs with an extension of 100 and a
+    /// required similarity of 0.9f: the two arguments are ignored.
+    /// Throws std::invalid_argument for a read id beyond its parser, a position
+    /// beyond its read or a strand that is neither Forward nor Reverse.
+    static void rescue_overlap_ends(std::vector<Overlap>& overlaps, const io::FastaParser& query_parser,
+                                    const io::FastaParser& target_parser, std::int32_t extension,
+                                    float required_similarity);
 };
 
 } // namespace cudamapper

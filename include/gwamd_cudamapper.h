@@ -1,6 +1,6 @@
 /*
  * gwamd_cudamapper.h -- C ABI of cudamapper's minimizer index, anchor matcher,
- * overlapper and overlap-alignment caller (libgwamd.so).
+ * overlapper, overlap-end rescue and overlap-alignment caller (libgwamd.so).
  *
  * The reference aligns cudamapper overlaps inside its cudamapper executable
  * (cudamapper/src/main.cu:48-175: run_alignment_batch / align_overlaps) and
@@ -23,6 +23,12 @@
  *   gwamd_post_process_overlaps
  *                          Overlapper::post_process_overlaps(overlaps,
  *                          drop_fused_overlaps)                            overlapper.hpp:93
+ *   gwamd_rescue_overlap_ends
+ *                          Overlapper::rescue_overlap_ends(overlaps, query_parser,
+ *                          target_parser, extension, required_similarity)  overlapper.hpp:95-106
+ *   gwamd_extend_overlap_by_sequence_similarity
+ *                          details::overlapper::extend_overlap_by_sequence_similarity(
+ *                          overlap, query, target, extension, required_similarity) overlapper.hpp:35-47
  *
  * Reads are passed as one byte array per side with n+1 offsets (read i is
  * bases[offsets[i], offsets[i+1])); names as NUL-separated strings with n+1
@@ -210,6 +216,56 @@ int32_t gwamd_match_overlaps_with_allocator(const gwamd_index* query_index, cons
 int32_t gwamd_post_process_overlaps(const gwamd_overlap* in, int64_t n, int32_t drop_fused_overlaps,
                                     gwamd_overlap** out, int64_t* num_out);
 void gwamd_overlaps_free(gwamd_overlap* overlaps);
+
+/* ---- overlap-end rescue ---------------------------------------------------------
+ *
+ * Overlapper::rescue_overlap_ends (overlapper.cpp:295-365) on the GPU, one
+ * wave per overlap: three rounds of extend_overlap_by_sequence_similarity.
+ * A round looks at the h = min(query_start, target_start, extension) bases
+ * before the overlap on both reads and at the t = min(extension, bases left on
+ * the query, bases left on the target) bases after it, and moves an end out by
+ * its whole window when the two windows' similarity is at least
+ * required_similarity (float32 quotient, float32 threshold).  The similarity
+ * is sequence_jaccard_similarity(a, b, 15, 1) as the reference computes it
+ * (cudamapper_utils.cpp:114-170): shared / (|A| + |B| - shared) over the
+ * multisets of substrings s[i, min(L, 2i + 15)), i = 0 .. L - 15 (substr is
+ * given i + 15 as its count), or over the whole windows when L < 15, so two
+ * empty windows are similar.  A Reverse overlap is rescued against the
+ * reverse complement of its target as the reference makes it
+ * (overlapper.cpp:94-109): A<->T and C<->G, every other letter kept, the
+ * middle base of a target of odd length not complemented; a byte outside
+ * 'A'..'Z', undefined behaviour there, is kept too.  Read ids, strand,
+ * num_residues and overlap_complete come back unchanged.
+ *
+ * Unlike the reference's C++ entry point, which runs every round with 100 and
+ * 0.9f whatever it is given, these honour extension and required_similarity.
+ * GWAMD_E_INVALID_ARGUMENT, before any device call: a NULL array with a
+ * positive count, a negative count, offsets that fall, a read of 2^31 bases or
+ * more, a read id at or beyond its side's count, start > end or end > read
+ * length on either side, a strand other than '+' and '-', extension outside
+ * 0..128, a NaN required_similarity.  n == 0 gives nothing without a device
+ * call.  Query and target arguments that are the same pointers are uploaded
+ * once. */
+
+/* The n overlaps with their ends rescued, in a host array owned by the library (gwamd_overlaps_free). */
+int32_t gwamd_rescue_overlap_ends(const char* query_bases, const int64_t* query_offsets, int32_t num_queries,
+                                  const char* target_bases, const int64_t* target_offsets, int32_t num_targets,
+                                  const gwamd_overlap* overlaps, int64_t n, int32_t extension,
+                                  float required_similarity, int32_t device_id, gwamd_overlap** out,
+                                  int64_t* num_out);
+int32_t gwamd_rescue_overlap_ends_with_allocator(const char* query_bases, const int64_t* query_offsets,
+                                                 int32_t num_queries, const char* target_bases,
+                                                 const int64_t* target_offsets, int32_t num_targets,
+                                                 const gwamd_overlap* overlaps, int64_t n, int32_t extension,
+                                                 float required_similarity, int32_t device_id,
+                                                 struct gwamd_device_allocator* allocator, gwamd_overlap** out,
+                                                 int64_t* num_out);
+/* One round on one overlap in place, on the host, with no limit on extension (a negative one is
+ * converted to unsigned, as in the reference).  The strand is not looked at: for a Reverse overlap
+ * the caller passes the reverse complement and the mirrored target positions. */
+int32_t gwamd_extend_overlap_by_sequence_similarity(gwamd_overlap* overlap, const char* query, int64_t query_len,
+                                                    const char* target, int64_t target_len, int32_t extension,
+                                                    float required_similarity);
 
 #ifdef __cplusplus
 }

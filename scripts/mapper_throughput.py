@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Throughput of the minimizer index, the anchor matcher and the overlapper on one GPU.
+"""Throughput of the minimizer index, the anchor matcher, the overlapper and the end rescue on one GPU.
 
 Builds the index of 2,000 synthetic 10 kb reads at (k,w) = (15,10), hashed,
 filtering_parameter 0.001, and matches it against itself.  The reads are
@@ -7,16 +7,23 @@ substrings of one random 2 Mb genome (10x coverage, every second one reverse
 complemented), so the reads share minimizers and the anchor count is bounded
 by the coverage.  Prints one JSON line with bases/s for the index, anchors/s
 for the matcher and for matching and chaining in one call (default overlapper
-parameters), then checks a 16-read subset against the plain-Python models
-(tests/mapper_model.py, tests/overlapper_model.py).
+parameters) and overlaps/s for the rescue of those overlaps' ends, then checks
+a 16-read subset against the plain-Python models (tests/mapper_model.py,
+tests/overlapper_model.py, tests/rescue_model.py).
 
-Each GPU step (index, match, overlap, verify) runs in a child process of its
-own under a time limit; a step that fails or runs out of time ends the run.
+Each GPU step (index, match, overlap, rescue, verify) runs in a child process
+of its own under a time limit; a step that fails or runs out of time ends the
+run.
 The timed calls are gwamd_index_create, gwamd_match_anchors (upload, kernels
 and the copy of the anchors to the host) and gwamd_match_overlaps (the same
 matching, the overlapper's kernels and the copy of the overlaps; the anchors
 stay on the device), timed with device events on the stream the library works
-on and with the host clock.
+on and with the host clock.  The rescue step times gwamd_rescue_overlap_ends
+(upload of the reads and the overlaps, one kernel, one copy back) on the
+overlaps of the overlap step, and next to it, once, the same overlaps through
+three rounds each of gwamd_extend_overlap_by_sequence_similarity on one host
+thread (the loop a caller without the kernel would write; the reverse
+complements it needs are made before the clock starts).
 
     python scripts/mapper_throughput.py [--reads 2000] [--length 10000] [--steps 5] [--warmup 2]
 """
@@ -35,7 +42,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 K, W, FILTERING = 15, 10, 0.001
-STEP_TIMEOUT = {"index": 300, "match": 300, "overlap": 300, "verify": 300}
+STEP_TIMEOUT = {"index": 300, "match": 300, "overlap": 300, "rescue": 300, "verify": 300}
+RESCUE_EXTENSION, RESCUE_SIMILARITY, RESCUE_ROUNDS = 100, 0.9, 3  # what the reference's rescue_overlap_ends runs with
 
 
 def synthetic_reads(num_reads, length, seed=1):
@@ -88,6 +96,49 @@ def create_index(L, bases, offsets, n):
     return h
 
 
+def reference_reverse_complement(read):
+    """The reverse complement the reference's rescue makes (overlapper.cpp:94-109): A<->T, C<->G,
+    the middle base of an odd length left as it is."""
+    table = np.arange(256, dtype=np.uint8)
+    table[list(b"ACGT")] = list(b"TGCA")
+    codes = np.frombuffer(read, np.uint8)
+    out = table[codes[::-1]]
+    if len(read) % 2:
+        out[len(read) // 2] = codes[len(read) // 2]
+    return out.tobytes()
+
+
+def host_rescue(L, reads, overlaps, n):
+    """The first n of the overlaps (a ctypes array) through RESCUE_ROUNDS host rounds each, on
+    this thread: the rescued array and the seconds the rounds took."""
+    from claragenomicsanalysis_amd.cudamapper import Overlap
+    out = (Overlap * max(n, 1))()
+    C.memmove(out, overlaps, C.sizeof(Overlap) * n)
+    reverse = {out[i].target_read_id: None for i in range(n) if out[i].strand == "-"}
+    for read_id in reverse:
+        reverse[read_id] = reference_reverse_complement(reads[read_id])
+    extend = L.gwamd_extend_overlap_by_sequence_similarity
+    t0 = time.perf_counter()
+    for i in range(n):
+        o = out[i]  # a view of the array's element
+        query, target = reads[o.query_read_id], reads[o.target_read_id]
+        flip = o.strand == "-"
+        if flip:
+            target = reverse[o.target_read_id]
+            o.target_start, o.target_end = len(target) - o.target_end, len(target) - o.target_start
+        for _ in range(RESCUE_ROUNDS):
+            if extend(C.byref(o), query, len(query), target, len(target), RESCUE_EXTENSION, RESCUE_SIMILARITY) != 0:
+                raise RuntimeError(L.gwamd_last_error().decode())
+        if flip:
+            o.target_start, o.target_end = len(target) - o.target_end, len(target) - o.target_start
+    return out, time.perf_counter() - t0
+
+
+def overlap_fields(o):
+    return (o.query_read_id, o.target_read_id, o.query_start, o.query_end, o.target_start, o.target_end, o.strand,
+            o.num_residues, bool(o.overlap_complete))
+
+
 def worker(args):
     import torch  # noqa: F401  (before libgwamd, so that both share one HIP runtime)
     from claragenomicsanalysis_amd import load_library
@@ -97,7 +148,9 @@ def worker(args):
     if args.worker == "verify":
         import mapper_model as model
         import overlapper_model
-        from claragenomicsanalysis_amd import Index, match_anchors, match_overlaps
+        import rescue_model
+        from claragenomicsanalysis_amd import Index, match_anchors, match_overlaps, rescue_overlap_ends
+        from claragenomicsanalysis_amd.cudamapper import _overlap_array
         subset = reads[:16]
         expected = model.Index(subset, K, W, filtering_parameter=FILTERING)
         with Index(subset, K, W, filtering_parameter=FILTERING) as idx:
@@ -109,11 +162,17 @@ def worker(args):
         want = model.match_anchors(expected, expected)
         assert [tuple(int(x) for x in a) for a in anchors] == want
         want_overlaps, counts = overlapper_model.get_overlaps(want)
-        assert [(o.query_read_id, o.target_read_id, o.query_start, o.query_end, o.target_start, o.target_end,
-                 o.strand, o.num_residues, bool(o.overlap_complete)) for o in overlaps] == want_overlaps
+        assert [overlap_fields(o) for o in overlaps] == want_overlaps
+        # the rescue on the GPU, the host rounds and the model agree on every field
+        rescued = [overlap_fields(o) for o in rescue_overlap_ends(overlaps, subset, subset)]
+        by_host, _ = host_rescue(L, subset, _overlap_array(overlaps), len(overlaps))
+        assert rescued == [overlap_fields(by_host[i]) for i in range(len(overlaps))]
+        assert rescued == rescue_model.rescue_overlap_ends(want_overlaps, subset, subset)
         print(json.dumps({"verified_reads": len(subset), "verified_elements": len(expected.representations),
                           "verified_anchors": len(want), "verified_chains": counts["chains"],
-                          "verified_overlaps": len(want_overlaps)}))
+                          "verified_overlaps": len(want_overlaps),
+                          "verified_rescued_ends": sum((a[2] != b[2]) + (a[3] != b[3])
+                                                       for a, b in zip(rescued, want_overlaps))}))
         return
     bases, offsets = pack(reads)
     timer = Timer()
@@ -152,6 +211,45 @@ def worker(args):
         wall = float(np.median([s[1] for s in samples]))
         print(json.dumps({"overlaps": n.value, "overlap_anchors": anchors.value, "overlap_event_s": round(ev, 6),
                           "overlap_wall_s": round(wall, 6), "overlap_anchors_per_s": round(anchors.value / ev, 1)}))
+    elif args.worker == "rescue":
+        from claragenomicsanalysis_amd.cudamapper import Overlap
+        h = create_index(L, bases, offsets, len(reads))
+        found, n = C.c_void_p(), C.c_int64()
+        if L.gwamd_match_overlaps(h, h, -1, 20, 50, 50, 0.9, C.byref(found), C.byref(n), None) != 0:
+            raise RuntimeError(L.gwamd_last_error().decode())
+        L.gwamd_index_free(h)
+        overlaps = (Overlap * max(n.value, 1))()
+        C.memmove(overlaps, found, C.sizeof(Overlap) * n.value)
+        L.gwamd_overlaps_free(found)
+        samples, rescued, last = [], C.c_int64(), None
+        for step in range(args.warmup + args.steps):
+            p = C.c_void_p()
+
+            def call():
+                rc = L.gwamd_rescue_overlap_ends(bases, offsets, len(reads), bases, offsets, len(reads), overlaps,
+                                                 n.value, RESCUE_EXTENSION, RESCUE_SIMILARITY, 0, C.byref(p),
+                                                 C.byref(rescued))
+                if rc != 0:
+                    raise RuntimeError(L.gwamd_last_error().decode())
+            ev, wall = timer.run(call)
+            if last:
+                L.gwamd_overlaps_free(last)
+            last = p
+            if step >= args.warmup:
+                samples.append((ev, wall))
+        ev = float(np.median([s[0] for s in samples]))
+        wall = float(np.median([s[1] for s in samples]))
+        by_host, host_s = host_rescue(L, reads, overlaps, n.value)
+        on_gpu = (Overlap * n.value).from_address(last.value) if n.value else []
+        same = all(overlap_fields(on_gpu[i]) == overlap_fields(by_host[i]) for i in range(n.value))
+        moved = sum((on_gpu[i].query_start != overlaps[i].query_start) +
+                    (on_gpu[i].query_end != overlaps[i].query_end) for i in range(n.value))
+        L.gwamd_overlaps_free(last)
+        if not same:
+            raise RuntimeError("the rescue on the GPU and the host rounds differ")
+        print(json.dumps({"rescue_overlaps": n.value, "rescue_ends_moved": moved, "rescue_event_s": round(ev, 6),
+                          "rescue_wall_s": round(wall, 6), "rescue_overlaps_per_s": round(n.value / wall, 1),
+                          "rescue_host_rounds_s": round(host_s, 6)}))
     else:
         h = create_index(L, bases, offsets, len(reads))
         samples, n = [], C.c_int64()
@@ -188,7 +286,7 @@ def main():
     result = {"metric": "mapper_throughput", "reads": args.reads, "read_length": args.length, "kmer_size": K,
               "window_size": W, "hash_representations": True, "filtering_parameter": FILTERING,
               "steps": args.steps, "warmup": args.warmup}
-    for step in ("index", "match", "overlap") + (() if args.no_verify else ("verify",)):
+    for step in ("index", "match", "overlap", "rescue") + (() if args.no_verify else ("verify",)):
         cmd = [sys.executable, os.path.abspath(__file__), "--worker", step, "--reads", str(args.reads), "--length",
                str(args.length), "--steps", str(args.steps), "--warmup", str(args.warmup)]
         try:

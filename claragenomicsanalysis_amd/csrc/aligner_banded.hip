@@ -24,10 +24,13 @@
 // emit the path 64 steps at a time.
 #include <hip/hip_runtime.h>
 
-#include "aligner_common.hpp"
-#include "aligner_plan.hpp"
+#include <climits>
 #include <type_traits>
+
+#include "aligner_backtrace.hpp"
+#include "aligner_common.hpp"
 #include "aligner_device.hpp"
+#include "aligner_plan.hpp"
 
 namespace gwamd
 {
@@ -42,51 +45,6 @@ __device__ __forceinline__ uint32_t bit_of(uint32_t m, int lane) { return __buil
 
 // (~1u) << b as the reference's GPU evaluates it (PTX shl: counts >= 32 give 0)
 __device__ __forceinline__ uint32_t shl_ptx(uint32_t x, int b) { return (b < 0 || b >= 32) ? 0u : (x << b); }
-
-// Path emission: 64 states buffered one per lane, stored 64 at a time.
-struct PathWriter
-{
-    int8_t* path;
-    int cap;
-    int pos = 0;
-    int buf = 0;
-    bool overflow = false;
-    __device__ void put(int8_t r, int lane)
-    {
-        if (lane == (pos & 63))
-            buf = r;
-        if ((pos & 63) == 63)
-            flush_full(lane);
-        ++pos;
-    }
-    __device__ void flush_full(int lane)
-    {
-        const int at = (pos & ~63) + lane;
-        if (at < cap)
-            path[at] = int8_t(buf);
-        else
-            overflow = true;
-    }
-    __device__ void finish(int lane)
-    {
-        const int at = (pos & ~63) + lane;
-        if (lane < (pos & 63))
-        {
-            if (at < cap)
-                path[at] = int8_t(buf);
-        }
-        overflow = overflow || pos > cap;
-    }
-    // n copies of r (lane-parallel), after finish()
-    __device__ void fill(int8_t r, int n, int lane)
-    {
-        for (int k = lane; k < n; k += kWave)
-            if (pos + k < cap)
-                path[pos + k] = r;
-        pos += n;
-        overflow = overflow || pos > cap;
-    }
-};
 
 // One Myers step over a chunk of up to 32 words in lanes 0..31
 // (myers_advance_block, myers_gpu.cu:95-125).  act: the chunk's lanes; hin
@@ -1015,6 +973,23 @@ __device__ __forceinline__ int dpp_from_upper(int v) // lane i <- lane i+1 (wave
     return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xf, 0xf, false);
 }
 
+// Cell (i, j) of column l on band row k (ukkonen_gpu.cu:96-133).  cmp: the
+// cell is computed (otherwise it takes its initial value); v1 / v2: the row's
+// cells of columns l-1 / l-2; lo / hi: rows k-1 / k+1 of column l-1; even:
+// the parity class of l - p.
+__device__ __forceinline__ int uk_cell(const GWAMD_LDS uint8_t* sA, const GWAMD_LDS uint8_t* sB, bool cmp, bool even,
+                                       int i, int j, int k, int l, int bw, int v1, int v2, int lo, int hi)
+{
+    constexpr int M = kUkMax;
+    const int ca    = sA[cmp ? i - 1 : 0];
+    const int cb    = sB[cmp ? j - 1 : 0];
+    const int dgv   = l < 2 ? M : v2 + (ca == cb ? 0 : 1);
+    const int left  = even ? (k - 1 < 0 ? M : lo + 1) : v1 + 1;
+    const int above = even ? v1 + 1 : (k + 1 >= bw ? M : hi + 1);
+    const int init  = i == 0 ? j : (j == 0 ? i : M);
+    return cmp ? min(dgv, min(left, above)) : init;
+}
+
 // One column of the anti-diagonal sweep for NCK live 64-row chunks; PAR is
 // the column's parity class (0: (l - p) even, 1: odd). Lane k of chunk c is
 // band row k = c * 64 + lane; its cell is (i, j) = (h - k, k + l - h) with
@@ -1050,25 +1025,8 @@ __device__ __forceinline__ void uk_column(const GWAMD_LDS uint8_t* sA, const GWA
             if (lane == kWave - 1)
                 hi = x;
         }
-        const int ii  = cmp ? i - 1 : 0;
-        const int jj  = cmp ? j - 1 : 0;
-        const int ca  = sA[ii];
-        const int cb  = sB[jj];
-        const int dgv = l < 2 ? M : V2[c] + (ca == cb ? 0 : 1);
-        int left, above;
-        if (PAR == 0)
-        {
-            left  = k - 1 < 0 ? M : lo + 1;
-            above = V1[c] + 1;
-        }
-        else
-        {
-            left  = V1[c] + 1;
-            above = k + 1 >= bw ? M : hi + 1;
-        }
-        const int init = i == 0 ? j : (j == 0 ? i : M);
-        const int v    = cmp ? min(dgv, min(left, above)) : init;
-        V0[c]          = int(int16_t(v));
+        const int v = uk_cell(sA, sB, cmp, PAR == 0, i, j, k, l, bw, V1[c], V2[c], lo, hi);
+        V0[c]       = int(int16_t(v));
         if (c + 1 < NCK || k < bw)
             Sl[k] = int16_t(v);
     }
@@ -1128,6 +1086,95 @@ __device__ void uk_sweep(const GWAMD_LDS uint8_t* sA, const GWAMD_LDS uint8_t* s
     }
     if (l < cols)
         uk_column<NCK, 0>(sA, sB, S + size_t(bw) * l, l, p, bw, lane, lo_lim, hi_lim, V1, V2);
+}
+
+// One pair as both Ukkonen kernels see it: A (m - 1 letters, along i) is the
+// shorter sequence and B (n - 1, along j) the longer one; when that swaps
+// query and target the two indel codes are exchanged.  The band has bw rows
+// k = (j - i + p) / 2 and cols anti-diagonal columns l = i + j.
+struct UkPair
+{
+    const char *A, *B;
+    int m, n, p, bw, cols;
+    int8_t ins, del;
+};
+__device__ __forceinline__ UkPair uk_pair(const Args& a, int idx)
+{
+    const int Q    = uni(a.lens[2 * idx]);
+    const int T    = uni(a.lens[2 * idx + 1]);
+    const char* qs = a.seqs + size_t(2 * idx) * a.stride;
+    const char* ts = a.seqs + size_t(2 * idx + 1) * a.stride;
+    const bool swp = Q > T;
+    const int m = (swp ? T : Q) + 1, n = (swp ? Q : T) + 1, p = a.ukkonen_p;
+    return {swp ? ts : qs, swp ? qs : ts, m, n, p, (1 + n - m + 2 * p + 1) / 2, n + m,
+            swp ? kDeletion : kInsertion, swp ? kInsertion : kDeletion};
+}
+// the pair's sequences into LDS, by nt threads
+__device__ __forceinline__ void uk_copy_seqs(const UkPair& u, GWAMD_LDS uint8_t* sA, GWAMD_LDS uint8_t* sB, int tid,
+                                             int nt)
+{
+    for (int k = tid; k < u.m - 1; k += nt)
+        sA[k] = uint8_t(u.A[k]);
+    for (int k = tid; k < u.n - 1; k += nt)
+        sB[k] = uint8_t(u.B[k]);
+}
+
+// The wide kernel's: rows [tk0, tk0 + KT) x columns [tl0, tl0 + LT), column-major.
+struct UkRectTile
+{
+    static constexpr int KT = kUkTileRows, LT = kUkTileCols;
+    GWAMD_LDS int16_t* tile;
+    const int16_t* S;
+    int tk0 = INT_MIN / 2, tl0 = INT_MIN / 2;
+    __device__ __forceinline__ int get(int k, int l, int bw) const
+    {
+        if (k >= tk0 && k < tk0 + KT && l >= tl0 && l < tl0 + LT)
+            return int(tile[(l - tl0) * KT + (k - tk0)]);
+        return int(S[size_t(k) + size_t(bw) * l]);
+    }
+    // rows [kc - KT/2, kc + KT/2) x columns [lc - LT + 1, lc], band edges as kUkMax
+    __device__ __forceinline__ void refill(const UkPair& u, int kc, int lc, int lane)
+    {
+        tk0 = kc - KT / 2;
+        tl0 = lc - LT + 1;
+        const int bw = u.bw, cols = u.cols;
+        GWAMD_LDS int16_t* dst = tile;
+        wave_sync();
+        staged_copy<int16_t>(
+            KT * LT, lane,
+            [this, bw, cols](int e, int16_t& v) {
+                const int kk  = tk0 + e % KT;
+                const int ll  = tl0 + e / KT;
+                const bool ok = kk >= 0 && kk < bw && ll >= 0 && ll < cols;
+                v             = S[ok ? size_t(kk) + size_t(bw) * ll : 0];
+                v             = ok ? v : kUkMax;
+            },
+            [dst](int e, int16_t v) { dst[e] = v; });
+        wave_sync();
+    }
+};
+// Value of cell (i, j) through to_band_indices (C division): kUkMax outside
+// the band, the tile's copy where it has one, S otherwise.
+template <typename Tile>
+__device__ __forceinline__ int uk_val(const UkPair& u, const Tile& t, int i, int j)
+{
+    const int k = (j - i + u.p) / 2;
+    const int l = j + i;
+    if (k < 0 || k >= u.bw || l < 0 || l >= u.cols)
+        return kUkMax;
+    return t.get(k, l, u.bw);
+}
+
+// One step of the per-step walk: lane 0 reads above (i-1, j), lane 1 the
+// diagonal (i-1, j-1), lane 2 left (i, j-1).
+template <typename Tile>
+__device__ __forceinline__ void uk_step(const UkPair& u, const Tile& t, int& i, int& j, int& s, PathWriter& pw, int lane)
+{
+    const int v      = uk_val(u, t, i - (lane == 2 ? 0 : 1), j - (lane == 0 ? 0 : 1));
+    const CellMove m = three_lane_step(v, s, u.ins, u.del);
+    i -= m.ins ? 0 : 1;
+    j -= m.del ? 0 : 1;
+    pw.put(int8_t(m.move), lane);
 }
 
 } // namespace
@@ -1385,37 +1432,17 @@ __global__ void __launch_bounds__(1024) ukkonen_wide_kernel(Args a)
     constexpr int kG        = kUkWideChunks * 16;
     GWAMD_LDS int16_t* tile = (GWAMD_LDS int16_t*)(base + a.lds_tile_off);
     int16_t* S              = reinterpret_cast<int16_t*>(a.ws + size_t(blockIdx.x) * size_t(a.ws_slot_bytes));
-    const int p             = a.ukkonen_p;
     constexpr int M         = kUkMax;
 
     for (int idx = blockIdx.x; idx < a.n; idx += gridDim.x)
     {
-        const int Q = uni(a.lens[2 * idx]);
-        const int T = uni(a.lens[2 * idx + 1]);
-        const char* qs = a.seqs + size_t(2 * idx) * a.stride;
-        const char* ts = a.seqs + size_t(2 * idx + 1) * a.stride;
-        int m = Q + 1, n = T + 1;
-        int8_t ins = kInsertion, del = kDeletion;
-        const bool swp = m > n;
-        if (swp)
-        {
-            m   = T + 1;
-            n   = Q + 1;
-            ins = kDeletion;
-            del = kInsertion;
-        }
-        const char* A = swp ? ts : qs;
-        const char* B = swp ? qs : ts;
-        for (int k = tid; k < m - 1; k += NT)
-            sA[k] = uint8_t(A[k]);
-        for (int k = tid; k < n - 1; k += NT)
-            sB[k] = uint8_t(B[k]);
+        const UkPair u = uk_pair(a, idx);
+        uk_copy_seqs(u, sA, sB, tid, NT);
         // column -1 (never a source of a computed cell, as in ukkonen_kernel)
         for (int e = tid; e < 4 * kG; e += NT)
             edge[e] = M;
         __syncthreads();
-        const int bw        = (1 + n - m + 2 * p + 1) / 2;
-        const int cols      = n + m;
+        const int m = u.m, n = u.n, p = u.p, bw = u.bw, cols = u.cols;
         const int kmax_odd  = (n - m + 2 * p - 1) / 2 + 1;
         const int kmax_even = (n - m + 2 * p) / 2 + 1;
         const int nck       = uni((bw + NT - 1) / NT); // <= kUkWideChunks (host plan)
@@ -1457,25 +1484,8 @@ __global__ void __launch_bounds__(1024) ukkonen_wide_kernel(Args a)
                         lo = g > 0 ? e_prev[kG + g - 1] : M; // row 64g - 1
                     if (lane == kWave - 1)
                         hi = g + 1 < kG ? e_prev[g + 1] : M; // row 64g + 64
-                    const int ii  = cmp ? i - 1 : 0;
-                    const int jj  = cmp ? j - 1 : 0;
-                    const int ca  = sA[ii];
-                    const int cb  = sB[jj];
-                    const int dgv = l < 2 ? M : V2[c] + (ca == cb ? 0 : 1);
-                    int left, above;
-                    if (even)
-                    {
-                        left  = k - 1 < 0 ? M : lo + 1;
-                        above = V1[c] + 1;
-                    }
-                    else
-                    {
-                        left  = V1[c] + 1;
-                        above = k + 1 >= bw ? M : hi + 1;
-                    }
-                    const int init = i == 0 ? j : (j == 0 ? i : M);
-                    const int v    = cmp ? min(dgv, min(left, above)) : init;
-                    V0[c]          = int(int16_t(v));
+                    const int v = uk_cell(sA, sB, cmp, even, i, j, k, l, bw, V1[c], V2[c], lo, hi);
+                    V0[c]       = int(int16_t(v));
                     if (k < bw)
                         S[size_t(k) + size_t(bw) * l] = int16_t(v);
                     if (lane == 0)
@@ -1498,49 +1508,12 @@ __global__ void __launch_bounds__(1024) ukkonen_wide_kernel(Args a)
         if (wave == 0)
         {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            constexpr int KT = kUkTileRows, LT = kUkTileCols;
-            int tk0 = INT_MIN / 2, tl0 = INT_MIN / 2;
-            // rows [k - KT/2, k + KT/2) x columns [l - LT + 1, l], band edges as M
-            auto refill = [&](int kc, int lc) {
-                tk0 = kc - KT / 2;
-                tl0 = lc - LT + 1;
-                wave_sync();
-                constexpr int kPer = KT * LT / kWave, kB = 8;
-                for (int e0 = 0; e0 < kPer; e0 += kB)
-                {
-                    int16_t v[kB];
-#pragma unroll
-                    for (int u = 0; u < kB; u++)
-                    {
-                        const int e   = (e0 + u) * kWave + lane;
-                        const int kk  = tk0 + e % KT;
-                        const int ll  = tl0 + e / KT;
-                        const bool ok = kk >= 0 && kk < bw && ll >= 0 && ll < cols;
-                        v[u]          = S[ok ? size_t(kk) + size_t(bw) * ll : 0];
-                        v[u]          = ok ? v[u] : int16_t(M);
-                    }
-#pragma unroll
-                    for (int u = 0; u < kB; u++)
-                        tile[(e0 + u) * kWave + lane] = v[u];
-                }
-                wave_sync();
-            };
-            auto val = [&](int i, int j) -> int {
-                const int k = (j - i + p) / 2;
-                const int l = j + i;
-                if (k < 0 || k >= bw || l < 0 || l >= cols)
-                    return M;
-                if (k >= tk0 && k < tk0 + KT && l >= tl0 && l < tl0 + LT)
-                    return int(tile[(l - tl0) * KT + (k - tk0)]);
-                return int(S[size_t(k) + size_t(bw) * l]);
-            };
+            constexpr int KT = UkRectTile::KT, LT = UkRectTile::LT;
+            UkRectTile view{tile, S};
             PathWriter pw{a.paths + size_t(idx) * a.max_path_length, a.max_path_length};
             int i = m - 1, j = n - 1;
-            refill((j - i + p) / 2, i + j);
-            int s = uni(val(i, j));
-            // lane 0: above (i-1, j), lane 1: diagonal (i-1, j-1), lane 2: left (i, j-1)
-            const int di = lane == 2 ? 0 : 1;
-            const int dj = lane == 0 ? 0 : 1;
+            view.refill(u, (j - i + p) / 2, i + j, lane);
+            int s = uni(uk_val(u, view, i, j));
             while (i > 0 && j > 0)
             {
                 i = uni(i);
@@ -1548,38 +1521,14 @@ __global__ void __launch_bounds__(1024) ukkonen_wide_kernel(Args a)
                 {
                     // the three neighbours inside the tile, or refill around (k, l)
                     const int kc = (j - i + p) / 2, lc = i + j;
-                    if (lc - 2 < tl0 || lc > tl0 + LT - 1 || kc - 1 < tk0 || kc + 1 >= tk0 + KT)
-                        refill(kc, lc);
+                    if (lc - 2 < view.tl0 || lc > view.tl0 + LT - 1 || kc - 1 < view.tk0 || kc + 1 >= view.tk0 + KT)
+                        view.refill(u, kc, lc, lane);
                 }
-                const int v     = val(i - di, j - dj);
-                const int above = uni(__builtin_amdgcn_readlane(v, 0));
-                const int dg    = uni(__builtin_amdgcn_readlane(v, 1));
-                const int left  = uni(__builtin_amdgcn_readlane(v, 2));
-                int8_t r;
-                if (left + 1 == s)
-                {
-                    r = ins;
-                    s = left;
-                    --j;
-                }
-                else if (above + 1 == s)
-                {
-                    r = del;
-                    s = above;
-                    --i;
-                }
-                else
-                {
-                    r = dg == s ? kMatch : kMismatch;
-                    s = dg;
-                    --i;
-                    --j;
-                }
-                pw.put(r, lane);
+                uk_step(u, view, i, j, s, pw, lane);
             }
             pw.finish(lane);
-            pw.fill(del, i, lane);
-            pw.fill(ins, j, lane);
+            pw.fill(u.del, i, lane);
+            pw.fill(u.ins, j, lane);
             if (lane == 0)
                 a.path_len[idx] = pw.overflow ? -1 : pw.pos;
         }

@@ -18,6 +18,7 @@
 //     workspace capacity (:569-638, aligner_global_hirschberg_myers.cpp:51-54).
 #include <hip/hip_runtime.h>
 
+#include "aligner_backtrace.hpp"
 #include "aligner_common.hpp"
 #include "aligner_device.hpp"
 #include "aligner_plan.hpp"
@@ -1153,27 +1154,13 @@ __global__ void __launch_bounds__(kWave) myers_kernel(Args a)
                 const int up      = __builtin_amdgcn_ds_bpermute(4 * (lane + 8), v);
                 const int dg      = __builtin_amdgcn_ds_bpermute(4 * (lane + 9), v);
                 const int lf      = __builtin_amdgcn_ds_bpermute(4 * (lane + 1), v);
-                const bool mv_ins = lf + 1 == v;
-                const bool mv_del = !mv_ins && up + 1 == v;
-                const int r       = mv_ins ? int(kInsertion) : (mv_del ? int(kDeletion) : (dg == v ? int(kMatch) : int(kMismatch)));
+                const CellMove m  = cell_move(v, up, dg, lf, kInsertion, kDeletion);
                 const bool term   = wa == 7 || wb == 7 || ci <= 0 || cj <= 0;
-                const int nxt     = term ? lane : lane + (mv_ins ? 1 : (mv_del ? 8 : 9));
-                uint64_t visited  = 0;
-                uint32_t sums     = 0;
-                int o = 0, steps = 0;
-                while (true)
-                {
-                    const int nx = uni(__builtin_amdgcn_readlane(nxt, o));
-                    if (nx == o)
-                        break;
-                    visited |= 1ull << o;
-                    sums |= 1u << ((o >> 3) + (o & 7));
-                    ++steps;
-                    o = nx;
-                }
-                if ((visited >> lane) & 1ull)
-                    path[pos + __builtin_popcount(sums & ((1u << (wa + wb)) - 1u))] = int8_t(r);
-                pos += steps;
+                const auto walk   = link_walk(term ? lane : lane + m.pick(1, 8, 9));
+                if (walk.on(lane))
+                    path[pos + walk.rank_of(wa + wb)] = int8_t(m.move);
+                pos += walk.steps;
+                const int o = walk.end;
                 i -= o >> 3;
                 j -= o & 7;
             }

@@ -12,15 +12,20 @@
 //    lists kept in HBM, predecessors farther back than the LDS ring, and
 //    bases other than A/C/G/T.  Unmarked rows never test for any of these;
 //  * a row with one predecessor takes a straight path: row r-1 from registers
-//    (its last cell per lane by one DPP shift), any other from the ring
-//    loaded into the same registers, so the two cases join without copies;
+//    (its last cell per lane by one DPP shift), any other from the ring.  The
+//    finished row is carried to the next row as the register tuple it was
+//    stored from (pin_row); the compiler still moves that tuple once per row
+//    (two 64-bit moves) and one register on the r-1 path;
 //  * the substitution scores come from a byte table per lane (score of the
 //    lane's read column against A, C, T, G in one 32-bit word per column)
 //    selected for the row's base with one v_perm per register pair, when
 //    both scores fit a byte (otherwise the caller keeps nw_forward_lds_pk);
-//  * the first span (column 0) and the carry-feeding wave are template
-//    parameters of the row loop, so each wave runs a loop without the other
-//    roles' branches.
+//  * the first span (column 0) and what a wave does with its carries (none,
+//    next wave, HBM for the next sweep) are template parameters of the row
+//    loop, so each wave runs a loop without the other roles' branches;
+//  * the loop runs block by block (poa_handover.hpp): the hand-over's waits,
+//    loads and stores sit between blocks of kHandBlock rows, and a row tests
+//    once each for its kind, for a spill row and for a sink row.
 //
 // Included by poa_kernels.hip inside namespace gwamd::poa, after the round-3
 // forward pass whose helpers (RowProg, load_row_pk, diag_src, pk_*) it uses.
@@ -67,6 +72,10 @@ __device__ __forceinline__ int wave_incl_max_b(int v)
 typedef u32x4 fwd_u32x4;
 typedef u32x2 fwd_u32x2;
 
+// v stays one register tuple here (an empty statement the compiler cannot see through)
+__device__ __forceinline__ void pin_row(fwd_u32x4& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void pin_row(fwd_u32x2& v) { asm volatile("" : "+v"(v)); }
+
 template <int NR>
 __device__ __forceinline__ void load_row_glb(const GWAMD_GLB int16_t* p, uint32_t (&P)[NR], uint32_t& prev)
 {
@@ -109,7 +118,17 @@ __device__ __forceinline__ void load_row_lds(const GWAMD_LDS int16_t* p, uint32_
     prev = uint32_t(uint16_t(p[0]));
 }
 
-template <int CPL, int NW, bool FIRST, bool FEED, int HB, typename SizeT>
+// What a wave does with its rows' carries: nothing (the last span), hand
+// them to the next wave of this sweep, or keep them in HBM for the next sweep
+// (block hand-over only; the per-row channel build tests to_hbm per row).
+enum : int
+{
+    kPostNone = 0,
+    kPostFeed = 1,
+    kPostHbm  = 2
+};
+
+template <int CPL, int NW, bool FIRST, int POST, int HB, typename SizeT>
 __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, int V, const uint8_t* read_f, int L,
                                           int16_t* ring_f, int ring_stride, int16_t* spill_f, int stride,
                                           uint8_t* codes_f, int code_stride, const Scores sc,
@@ -119,6 +138,8 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
 {
     static_assert(HB == 0 || (hand_block_ok(HB) && HB + kMaxRingRows16 <= kHandSlots && kChanRows == kHandSlots),
                   "a block and the ring's reach fit the 64 lanes of the carry register");
+    static_assert(POST != kPostHbm || HB > 0, "the HBM carries are batched per block");
+    constexpr bool FEED = POST == kPostFeed;
     g = as_global(g);
     GWAMD_LDS int16_t* ring          = lds_of(ring_f);
     const GWAMD_LDS uint8_t* read    = lds_of(read_f);
@@ -129,6 +150,8 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
     GWAMD_GLB int16_t* carry_hbm     = (GWAMD_GLB int16_t*)(carry_f);
     constexpr int NR    = CPL / 2;
     const int gap       = sc.gap;
+    // end row so far, on the scalar unit
+    int bval = uniform(best_val), brow = uniform(best_row);
     const int s_eq      = sc.match - gap;
     const int s_ne      = sc.mismatch - gap;
     const uint32_t gap2 = pk_bcast(gap);
@@ -154,6 +177,9 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
     // region that follows the lists (>= 64 entries), and real lists end
     // before xl_cap
     const int xl_last = xl_cap;
+    // bit 14 of a record marks a sink row; only the wave that owns the last
+    // column looks at it
+    const uint32_t sink_bit = uniform(int(owner)) ? (1u << 14) : 0u;
 
     // substitution byte table: byte b of T[c] = score of read column jb + c + 1
     // (read[jb + c]) against base code b = (base >> 1) & 3 (A 0, C 1, T 2, G 3)
@@ -165,10 +191,22 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
         T[c] = uint32_t(ch == 'A' ? s_eq : s_ne) | (uint32_t(ch == 'C' ? s_eq : s_ne) << 8) |
                (uint32_t(ch == 'T' ? s_eq : s_ne) << 16) | (uint32_t(ch == 'G' ? s_eq : s_ne) << 24);
     }
-    uint32_t Eprev[NR]; // final E of row r-1 (row 0: zeros); also the loaded predecessor row
+    // Final E of row r-1 (row 0: zeros), carried from row to row as the
+    // register tuples the row was stored from: as separate 32-bit values the
+    // compiler kept them in registers of their own and copied the finished
+    // row there (and back for a row with the predecessor r-1) on every row.
+    // pin_row keeps each tuple whole across the loop's back edge.
+    constexpr int VW = NR % 4 == 0 ? 4 : 2;
+    constexpr int NV = NR / VW;
+    using RowVec     = std::conditional_t<VW == 4, fwd_u32x4, fwd_u32x2>;
+    RowVec Ev[NV];
 #pragma unroll
-    for (int i = 0; i < NR; i++)
-        Eprev[i] = 0;
+    for (int q = 0; q < NV; q++)
+    {
+        Ev[q] = RowVec(0);
+        pin_row(Ev[q]);
+    }
+    auto Eprev = [&](int i) __attribute__((always_inline)) { return uint32_t(Ev[i / VW][i % VW]); };
     int cin_prev = 0;
     // Carries by row, lane r & 63.  Received ones (wave > 0: from the channel;
     // wave 0 of a later sweep: from HBM; never both), HB > 0: the block of the
@@ -184,12 +222,16 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
     GWAMD_GLB uint8_t* crow = codes + code_stride;
     GWAMD_GLB int16_t* srow = spill + stride;
     GWAMD_FP_START(fp);
-    for (int r = 1; r <= V; r++, crow += code_stride, srow += stride)
+    // Outer loop: one hand-over block of rows [r, rl] (HB == 0: every row in
+    // one block), which opens before its first row and is posted after its
+    // last; the rows inside test for neither.
+    for (int r = 1, rl; r <= V; r = rl + 1)
     {
+        rl = HB > 0 ? hand_block_last(r, V, HB) : V;
         if constexpr (HB > 0)
         {
             GWAMD_FP_MARK(fp, 4);
-            if (!FIRST && hand_opens(r, HB))
+            if (!FIRST)
             {
                 // the carries of this block of rows, into their lanes of cv
                 if (from_hbm)
@@ -213,7 +255,7 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                         prog_v[wave] = hand_new_tail(r, V, HB); // after the load, from the same wave
                 }
             }
-            if (FEED && hand_opens(r, HB) && hand_must_wait(r))
+            if (FEED && hand_must_wait(r))
             {
                 // flow control: the consumer must have taken the block whose slots this one reuses
                 const int need = hand_free_tail(r, HB);
@@ -225,100 +267,98 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
             }
             GWAMD_FP_LAP(fp, 4);
         }
-        GWAMD_FP_COUNT(fp, 7);
-        const uint32_t rec = rec_c;
-        // next rows: the record of row r+2, the predecessor list of row r+1
-        const uint32_t rec_nn = prec[min(r + 2, V)];
-        // (read for every row: rows without a list get garbage they never
-        // use; the offset is clamped into the list region)
-        const int pv_n = xls_at(min(int(rec_n >> 16), xl_last) + lane);
-        const int np       = int((rec >> 8) & 63);
-        const bool spill_r = (rec >> 15) & 1;
-        GWAMD_LDS int16_t* row = ring + (r & mask) * ring_stride;
-        uint32_t sig[NR];
+        for (; r <= rl; r++, crow += code_stride, srow += stride)
         {
-            const uint32_t bsel = 0x0c040c00u + ((rec >> 1) & 3u) * 0x00010001u;
-#pragma unroll
-            for (int i = 0; i < NR; i++)
-                sig[i] = __builtin_amdgcn_perm(T[2 * i + 1], T[2 * i], bsel);
-        }
-        GWAMD_FP_LAP(fp, 0);
-        int cin = 0;
-        // Rest of the row once dg, vt (and kd, kv) hold the maxima over the
-        // predecessors: in-lane prefix, closure across lanes and spans,
-        // codes and stores.  Instantiated once per path so each path is
-        // straight-line code.
-        auto finish = [&](auto multi_tag, const uint32_t(&dg)[NR], const uint32_t(&vt)[NR],
-                          const uint32_t(&kd)[NR], const uint32_t(&kv)[NR], int c0v,
-                          int c0kv) __attribute__((always_inline)) {
-            constexpr bool kMulti = decltype(multi_tag)::value;
-            uint32_t E[NR];
-#pragma unroll
-            for (int i = 0; i < NR; i++)
+            GWAMD_FP_COUNT(fp, 7);
+            const uint32_t rec = rec_c;
+            // next rows: the record of row r+2, the predecessor list of row r+1
+            const uint32_t rec_nn = prec[min(r + 2, V)];
+            // (read for every row: rows without a list get garbage they never
+            // use; the offset is clamped into the list region)
+            const int pv_n = xls_at(min(int(rec_n >> 16), xl_last) + lane);
+            const int np       = int((rec >> 8) & 63);
+            GWAMD_LDS int16_t* row = ring + (r & mask) * ring_stride;
+            uint32_t sig[NR];
             {
-                const uint32_t s = pk_max_lo_into_hi(pk_max(dg[i], vt[i]));
-                E[i]             = i == 0 ? s : pk_max_hi_carry(s, E[i - 1]);
+                const uint32_t bsel = 0x0c040c00u + ((rec >> 1) & 3u) * 0x00010001u;
+#pragma unroll
+                for (int i = 0; i < NR; i++)
+                    sig[i] = __builtin_amdgcn_perm(T[2 * i + 1], T[2 * i], bsel);
             }
-            const int m    = active ? int(int16_t(E[NR - 1] >> 16)) : kNeg;
-            const int incl = wave_incl_max_b(m);
-            const int excl = __builtin_amdgcn_update_dpp(kNeg, incl, 0x138, 0xf, 0xf, false);
-            const int wtot = __builtin_amdgcn_readlane(incl, kWave - 1);
-            GWAMD_FP_LAP(fp, 3);
-            GWAMD_FP_MARK(fp, 4);
-            if (FIRST)
-            {
-                cin = c0v + gap; // column 0
-                if (lane == 0)
+            GWAMD_FP_LAP(fp, 0);
+            int cin = 0;
+            // Rest of the row once dg, vt (and kd, kv) hold the maxima over the
+            // predecessors: in-lane prefix, closure across lanes and spans,
+            // codes and stores.  Instantiated once per path so each path is
+            // straight-line code.
+            auto finish = [&](auto multi_tag, const uint32_t(&dg)[NR], const uint32_t(&vt)[NR],
+                              const uint32_t(&kd)[NR], const uint32_t(&kv)[NR], int c0v,
+                              int c0kv) __attribute__((always_inline)) {
+                constexpr bool kMulti = decltype(multi_tag)::value;
+                uint32_t E[NR];
+#pragma unroll
+                for (int i = 0; i < NR; i++)
                 {
-                    row[kColShift]  = int16_t(cin);
-                    crow[kColShift] = uint8_t(1 | (c0kv << 2));
-                    if (spill_r)
-                        srow[kColShift] = int16_t(cin);
+                    const uint32_t s = pk_max_lo_into_hi(pk_max(dg[i], vt[i]));
+                    E[i]             = i == 0 ? s : pk_max_hi_carry(s, E[i - 1]);
                 }
-            }
-            else
-            {
-                if constexpr (HB > 0)
-                    cin = int(int16_t(__builtin_amdgcn_readlane(cv, hand_slot(r))));
-                else if (from_hbm)
+                const int m    = active ? int(int16_t(E[NR - 1] >> 16)) : kNeg;
+                const int incl = wave_incl_max_b(m);
+                const int excl = __builtin_amdgcn_update_dpp(kNeg, incl, 0x138, 0xf, 0xf, false);
+                const int wtot = __builtin_amdgcn_readlane(incl, kWave - 1);
+                GWAMD_FP_LAP(fp, 3);
+                GWAMD_FP_MARK(fp, 4);
+                if (FIRST)
                 {
-                    // carry of this row from the previous sweep's last span
-                    if (((r - 1) & (kWave - 1)) == 0)
+                    cin = c0v + gap; // column 0
+                    if (lane == 0)
                     {
-                        const int x = r + lane;
-                        uint32_t hc = x <= V ? uint32_t(int(carry_hbm[x])) : 0u;
-                        settle_vm1(hc); // wait here, once per 64 rows, not at every row's readlane
-                        cv = int(hc);
+                        row[kColShift]  = int16_t(cin);
+                        crow[kColShift] = uint8_t(1 | (c0kv << 2));
                     }
-                    cin = int(int16_t(__builtin_amdgcn_readlane(cv, (r - 1) & (kWave - 1))));
                 }
                 else
                 {
-                    // carry of this row from the previous span
-                    uint32_t w = uint32_t(uniform(int(chan_in[r & (kChanRows - 1)])));
-                    while ((w >> 16) != (uint32_t(r) & 0xffffu))
+                    if constexpr (HB > 0)
+                        cin = int(int16_t(__builtin_amdgcn_readlane(cv, hand_slot(r))));
+                    else if (from_hbm)
                     {
-                        GWAMD_FP_COUNT(fp, 4);
-                        __builtin_amdgcn_s_sleep(1);
-                        w = uint32_t(uniform(int(chan_in[r & (kChanRows - 1)])));
+                        // carry of this row from the previous sweep's last span
+                        if (((r - 1) & (kWave - 1)) == 0)
+                        {
+                            const int x = r + lane;
+                            uint32_t hc = x <= V ? uint32_t(int(carry_hbm[x])) : 0u;
+                            settle_vm1(hc); // wait here, once per 64 rows, not at every row's readlane
+                            cv = int(hc);
+                        }
+                        cin = int(int16_t(__builtin_amdgcn_readlane(cv, (r - 1) & (kWave - 1))));
                     }
-                    cin = int(int16_t(w & 0xffffu));
-                    if ((r & 7) == 0 && lane == 0)
-                        prog_v[wave] = r;
-                }
-                if (lane == 0)
-                {
+                    else
+                    {
+                        // carry of this row from the previous span
+                        uint32_t w = uint32_t(uniform(int(chan_in[r & (kChanRows - 1)])));
+                        while ((w >> 16) != (uint32_t(r) & 0xffffu))
+                        {
+                            GWAMD_FP_COUNT(fp, 4);
+                            __builtin_amdgcn_s_sleep(1);
+                            w = uint32_t(uniform(int(chan_in[r & (kChanRows - 1)])));
+                        }
+                        cin = int(int16_t(w & 0xffffu));
+                        if ((r & 7) == 0 && lane == 0)
+                            prog_v[wave] = r;
+                    }
                     if constexpr (HB == 0)
-                        bnd[r & mask] = int16_t(cin);
-                    if (spill_r)
-                        srow[cb + kColShift] = int16_t(cin); // same value as the previous span's last cell
+                    {
+                        if (lane == 0)
+                            bnd[r & mask] = int16_t(cin);
+                    }
                 }
-            }
-            if (FEED)
-            {
                 if constexpr (HB > 0)
-                    pvr = write_lane(pvr, max(cin, wtot), hand_slot(r), lane);
-                else
+                {
+                    if (POST != kPostNone)
+                        pvr = write_lane(pvr, max(cin, wtot), hand_slot(r), lane);
+                }
+                else if (FEED)
                 {
                     // flow control: the consumer must have taken row r-kChanRows+32
                     if ((r & 31) == 0 && r >= kChanRows)
@@ -332,283 +372,325 @@ __device__ __forceinline__ void fwd2_rows(WinGraph<SizeT> g, const RowProg& P, i
                     if (lane == 0)
                         chan_out[r & (kChanRows - 1)] = (uint32_t(r) << 16) | uint32_t(uint16_t(max(cin, wtot)));
                 }
-            }
-            if (to_hbm && lane == 0)
-                carry_hbm[r] = int16_t(max(cin, wtot));
-            GWAMD_FP_LAP(fp, 4);
-            const uint32_t b2v = pk_bcast(max(excl, cin));
-#pragma unroll
-            for (int i = 0; i < NR; i++)
-                E[i] = pk_max(E[i], b2v);
-            if (active)
-            {
-                // codes: 0 diagonal, 1 vertical, 2 horizontal (+ slot << 2)
-                uint32_t code[NR];
+                if (HB == 0 && to_hbm && lane == 0)
+                    carry_hbm[r] = int16_t(max(cin, wtot));
+                GWAMD_FP_LAP(fp, 4);
+                const uint32_t b2v = pk_bcast(max(excl, cin));
 #pragma unroll
                 for (int i = 0; i < NR; i++)
+                    E[i] = pk_max(E[i], b2v);
+                if (active)
                 {
-                    if constexpr (kMulti)
+                    // codes: 0 diagonal, 1 vertical, 2 horizontal (+ slot << 2)
+                    uint32_t code[NR];
+#pragma unroll
+                    for (int i = 0; i < NR; i++)
                     {
-                        const uint32_t a   = pk_min_u(pk_sub(E[i], dg[i]), one2); // 0: diagonal match
-                        const uint32_t bb  = pk_min_u(pk_sub(E[i], vt[i]), one2); // 0: vertical match
-                        const uint32_t cvh = pk_mad(bb, pk_sub(two2, kv[i]), kv[i]); // vertical or horizontal
-                        code[i]            = pk_mad(a, pk_sub(cvh, kd[i]), kd[i]);
+                        if constexpr (kMulti)
+                        {
+                            const uint32_t a   = pk_min_u(pk_sub(E[i], dg[i]), one2); // 0: diagonal match
+                            const uint32_t bb  = pk_min_u(pk_sub(E[i], vt[i]), one2); // 0: vertical match
+                            const uint32_t cvh = pk_mad(bb, pk_sub(two2, kv[i]), kv[i]); // vertical or horizontal
+                            code[i]            = pk_mad(a, pk_sub(cvh, kd[i]), kd[i]);
+                        }
+                        else
+                        {
+                            // one predecessor (slot 0): a + min(a, E - vt)
+                            const uint32_t a = pk_min_u(pk_sub(E[i], dg[i]), one2);
+                            code[i]          = pk_add(a, pk_min_u(pk_sub(E[i], vt[i]), a));
+                        }
+                    }
+                    if constexpr (NR % 4 == 0)
+                    {
+#pragma unroll
+                        for (int q = 0; q < NR / 4; q++)
+                        {
+                            const fwd_u32x4 ev = {E[4 * q], E[4 * q + 1], E[4 * q + 2], E[4 * q + 3]};
+                            *reinterpret_cast<GWAMD_LDS fwd_u32x4*>(row + jb + kColShift + 1 + 8 * q) = ev;
+                            const uint32_t w0 = __builtin_amdgcn_perm(code[4 * q + 1], code[4 * q], 0x06040200u);
+                            const uint32_t w1 = __builtin_amdgcn_perm(code[4 * q + 3], code[4 * q + 2], 0x06040200u);
+                            __builtin_nontemporal_store(uint64_t(w0) | (uint64_t(w1) << 32),
+                                                        reinterpret_cast<GWAMD_GLB uint64_t*>(crow + jb + kColShift + 1 + 8 * q));
+                        }
                     }
                     else
                     {
-                        // one predecessor (slot 0): a + min(a, E - vt)
-                        const uint32_t a = pk_min_u(pk_sub(E[i], dg[i]), one2);
-                        code[i]          = pk_add(a, pk_min_u(pk_sub(E[i], vt[i]), a));
+                        const fwd_u32x2 ev = {E[0], E[1]};
+                        *reinterpret_cast<GWAMD_LDS fwd_u32x2*>(row + jb + kColShift + 1) = ev;
+                        __builtin_nontemporal_store(__builtin_amdgcn_perm(code[1], code[0], 0x06040200u),
+                                                    reinterpret_cast<GWAMD_GLB uint32_t*>(crow + jb + kColShift + 1));
                     }
                 }
-                if constexpr (NR % 4 == 0)
+                if (rec & (1u << 15))
+                {
+                    // the row's copy in HBM, tested once per row: the span's
+                    // first column (column 0, or the previous span's last cell)
+                    // from lane 0, then the lanes' cells
+                    if (lane == 0)
+                        srow[cb + kColShift] = int16_t(cin);
+                    if (active)
+                    {
+                        if constexpr (NR % 4 == 0)
+                        {
+#pragma unroll
+                            for (int q = 0; q < NR / 4; q++)
+                            {
+                                const fwd_u32x4 ev = {E[4 * q], E[4 * q + 1], E[4 * q + 2], E[4 * q + 3]};
+                                *reinterpret_cast<GWAMD_GLB fwd_u32x4*>(srow + jb + kColShift + 1 + 8 * q) = ev;
+                            }
+                        }
+                        else
+                        {
+                            const fwd_u32x2 ev = {E[0], E[1]};
+                            *reinterpret_cast<GWAMD_GLB fwd_u32x2*>(srow + jb + kColShift + 1) = ev;
+                        }
+                    }
+                }
+                GWAMD_FP_LAP(fp, 5);
+                if (rec & sink_bit)
+                {
+                    // sink row: E at the last column (column 0 for an empty read),
+                    // read back from the ring row just stored
+                    int endv = cin;
+#pragma unroll
+                    for (int i = 0; i < NR; i++)
+                    {
+                        if (2 * i == own_c)
+                            endv = int(int16_t(E[i] & 0xffff));
+                        if (2 * i + 1 == own_c)
+                            endv = int(int16_t(E[i] >> 16));
+                    }
+                    // (compared on the scalar unit: a vector compare put an exec
+                    // region with the loop-carried copies behind every row)
+                    const int v = uniform(L == 0 ? cin : __builtin_amdgcn_readlane(endv, own_lane));
+                    if (bval < v)
+                        bval = v, brow = r;
+                }
+#pragma unroll
+                for (int q = 0; q < NV; q++)
                 {
 #pragma unroll
-                    for (int q = 0; q < NR / 4; q++)
-                    {
-                        const fwd_u32x4 ev = {E[4 * q], E[4 * q + 1], E[4 * q + 2], E[4 * q + 3]};
-                        *reinterpret_cast<GWAMD_LDS fwd_u32x4*>(row + jb + kColShift + 1 + 8 * q) = ev;
-                        if (spill_r)
-                            *reinterpret_cast<GWAMD_GLB fwd_u32x4*>(srow + jb + kColShift + 1 + 8 * q) = ev;
-                        const uint32_t w0 = __builtin_amdgcn_perm(code[4 * q + 1], code[4 * q], 0x06040200u);
-                        const uint32_t w1 = __builtin_amdgcn_perm(code[4 * q + 3], code[4 * q + 2], 0x06040200u);
-                        __builtin_nontemporal_store(uint64_t(w0) | (uint64_t(w1) << 32),
-                                                    reinterpret_cast<GWAMD_GLB uint64_t*>(crow + jb + kColShift + 1 + 8 * q));
-                    }
+                    for (int k = 0; k < VW; k++)
+                        Ev[q][k] = E[VW * q + k];
+                    pin_row(Ev[q]);
+                }
+            };
+            // one compare for the commonest kind: no mark (bit 7) and a
+            // predecessor count (bits 8-13) of one
+            if ((rec & 0x3f80u) == 0x0100u)
+            {
+                // one predecessor, in registers (row r-1) or in the ring
+                const int d = int(rec >> 16);
+                uint32_t Pr[NR], prev;
+                if (d == 1)
+                {
+                    GWAMD_FP_COUNT(fp, 0);
+#pragma unroll
+                    for (int i = 0; i < NR; i++)
+                        Pr[i] = Eprev(i);
+                    prev = uint32_t(__builtin_amdgcn_update_dpp(int(uint32_t(uint16_t(cin_prev))),
+                                                                int(Eprev(NR - 1) >> 16), 0x138, 0xf, 0xf, false));
                 }
                 else
                 {
-                    const fwd_u32x2 ev = {E[0], E[1]};
-                    *reinterpret_cast<GWAMD_LDS fwd_u32x2*>(row + jb + kColShift + 1) = ev;
-                    if (spill_r)
-                        *reinterpret_cast<GWAMD_GLB fwd_u32x2*>(srow + jb + kColShift + 1) = ev;
-                    __builtin_nontemporal_store(__builtin_amdgcn_perm(code[1], code[0], 0x06040200u),
-                                                reinterpret_cast<GWAMD_GLB uint32_t*>(crow + jb + kColShift + 1));
+                    GWAMD_FP_COUNT(fp, 1);
+                    const int ps = (r - d) & mask;
+                    load_row_lds<NR>(ring + ps * ring_stride + ja + kColShift, Pr, prev);
+                    if (!FIRST)
+                    {
+                        const uint32_t bv = HB > 0 ? uint32_t(__builtin_amdgcn_readlane(cv, hand_slot(r - d))) & 0xffffu
+                                                   : uint32_t(uint16_t(bnd[ps]));
+                        prev              = lane == 0 ? bv : prev;
+                    }
                 }
-            }
-            GWAMD_FP_LAP(fp, 5);
-            if ((rec & (1u << 14)) && owner)
-            {
-                // sink row: E at the last column (column 0 for an empty read),
-                // read back from the ring row just stored
-                int endv = cin;
+                const int c0v = FIRST ? int(int16_t(__builtin_amdgcn_readfirstlane(prev))) : 0;
+                uint32_t dg[NR], vt[NR];
+                diag_src<NR>(Pr, prev, dg);
 #pragma unroll
                 for (int i = 0; i < NR; i++)
                 {
-                    if (2 * i == own_c)
-                        endv = int(int16_t(E[i] & 0xffff));
-                    if (2 * i + 1 == own_c)
-                        endv = int(int16_t(E[i] >> 16));
+                    dg[i] = pk_add(dg[i], sig[i]);
+                    vt[i] = pk_add(Pr[i], gap2);
                 }
-                const int v = L == 0 ? cin : __builtin_amdgcn_readlane(endv, own_lane);
-                if (best_val < v)
-                    best_val = v, best_row = r;
-            }
-#pragma unroll
-            for (int i = 0; i < NR; i++)
-                Eprev[i] = E[i];
-        };
-        if (!(rec & 0x80u) && np == 1)
-        {
-            // one predecessor, in registers (row r-1) or in the ring; the ring
-            // row is loaded into Eprev, so both cases continue from there
-            const int d = int(rec >> 16);
-            uint32_t prev;
-            if (d == 1)
-            {
-                GWAMD_FP_COUNT(fp, 0);
-                prev = uint32_t(__builtin_amdgcn_update_dpp(int(uint32_t(uint16_t(cin_prev))),
-                                                            int(Eprev[NR - 1] >> 16), 0x138, 0xf, 0xf, false));
+                GWAMD_FP_LAP(fp, 1);
+                finish(std::false_type{}, dg, vt, dg, vt, c0v, 0);
             }
             else
             {
-                GWAMD_FP_COUNT(fp, 1);
-                const int ps = (r - d) & mask;
-                load_row_lds<NR>(ring + ps * ring_stride + ja + kColShift, Eprev, prev);
-                if (!FIRST)
-                {
-                    const uint32_t bv = HB > 0 ? uint32_t(__builtin_amdgcn_readlane(cv, hand_slot(r - d))) & 0xffffu
-                                               : uint32_t(uint16_t(bnd[ps]));
-                    prev              = lane == 0 ? bv : prev;
-                }
-            }
-            const int c0v = FIRST ? int(int16_t(__builtin_amdgcn_readfirstlane(prev))) : 0;
-            uint32_t dg[NR], vt[NR];
-            diag_src<NR>(Eprev, prev, dg);
-#pragma unroll
-            for (int i = 0; i < NR; i++)
-            {
-                dg[i] = pk_add(dg[i], sig[i]);
-                vt[i] = pk_add(Eprev[i], gap2);
-            }
-            GWAMD_FP_LAP(fp, 1);
-            finish(std::false_type{}, dg, vt, dg, vt, c0v, 0);
-        }
-        else
-        {
-            // Several predecessors (slot by slot with the first maximising
-            // slot), and the rows the row program marked (sources, far or
-            // escaped predecessors, other bases).  The two kinds get separate
-            // predecessor loaders: a loader that tested the mark per slot was
-            // miscompiled (ROCm 7.2: the flag reached the slot tests inverted).
-            auto rows_general = [&](auto slow_tag, int pv, int n) __attribute__((always_inline)) {
-                constexpr bool kSlow = decltype(slow_tag)::value;
-                auto load_pred = [&](int p, uint32_t(&Q)[NR], uint32_t& qprev) __attribute__((always_inline)) {
-                    if (p == r - 1)
-                    {
-#pragma unroll
-                        for (int i = 0; i < NR; i++)
-                            Q[i] = Eprev[i];
-                        qprev = uint32_t(__builtin_amdgcn_update_dpp(int(uint32_t(uint16_t(cin_prev))),
-                                                                     int(Eprev[NR - 1] >> 16), 0x138, 0xf, 0xf,
-                                                                     false));
-                        return;
-                    }
-                    if constexpr (kSlow)
-                    {
-                        if (p == 0)
+                // Several predecessors (slot by slot with the first maximising
+                // slot), and the rows the row program marked (sources, far or
+                // escaped predecessors, other bases).  The two kinds get separate
+                // predecessor loaders: a loader that tested the mark per slot was
+                // miscompiled (ROCm 7.2: the flag reached the slot tests inverted).
+                auto rows_general = [&](auto slow_tag, int pv, int n) __attribute__((always_inline)) {
+                    constexpr bool kSlow = decltype(slow_tag)::value;
+                    auto load_pred = [&](int p, uint32_t(&Q)[NR], uint32_t& qprev) __attribute__((always_inline)) {
+                        if (p == r - 1)
                         {
 #pragma unroll
                             for (int i = 0; i < NR; i++)
-                                Q[i] = 0;
-                            qprev = 0;
+                                Q[i] = Eprev(i);
+                            qprev = uint32_t(__builtin_amdgcn_update_dpp(int(uint32_t(uint16_t(cin_prev))),
+                                                                         int(Eprev(NR - 1) >> 16), 0x138, 0xf, 0xf,
+                                                                         false));
                             return;
                         }
-                        if (r - p > mask)
+                        if constexpr (kSlow)
                         {
-                            load_row_glb<NR>(spill + size_t(p) * stride + ja + kColShift, Q, qprev);
-                            settle_vm<NR>(Q, qprev);
-                            return;
+                            if (p == 0)
+                            {
+#pragma unroll
+                                for (int i = 0; i < NR; i++)
+                                    Q[i] = 0;
+                                qprev = 0;
+                                return;
+                            }
+                            if (r - p > mask)
+                            {
+                                load_row_glb<NR>(spill + size_t(p) * stride + ja + kColShift, Q, qprev);
+                                settle_vm<NR>(Q, qprev);
+                                return;
+                            }
                         }
-                    }
-                    load_row_lds<NR>(ring + (p & mask) * ring_stride + ja + kColShift, Q, qprev);
-                    if (!FIRST)
+                        load_row_lds<NR>(ring + (p & mask) * ring_stride + ja + kColShift, Q, qprev);
+                        if (!FIRST)
+                        {
+                            const uint32_t bv = HB > 0 ? uint32_t(__builtin_amdgcn_readlane(cv, hand_slot(p))) & 0xffffu
+                                                       : uint32_t(uint16_t(bnd[p & mask]));
+                            qprev             = lane == 0 ? bv : qprev;
+                        }
+                    };
+                    uint32_t dg[NR], vt[NR];
+                    int c0v = 0, c0kv = 0;
                     {
-                        const uint32_t bv = HB > 0 ? uint32_t(__builtin_amdgcn_readlane(cv, hand_slot(p))) & 0xffffu
-                                                   : uint32_t(uint16_t(bnd[p & mask]));
-                        qprev             = lane == 0 ? bv : qprev;
-                    }
-                };
-                uint32_t dg[NR], vt[NR];
-                int c0v = 0, c0kv = 0;
-                {
-                    uint32_t Pv[NR], prev;
-                    load_pred(__builtin_amdgcn_readfirstlane(pv), Pv, prev);
-                    if (FIRST)
-                        c0v = int(int16_t(__builtin_amdgcn_readfirstlane(prev)));
-                    diag_src<NR>(Pv, prev, dg);
-#pragma unroll
-                    for (int i = 0; i < NR; i++)
-                    {
-                        dg[i] = pk_add(dg[i], sig[i]);
-                        vt[i] = pk_add(Pv[i], gap2);
-                    }
-                }
-                if (n > 1)
-                {
-                    uint32_t kd[NR], kv[NR];
-#pragma unroll
-                    for (int i = 0; i < NR; i++)
-                    {
-                        kd[i] = 0;
-                        kv[i] = one2;
-                    }
-                    for (int k = 1; k < n; k++)
-                    {
-                        uint32_t Q[NR], qprev, dq[NR];
-                        load_pred(__builtin_amdgcn_readlane(pv, k), Q, qprev);
+                        uint32_t Pv[NR], prev;
+                        load_pred(__builtin_amdgcn_readfirstlane(pv), Pv, prev);
                         if (FIRST)
-                        {
-                            // column 0: first maximising predecessor slot
-                            const int pe = int(int16_t(__builtin_amdgcn_readfirstlane(qprev)));
-                            c0kv         = pe > c0v ? k : c0kv;
-                            c0v          = max(c0v, pe);
-                        }
-                        diag_src<NR>(Q, qprev, dq);
-                        const uint32_t kk4 = pk_bcast(4 * k);
-                        const uint32_t kk1 = pk_bcast(4 * k + 1);
+                            c0v = int(int16_t(__builtin_amdgcn_readfirstlane(prev)));
+                        diag_src<NR>(Pv, prev, dg);
 #pragma unroll
                         for (int i = 0; i < NR; i++)
                         {
-                            const uint32_t d  = pk_add(dq[i], sig[i]);
-                            const uint32_t nd = pk_max(dg[i], d);
-                            kd[i] = pk_mad(pk_min_u(pk_sub(nd, dg[i]), one2), pk_sub(kk4, kd[i]), kd[i]);
-                            dg[i] = nd;
-                            const uint32_t v  = pk_add(Q[i], gap2);
-                            const uint32_t nv = pk_max(vt[i], v);
-                            kv[i] = pk_mad(pk_min_u(pk_sub(nv, vt[i]), one2), pk_sub(kk1, kv[i]), kv[i]);
-                            vt[i] = nv;
+                            dg[i] = pk_add(dg[i], sig[i]);
+                            vt[i] = pk_add(Pv[i], gap2);
                         }
                     }
-                    GWAMD_FP_LAP(fp, 2);
-                    finish(std::true_type{}, dg, vt, kd, kv, c0v, c0kv);
-                }
-                else
-                {
-                    GWAMD_FP_LAP(fp, 2);
-                    finish(std::false_type{}, dg, vt, dg, vt, c0v, 0);
-                }
-            };
-            if (!(rec & 0x80u))
-            {
-                GWAMD_FP_COUNT(fp, 2);
-                rows_general(std::false_type{}, pv_c, np); // np >= 2, every predecessor in the ring
-            }
-            else
-            {
-                GWAMD_FP_COUNT(fp, 3);
-                // predecessor rows (sources: n = 1, row 0); lists through the
-                // typed LDS pointer (P's own is flat: its loads count in
-                // vmcnt, so a wait for them also waits for every code store)
-                int n  = np;
-                int pv = 0;
-                if (np == int(kRecEscape))
-                    pv = row_preds<SizeT>(P, g, r, rec, lane, n);
-                else
-                {
-                    if (np >= 2)
-                        pv = lane < np ? int(pxl[(rec >> 16) + lane]) : 0;
-                    else if (np == 1)
-                        pv = r - int(rec >> 16);
-                    if (np == 0)
-                        n = 1;
-                }
-                const uint32_t ub = uint32_t(row_base<SizeT>(g, rec, r));
-                if (!((ub & 0xc0u) == 0x40u && ((0x10008aull >> (ub & 0x3fu)) & 1u)))
-                {
-                    const GWAMD_LDS uint32_t* rw = reinterpret_cast<const GWAMD_LDS uint32_t*>(read + ja);
-#pragma unroll
-                    for (int i = 0; i < NR; i++)
+                    if (n > 1)
                     {
-                        const uint32_t wv = rw[i / 2] >> ((i & 1) * 16);
-                        const int ch0 = int(wv & 0xff), ch1 = int((wv >> 8) & 0xff);
-                        sig[i]        = uint32_t(uint16_t(ch0 == int(ub) ? s_eq : s_ne)) |
-                                 (uint32_t(uint16_t(ch1 == int(ub) ? s_eq : s_ne)) << 16);
+                        uint32_t kd[NR], kv[NR];
+#pragma unroll
+                        for (int i = 0; i < NR; i++)
+                        {
+                            kd[i] = 0;
+                            kv[i] = one2;
+                        }
+                        for (int k = 1; k < n; k++)
+                        {
+                            uint32_t Q[NR], qprev, dq[NR];
+                            load_pred(__builtin_amdgcn_readlane(pv, k), Q, qprev);
+                            if (FIRST)
+                            {
+                                // column 0: first maximising predecessor slot
+                                const int pe = int(int16_t(__builtin_amdgcn_readfirstlane(qprev)));
+                                c0kv         = pe > c0v ? k : c0kv;
+                                c0v          = max(c0v, pe);
+                            }
+                            diag_src<NR>(Q, qprev, dq);
+                            const uint32_t kk4 = pk_bcast(4 * k);
+                            const uint32_t kk1 = pk_bcast(4 * k + 1);
+#pragma unroll
+                            for (int i = 0; i < NR; i++)
+                            {
+                                const uint32_t d  = pk_add(dq[i], sig[i]);
+                                const uint32_t nd = pk_max(dg[i], d);
+                                kd[i] = pk_mad(pk_min_u(pk_sub(nd, dg[i]), one2), pk_sub(kk4, kd[i]), kd[i]);
+                                dg[i] = nd;
+                                const uint32_t v  = pk_add(Q[i], gap2);
+                                const uint32_t nv = pk_max(vt[i], v);
+                                kv[i] = pk_mad(pk_min_u(pk_sub(nv, vt[i]), one2), pk_sub(kk1, kv[i]), kv[i]);
+                                vt[i] = nv;
+                            }
+                        }
+                        GWAMD_FP_LAP(fp, 2);
+                        finish(std::true_type{}, dg, vt, kd, kv, c0v, c0kv);
                     }
+                    else
+                    {
+                        GWAMD_FP_LAP(fp, 2);
+                        finish(std::false_type{}, dg, vt, dg, vt, c0v, 0);
+                    }
+                };
+                if (!(rec & 0x80u))
+                {
+                    GWAMD_FP_COUNT(fp, 2);
+                    rows_general(std::false_type{}, pv_c, np); // np >= 2, every predecessor in the ring
                 }
-                rows_general(std::true_type{}, pv, uniform(n));
+                else
+                {
+                    GWAMD_FP_COUNT(fp, 3);
+                    // predecessor rows (sources: n = 1, row 0); lists through the
+                    // typed LDS pointer (P's own is flat: its loads count in
+                    // vmcnt, so a wait for them also waits for every code store)
+                    int n  = np;
+                    int pv = 0;
+                    if (np == int(kRecEscape))
+                        pv = row_preds<SizeT>(P, g, r, rec, lane, n);
+                    else
+                    {
+                        if (np >= 2)
+                            pv = lane < np ? int(pxl[(rec >> 16) + lane]) : 0;
+                        else if (np == 1)
+                            pv = r - int(rec >> 16);
+                        if (np == 0)
+                            n = 1;
+                    }
+                    const uint32_t ub = uint32_t(row_base<SizeT>(g, rec, r));
+                    if (!((ub & 0xc0u) == 0x40u && ((0x10008aull >> (ub & 0x3fu)) & 1u)))
+                    {
+                        const GWAMD_LDS uint32_t* rw = reinterpret_cast<const GWAMD_LDS uint32_t*>(read + ja);
+#pragma unroll
+                        for (int i = 0; i < NR; i++)
+                        {
+                            const uint32_t wv = rw[i / 2] >> ((i & 1) * 16);
+                            const int ch0 = int(wv & 0xff), ch1 = int((wv >> 8) & 0xff);
+                            sig[i]        = uint32_t(uint16_t(ch0 == int(ub) ? s_eq : s_ne)) |
+                                     (uint32_t(uint16_t(ch1 == int(ub) ? s_eq : s_ne)) << 16);
+                        }
+                    }
+                    rows_general(std::true_type{}, pv, uniform(n));
+                }
             }
-        }
+            cin_prev = cin;
+            rec_c    = rec_n;
+            rec_n    = uint32_t(uniform(int(rec_nn)));
+            pv_c     = pv_n;
+            GWAMD_FP_LAP(fp, 6);
+        } // rows of the block
         if constexpr (HB > 0)
         {
-            if (FEED && hand_closes(r, V, HB))
+            // rl closes the block: its last row, or row V (a partial block)
+            if (FEED)
             {
                 GWAMD_FP_MARK(fp, 4);
-                // post the block (a partial one at row V): its carries, then the head, from the same wave
-                if (hand_lane_in_block(lane, r, HB))
+                // post the block: its carries, then the head, from the same wave
+                if (hand_lane_in_block(lane, rl, HB))
                     chan_out[lane] = uint32_t(pvr);
                 if (lane == 0)
-                    head_v[wave] = r;
+                    head_v[wave] = rl;
                 GWAMD_FP_LAP(fp, 4);
             }
+            else if (POST == kPostHbm)
+            {
+                // the block's carries for the next sweep, one store per lane
+                const int x = hand_lane_row(lane, rl);
+                if (hand_lane_in_block(lane, rl, HB) && x >= 1 && x <= rl)
+                    carry_hbm[x] = int16_t(pvr);
+            }
         }
-        cin_prev = cin;
-        rec_c    = rec_n;
-        rec_n    = uint32_t(uniform(int(rec_nn)));
-        pv_c     = pv_n;
-        GWAMD_FP_LAP(fp, 6);
     }
     GWAMD_FP_STOP(fp);
+    best_val = bval;
+    best_row = brow;
 }
 
 // Drop-in for nw_forward_lds_pk (same arguments and result) when fwd2_ok(sc).
@@ -649,22 +731,33 @@ __device__ int nw_forward_lds_v2(WinGraph<SizeT> g, const RowProg& P, int V, con
         const bool owner    = span == own_span;
         if (!wact || V < 1)
             continue;
-        auto rows = [&](auto first_tag, auto feed_tag) __attribute__((always_inline)) {
-            fwd2_rows<CPL, NW, decltype(first_tag)::value, decltype(feed_tag)::value, kHandBlock>(
+        auto rows = [&](auto first_tag, auto post_tag) __attribute__((always_inline)) {
+            fwd2_rows<CPL, NW, decltype(first_tag)::value, decltype(post_tag)::value, kHandBlock>(
                 g, P, V, read, L, ring, ring_stride, spill, stride, codes, code_stride, sc, shb, carry_hbm, lane, wave,
                 cb, to_hbm, from_hbm, owner, xl_cap, best_row, best_val, fp);
         };
-        if (first)
-        {
+        // (feed and to_hbm exclude each other: a wave with a next span in
+        // this sweep is not the sweep's last)
+        auto rows_post = [&](auto first_tag) __attribute__((always_inline)) {
             if (feed)
-                rows(std::true_type{}, std::true_type{});
-            else
-                rows(std::true_type{}, std::false_type{});
-        }
-        else if (feed)
-            rows(std::false_type{}, std::true_type{});
+            {
+                rows(first_tag, std::integral_constant<int, kPostFeed>{});
+                return;
+            }
+            if constexpr (kHandBlock > 0)
+            {
+                if (to_hbm)
+                {
+                    rows(first_tag, std::integral_constant<int, kPostHbm>{});
+                    return;
+                }
+            }
+            rows(first_tag, std::integral_constant<int, kPostNone>{});
+        };
+        if (first)
+            rows_post(std::true_type{});
         else
-            rows(std::false_type{}, std::false_type{});
+            rows_post(std::false_type{});
     } // sweeps
     if (nsweep > 1 || NW > 1)
     {

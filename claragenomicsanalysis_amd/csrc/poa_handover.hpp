@@ -36,6 +36,22 @@
 //    the oldest block is waited for by nobody: by induction every wait ends;
 //  * a restart (next read, next sweep) zeroes head, tail and the slots between
 //    two barriers, after every wave has left the row loop.
+//
+// The row loop is written block by block: an outer loop whose step is one
+// block [s, min(e, V)] (hand_block_last), with the consumer's wait, load and
+// tail store and the producer's flow-control wait before the block's first
+// row, and the producer's slot and head stores after its last; the rows inside
+// test for none of these.  This is the same sequence of waits and stores, at
+// the same rows, as the per-row tests hand_opens / hand_closes gave (the loop
+// starts at row 1, every later block at a multiple of B, and a block ends at
+// its last row or at V), so the argument above holds unchanged: no wait was
+// added, moved before a store it used to follow, or given a larger threshold.
+//
+// The wave that ends a sweep keeps its carries for the next sweep in HBM.  It
+// fills the same register as a producer and stores the block's lanes to
+// carry[row] after the block's last row, rows 1 .. V only.  Nobody waits for
+// these stores in the row loop: the next sweep starts behind two barriers, and
+// its wave 0 then loads them block by block (hand_lane_row).
 #pragma once
 
 namespace gwamd

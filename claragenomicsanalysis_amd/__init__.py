@@ -1,5 +1,6 @@
 """MI355X-native batched POA consensus/MSA, global alignment and cudamapper's
-minimizer index, anchor matcher, overlapper and overlap-end rescue.
+minimizer index, anchor matcher, overlapper, overlap-end rescue, index
+batches and reads resident on the device.
 
 Python mirror of the reference's pygenomeworks bindings (genomeworks.cudapoa,
 genomeworks.cudaaligner) over the C ABI of libgwamd.so (include/*.h).  All
@@ -7,7 +8,10 @@ compute runs in hand-written HIP kernels for gfx950; there is no CPU fallback.
 """
 from ._lib import load_library, library_path  # noqa: F401
 from .cudamapper import (Index, match_anchors, get_overlaps, match_overlaps, post_process_overlaps,  # noqa: F401
-                         rescue_overlap_ends, extend_overlap_by_sequence_similarity)
+                         rescue_overlap_ends, extend_overlap_by_sequence_similarity, DeviceReads,
+                         group_reads_into_indices, generate_batches_of_indices, IndexHostCopy)
 
 __all__ = ["load_library", "library_path", "Index", "match_anchors", "get_overlaps", "match_overlaps",
-           "post_process_overlaps", "rescue_overlap_ends", "extend_overlap_by_sequence_similarity"]
+           "post_process_overlaps", "rescue_overlap_ends", "extend_overlap_by_sequence_similarity",
+           "DeviceReads", "group_reads_into_indices", "generate_batches_of_indices",
+           "IndexHostCopy"]

@@ -8,6 +8,7 @@
 
 #include "aligner_common.hpp"
 #include "aligner_plan.hpp"
+#include "aligner_resident.hpp"
 #include "allocator_handle.hpp"
 #include "gwamd_cudaaligner.h"
 #include "host_common.hpp"
@@ -274,19 +275,12 @@ public:
     StatusType add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
                              bool rc_query, bool rc_target) override
     {
-        // AlignerGlobalUkkonen::add_alignment (aligner_global_ukkonen.cpp:47-57)
-        if (algo_ == GWAMD_ALIGNER_UKKONEN && std::abs(query_length - target_length) > ukkonen_max_difference())
-            return StatusType::exceeded_max_alignment_difference;
-        // aligner_global.cpp:60-118
-        if (query_length < 0 || target_length < 0)
+        if (device_added_) // a batch is all host-added or all device-added
             return StatusType::generic_error;
-        const int32_t n = int32_t(alignments_.size());
-        if (n >= max_n_)
-            return StatusType::exceeded_max_alignments;
-        if (query_length > max_q_)
-            return StatusType::exceeded_max_length;
-        if (target_length > max_t_)
-            return StatusType::exceeded_max_length;
+        const int32_t n     = int32_t(alignments_.size());
+        const StatusType ok = can_add(n, query_length, target_length);
+        if (ok != StatusType::success)
+            return ok;
         char* qd = h_seqs_.as<char>() + size_t(2 * n) * stride_;
         char* td = h_seqs_.as<char>() + size_t(2 * n + 1) * stride_;
         if (rc_query)
@@ -303,6 +297,57 @@ public:
         auto a = std::make_shared<AlignmentImpl>(qd, query_length, td, target_length);
         a->set_alignment_type(AlignmentType::global_alignment);
         alignments_.push_back(a);
+        return StatusType::success;
+    }
+
+    // The overlap regions of `count` overlaps added from reads resident on this
+    // aligner's device (not part of the Aligner interface: aligner_resident.hpp).
+    // Lengths and statuses are checked on the host as add_alignment checks
+    // them, all before anything is added; the sequences are written into the
+    // device buffer by gather_overlap_regions_kernel on the aligner's stream,
+    // so the Alignment objects carry no sequence copies and the uploads skip
+    // the sequence buffer for this batch.  The caller has checked the overlaps
+    // against the reads (gwamd::mapper::check_overlaps).
+    StatusType add_device_overlaps(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target,
+                                   const gwamd::mapper::OverlapRecord* overlaps, int32_t count)
+    {
+        if (count < 0 || (!alignments_.empty() && !device_added_))
+            return StatusType::generic_error;
+        if (query.device_id != device_id_ || target.device_id != device_id_)
+            return StatusType::generic_error;
+        const int32_t n = int32_t(alignments_.size());
+        for (int32_t k = 0; k < count; k++)
+        {
+            const gwamd::mapper::OverlapRecord& o = overlaps[k];
+            const StatusType ok = can_add(n + k, int32_t(o.query_end - o.query_start),
+                                          int32_t(o.target_end - o.target_start));
+            if (ok != StatusType::success)
+                return ok;
+        }
+        if (count == 0)
+            return StatusType::success;
+        ScopedDevice dev(device_id_);
+        // the records of every device-added range of the batch stay until reset(): the gather reads them in stream order
+        d_records_.emplace_back(size_t(count), nullptr);
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_records_.back().data(), overlaps,
+                                       size_t(count) * sizeof(gwamd::mapper::OverlapRecord), hipMemcpyHostToDevice,
+                                       stream_));
+        gwamd::mapper::gather_overlap_regions(d_seqs_.data() + size_t(2 * n) * stride_, d_lens_.data() + 2 * n,
+                                              d_records_.back().data(), count, stride_, query, target, stream_);
+        // (the pageable source is staged before hipMemcpyAsync returns only for small copies: wait for it)
+        GWAMD_HIP_CHECK(hipStreamSynchronize(stream_));
+        for (int32_t k = 0; k < count; k++)
+        {
+            const int32_t ql = int32_t(overlaps[k].query_end - overlaps[k].query_start);
+            const int32_t tl = int32_t(overlaps[k].target_end - overlaps[k].target_start);
+            h_lens_.as<int32_t>()[2 * (n + k)]     = ql;
+            h_lens_.as<int32_t>()[2 * (n + k) + 1] = tl;
+            max_diff_ = std::max(max_diff_, std::abs(ql - tl));
+            auto a = std::make_shared<AlignmentImpl>("", 0, "", 0);
+            a->set_alignment_type(AlignmentType::global_alignment);
+            alignments_.push_back(a);
+        }
+        device_added_ = true;
         return StatusType::success;
     }
 
@@ -344,9 +389,10 @@ public:
             chunk0_[k + 1]   = i0 + c;
             GWAMD_HIP_CHECK(hipMemcpyAsync(d_lens_.data() + 2 * size_t(i0), h_lens_.as<int32_t>() + 2 * size_t(i0),
                                            2 * size_t(c) * 4, hipMemcpyHostToDevice, pipe_->s_in));
-            GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.data() + 2 * size_t(i0) * stride_,
-                                           h_seqs_.as<char>() + 2 * size_t(i0) * stride_, 2 * size_t(c) * stride_,
-                                           hipMemcpyHostToDevice, pipe_->s_in));
+            if (!device_added_) // (device-added: already gathered on stream_, before ev_fork)
+                GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.data() + 2 * size_t(i0) * stride_,
+                                               h_seqs_.as<char>() + 2 * size_t(i0) * stride_,
+                                               2 * size_t(c) * stride_, hipMemcpyHostToDevice, pipe_->s_in));
             GWAMD_HIP_CHECK(hipEventRecord(pipe_->ev_h[k], pipe_->s_in));
         }
         for (int k = 0; k < stages_; k++)
@@ -460,6 +506,14 @@ public:
         alignments_.clear();
         max_diff_ = 0;
         stages_   = 0; // no launch of this batch yet
+        if (device_added_)
+        {
+            // a gather of the batch may still read its records
+            ScopedDevice dev(device_id_);
+            (void)hipStreamSynchronize(stream_);
+            d_records_.clear();
+            device_added_ = false;
+        }
     }
 
     // bench / C ABI helpers: the split path (upload, launch, download) runs
@@ -474,8 +528,9 @@ public:
         chunk0_[0]     = 0;
         chunk0_[1]     = int32_t(n);
         GWAMD_HIP_CHECK(hipMemcpyAsync(d_lens_.data(), h_lens_.as<int32_t>(), 2 * n * 4, hipMemcpyHostToDevice, stream_));
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.data(), h_seqs_.as<char>(), 2 * n * size_t(stride_), hipMemcpyHostToDevice,
-                                       stream_));
+        if (!device_added_)
+            GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.data(), h_seqs_.as<char>(), 2 * n * size_t(stride_),
+                                           hipMemcpyHostToDevice, stream_));
     }
     void launch()
     {
@@ -551,6 +606,24 @@ public:
 private:
     int32_t ukkonen_max_difference() const { return gwamd::aln::ukkonen_max_difference(max_t_); }
 
+    // whether a pair of these lengths can be the n-th of the batch
+    StatusType can_add(int32_t n, int32_t query_length, int32_t target_length) const
+    {
+        // AlignerGlobalUkkonen::add_alignment (aligner_global_ukkonen.cpp:47-57)
+        if (algo_ == GWAMD_ALIGNER_UKKONEN && std::abs(query_length - target_length) > ukkonen_max_difference())
+            return StatusType::exceeded_max_alignment_difference;
+        // aligner_global.cpp:60-118
+        if (query_length < 0 || target_length < 0)
+            return StatusType::generic_error;
+        if (n >= max_n_)
+            return StatusType::exceeded_max_alignments;
+        if (query_length > max_q_)
+            return StatusType::exceeded_max_length;
+        if (target_length > max_t_)
+            return StatusType::exceeded_max_length;
+        return StatusType::success;
+    }
+
     // the planned layout with this aligner's arrays, for the whole batch
     gwamd::aln::Args args() const
     {
@@ -591,6 +664,7 @@ private:
     int32_t slots_ = 1; // slot_plan_.slots, or as many as the allocator's pool had room for
     int32_t stride_ = 0, max_result_ = 0;
     int32_t max_diff_ = 0; // largest |query - target| of the batch
+    bool device_added_ = false; // the batch's sequences were gathered on the device: no upload of h_seqs_
     // stages of the last align_all() (0: none yet) and their first pairs
     int stages_                                 = 0;
     int32_t chunk0_[gwamd::aln::kMaxStages + 1] = {};
@@ -603,6 +677,7 @@ private:
     gwamd::host::DevBuf<uint8_t> d_ws_;
     gwamd::host::DevBuf<unsigned long long> d_stats_;
     gwamd::host::DevBuf<int32_t> d_spec_ed_; // banded Myers: distances of the sweeps run ahead
+    std::vector<gwamd::host::DevBuf<gwamd::mapper::OverlapRecord>> d_records_; // of the device-added ranges
     std::unique_ptr<Pipeline> pipe_;
     PinnedBuf h_seqs_, h_lens_, h_paths_, h_plen_;
     std::vector<std::shared_ptr<Alignment>> alignments_;
@@ -646,6 +721,23 @@ std::unique_ptr<Aligner> create_aligner(int32_t max_query_length, int32_t max_ta
 } // namespace cudaaligner
 } // namespace genomeworks
 } // namespace claraparabricks
+
+namespace gwamd
+{
+namespace aln
+{
+claraparabricks::genomeworks::cudaaligner::StatusType
+add_device_overlaps(claraparabricks::genomeworks::cudaaligner::Aligner& aligner, const gwamd::mapper::DeviceReads& query,
+                    const gwamd::mapper::DeviceReads& target, const gwamd::mapper::OverlapRecord* overlaps,
+                    int32_t count)
+{
+    auto* impl = dynamic_cast<claraparabricks::genomeworks::cudaaligner::AlignerGlobalHip*>(&aligner);
+    if (!impl)
+        throw std::invalid_argument("add_device_overlaps: not an aligner of create_aligner");
+    return impl->add_device_overlaps(query, target, overlaps, count);
+}
+} // namespace aln
+} // namespace gwamd
 
 // ===========================================================================
 // C ABI (include/gwamd_cudaaligner.h)

@@ -1,5 +1,6 @@
 // What the C ABI entry points of include/gwamd_cudamapper.h share
-// (mapper_batch.cpp, mapper_rescue_host.cpp): the error convention, the checks of
+// (mapper_batch.cpp, mapper_rescue_host.cpp, mapper_reads.cpp, mapper_batcher.cpp,
+// mapper_index_cache.cpp): the error convention, the checks of
 // packed reads and the hand-over of overlaps in a library-owned array.
 #pragma once
 

@@ -1,6 +1,7 @@
 // Host-side declarations shared by the minimizer index, the matcher, the
 // overlapper and the end rescue (mapper_index.hip, mapper_match.hip, mapper_overlap.hip,
-// mapper_rescue.hip, mapper_batch.cpp, mapper_rescue_host.cpp).
+// mapper_rescue.hip, mapper_batch.cpp, mapper_rescue_host.cpp).  Reads resident
+// on the device and the gather of overlap regions: mapper_reads.hpp.
 #pragma once
 
 #include "host_common.hpp"

@@ -23,6 +23,7 @@
 // An end that a round refused, or accepted with nothing to add, meets the
 // same windows in the next round; it is left out of the later rounds.
 #include "mapper_prims.hpp"
+#include "mapper_reads.hpp"
 
 namespace gwamd
 {
@@ -241,6 +242,23 @@ void rescue_overlap_ends(OverlapRecord* overlaps, int64_t n, const ReadSet& quer
         query_bases.data(), query_offsets.data(), one_side ? query_bases.data() : target_bases.data(),
         one_side ? query_offsets.data() : target_offsets.data(), reinterpret_cast<uint32_t*>(records.data()),
         uint32_t(n), uint32_t(extension), required_similarity);
+    check_launch();
+    GWAMD_HIP_CHECK(
+        hipMemcpyAsync(overlaps, records.data(), size_t(n) * sizeof(OverlapRecord), hipMemcpyDeviceToHost, stream));
+    GWAMD_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// The same kernel on reads that are already on the device: the records go up and come back.
+void rescue_overlap_ends(OverlapRecord* overlaps, int64_t n, const DeviceReads& query, const DeviceReads& target,
+                         int extension, float required_similarity, const Budget& budget, hipStream_t stream)
+{
+    DevBuf<OverlapRecord> records;
+    upload(records, overlaps, size_t(n), budget, stream);
+    const unsigned blocks = unsigned((n + kWaves - 1) / kWaves);
+    rescue_kernel<<<blocks, kThreads, 0, stream>>>(query.bases(), query.d_offsets.data(), target.bases(),
+                                                   target.d_offsets.data(),
+                                                   reinterpret_cast<uint32_t*>(records.data()), uint32_t(n),
+                                                   uint32_t(extension), required_similarity);
     check_launch();
     GWAMD_HIP_CHECK(
         hipMemcpyAsync(overlaps, records.data(), size_t(n) * sizeof(OverlapRecord), hipMemcpyDeviceToHost, stream));

@@ -13,7 +13,9 @@
 
 #include "../../include/gwamd_cudaaligner.h"
 #include "../../include/gwamd_cudamapper.h"
+#include "aligner_resident.hpp"
 #include "host_common.hpp"
+#include "mapper_reads.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -152,15 +154,21 @@ struct Region
 };
 
 using RegionFn = std::function<Region(int32_t)>;
+// Adds the pairs [start, end) of the list an engine works on to its aligner in
+// one step (reads resident on the device); without one, the pairs are added
+// one by one from the host pointers of their regions.
+using AddRangeFn = std::function<cudaaligner::StatusType(cudaaligner::Aligner&, int32_t, int32_t)>;
 
 void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, int32_t num_alignment_engines,
-                    const RegionFn& region, std::vector<std::string>& cigars);
+                    const RegionFn& region, std::vector<std::string>& cigars, const AddRangeFn* add_range);
 
 // Overlaps longer than the aligner's limits (gwamd_aligner_max_lengths; the
 // reference has none) are left without a CIGAR, with a warning on stderr, so
 // one long overlap does not fail the whole call; the others are aligned by an
 // aligner sized for them (main.cu:125-175 sizes it by the longest overlap).
-void run_engines(int32_t n, int32_t num_alignment_engines, const RegionFn& region, std::vector<std::string>& cigars)
+// kept_out (may be null) receives the indices of the overlaps that are aligned, which is what add_range counts in.
+void run_engines(int32_t n, int32_t num_alignment_engines, const RegionFn& region, std::vector<std::string>& cigars,
+                 const AddRangeFn* add_range = nullptr, std::vector<int32_t>* kept_out = nullptr)
 {
     if (num_alignment_engines < 1)
         throw std::runtime_error("num_alignment_engines must be at least 1");
@@ -182,16 +190,18 @@ void run_engines(int32_t n, int32_t num_alignment_engines, const RegionFn& regio
         std::cerr << "align_overlaps: " << n - int32_t(kept.size())
                   << " overlap(s) longer than the aligner's limits (query " << lim_q << ", target " << lim_t
                   << " bases) left without a CIGAR" << std::endl;
+    if (kept_out)
+        *kept_out = kept;
     std::vector<std::string> kept_cigars;
     run_engines_on(int32_t(kept.size()), max_q, max_t, num_alignment_engines,
-                   [&](int32_t k) { return region(kept[size_t(k)]); }, kept_cigars);
+                   [&](int32_t k) { return region(kept[size_t(k)]); }, kept_cigars, add_range);
     cigars.assign(size_t(n), std::string());
     for (size_t k = 0; k < kept.size(); k++)
         cigars[size_t(kept[k])] = std::move(kept_cigars[k]);
 }
 
 void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, int32_t num_alignment_engines,
-                    const RegionFn& region, std::vector<std::string>& cigars)
+                    const RegionFn& region, std::vector<std::string>& cigars, const AddRangeFn* add_range)
 {
     cigars.assign(size_t(n), std::string());
     if (n == 0)
@@ -243,7 +253,13 @@ void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, 
                     end   = int32_t(std::min<int64_t>(int64_t(start) + batch_size, n));
                     next  = end;
                 }
-                for (int32_t i = start; i < end; i++)
+                if (add_range)
+                {
+                    const cudaaligner::StatusType st = (*add_range)(*aligner, start, end);
+                    if (st != cudaaligner::StatusType::success)
+                        throw std::runtime_error("Experienced error type " + std::to_string(int(st)));
+                }
+                for (int32_t i = start; i < end && !add_range; i++)
                 {
                     const Region r = region(i);
                     const cudaaligner::StatusType st =
@@ -347,6 +363,74 @@ void align_overlaps(DefaultDeviceAllocator /*allocator*/, std::vector<Overlap>& 
                                   o.relative_strand == RelativeStrand::Reverse};
                 },
                 cigars);
+}
+
+namespace
+{
+
+// align_overlaps on n checked records whose reads are resident on the current device
+void align_resident(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target,
+                    const gwamd::mapper::OverlapRecord* records, int32_t n, int32_t num_alignment_engines,
+                    std::vector<std::string>& cigars)
+{
+    std::vector<gwamd::mapper::OverlapRecord> kept_records; // the overlaps within the aligner's limits, in order
+    std::vector<int32_t> kept;
+    bool packed = false;
+    std::mutex pack_mtx;
+    const AddRangeFn add_range = [&](cudaaligner::Aligner& aligner, int32_t start, int32_t end) {
+        {
+            std::lock_guard<std::mutex> lk(pack_mtx);
+            if (!packed)
+            {
+                kept_records.reserve(kept.size());
+                for (int32_t i : kept)
+                    kept_records.push_back(records[i]);
+                packed = true;
+            }
+        }
+        return gwamd::aln::add_device_overlaps(aligner, query, target, kept_records.data() + start, end - start);
+    };
+    run_engines(n, num_alignment_engines,
+                [&](int32_t i) {
+                    const gwamd::mapper::OverlapRecord& o = records[i];
+                    return Region{nullptr, int32_t(o.query_end - o.query_start), nullptr,
+                                  int32_t(o.target_end - o.target_start), o.relative_strand == '-'};
+                },
+                cigars, &add_range, &kept);
+}
+
+void check_reads_on_current_device(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target)
+{
+    int current = -1;
+    GWAMD_HIP_CHECK(hipGetDevice(&current));
+    if (query.device_id != current || target.device_id != current)
+        throw std::invalid_argument("the reads are on device " + std::to_string(query.device_id) + " and " +
+                                    std::to_string(target.device_id) + ", the current device is " +
+                                    std::to_string(current));
+}
+
+} // namespace
+
+void align_overlaps(DefaultDeviceAllocator /*allocator*/, std::vector<Overlap>& overlaps,
+                    const DeviceReads& query_reads, const DeviceReads& target_reads, int32_t num_alignment_engines,
+                    std::vector<std::string>& cigars)
+{
+    if (overlaps.size() > size_t(INT32_MAX))
+        throw std::invalid_argument("too many overlaps for one call");
+    const gwamd::mapper::DeviceReads& query  = *query_reads.impl().reads;
+    const gwamd::mapper::DeviceReads& target = *target_reads.impl().reads;
+    static_assert(sizeof(Overlap) == sizeof(gwamd::mapper::OverlapRecord), "overlaps are copied as bytes");
+    std::vector<gwamd::mapper::OverlapRecord> records(overlaps.size());
+    if (!overlaps.empty())
+        std::memcpy(static_cast<void*>(records.data()), overlaps.data(), overlaps.size() * sizeof(Overlap));
+    gwamd::mapper::check_overlaps(query, target, records.data(), int64_t(records.size()));
+    if (num_alignment_engines < 1)
+        throw std::runtime_error("num_alignment_engines must be at least 1");
+    cigars.clear();
+    if (records.empty())
+        return;
+    check_reads_on_current_device(query, target);
+    align_resident(query, target, records.data(), int32_t(records.size()), num_alignment_engines, cigars);
 }
 
 std::string format_paf(const std::vector<Overlap>& overlaps, const std::vector<std::string>& cigars,
@@ -479,6 +563,39 @@ int32_t gwamd_align_overlaps(const char* query_bases, const int64_t* query_offse
                                               o.relative_strand == cm::RelativeStrand::Reverse};
                         },
                         list->items);
+        *cigars = list.release();
+        return 0;
+    });
+}
+
+int32_t gwamd_align_overlaps_resident(const gwamd_device_reads* query_reads, const gwamd_device_reads* target_reads,
+                                      const gwamd_overlap* overlaps, int32_t n, int32_t num_alignment_engines,
+                                      gwamd_text_list** cigars)
+{
+    if (cigars)
+        *cigars = nullptr;
+    return guarded_cm([&] {
+        if (!cigars)
+            throw std::invalid_argument("cigars is NULL");
+        if (!query_reads || !target_reads)
+            throw std::invalid_argument("query_reads or target_reads is NULL");
+        if (n < 0)
+            throw std::invalid_argument("the number of overlaps must not be negative");
+        if (n > 0 && !overlaps)
+            throw std::invalid_argument("overlaps is NULL");
+        std::vector<gwamd::mapper::OverlapRecord> records(static_cast<size_t>(n));
+        if (n > 0)
+            std::memcpy(static_cast<void*>(records.data()), overlaps, size_t(n) * sizeof(gwamd_overlap));
+        gwamd::mapper::check_overlaps(*query_reads->reads, *target_reads->reads, records.data(), n);
+        if (num_alignment_engines < 1)
+            throw std::runtime_error("num_alignment_engines must be at least 1");
+        auto list = std::make_unique<gwamd_text_list>();
+        if (n > 0)
+        {
+            cm::check_reads_on_current_device(*query_reads->reads, *target_reads->reads);
+            cm::align_resident(*query_reads->reads, *target_reads->reads, records.data(), n, num_alignment_engines,
+                               list->items);
+        }
         *cigars = list.release();
         return 0;
     });

@@ -9,6 +9,10 @@ representation, and get_overlaps chains sorted anchors into Overlap records
 (match_overlaps does both without bringing the anchors to the host).
 rescue_overlap_ends pushes the ends of overlaps out towards the read ends on
 the GPU; extend_overlap_by_sequence_similarity is one round of it on the host.
+DeviceReads puts a read set on the device once; rescue_overlap_ends and
+align_overlaps take it in place of the sequences.  group_reads_into_indices,
+generate_batches_of_indices and IndexHostCopy are the building blocks of the
+cudamapper tool's loop over index pairs (csrc/cudamapper_main.cpp).
 
 Overlaps are aligned with the MI355X global aligner (Hirschberg-Myers, the
 aligner create_aligner returns); a Reverse ('-') overlap aligns the query
@@ -106,6 +110,36 @@ def _declare(L):
     L.gwamd_rescue_overlap_ends.argtypes = rescue_args + [P(vp), P(i64)]
     L.gwamd_rescue_overlap_ends_with_allocator.restype = i32
     L.gwamd_rescue_overlap_ends_with_allocator.argtypes = rescue_args + [vp, P(vp), P(i64)]
+    L.gwamd_group_reads_into_indices.restype = i32
+    L.gwamd_group_reads_into_indices.argtypes = [vp, i32, i64, P(vp), P(i64)]
+    L.gwamd_index_descriptors_free.restype = None
+    L.gwamd_index_descriptors_free.argtypes = [vp]
+    L.gwamd_index_descriptor_hash.restype = C.c_uint64
+    L.gwamd_index_descriptor_hash.argtypes = [C.c_uint32, C.c_uint32]
+    L.gwamd_generate_batches_of_indices.restype = i32
+    L.gwamd_generate_batches_of_indices.argtypes = [i32, i32, i32, i32, vp, i32, vp, i32, i64, i64, i32, P(vp), P(i64)]
+    L.gwamd_batches_of_indices_free.restype = None
+    L.gwamd_batches_of_indices_free.argtypes = [vp]
+    L.gwamd_index_host_copy_create.restype = i32
+    L.gwamd_index_host_copy_create.argtypes = [vp, C.c_uint32, i32, i32, P(vp)]
+    L.gwamd_index_host_copy_to_device.restype = i32
+    L.gwamd_index_host_copy_to_device.argtypes = [vp, i32, vp, P(vp)]
+    L.gwamd_index_host_copy_info.restype = i32
+    L.gwamd_index_host_copy_info.argtypes = [vp, P(IndexInfo), P(C.c_uint32), P(i32), P(i32)]
+    L.gwamd_index_host_copy_free.restype = None
+    L.gwamd_index_host_copy_free.argtypes = [vp]
+    L.gwamd_device_reads_create.restype = i32
+    L.gwamd_device_reads_create.argtypes = [C.c_char_p, vp, i32, i32, vp, P(vp)]
+    L.gwamd_device_reads_free.restype = None
+    L.gwamd_device_reads_free.argtypes = [vp]
+    L.gwamd_device_reads_info.restype = i32
+    L.gwamd_device_reads_info.argtypes = [vp, P(i64), P(i64), P(i32)]
+    L.gwamd_rescue_overlap_ends_resident.restype = i32
+    L.gwamd_rescue_overlap_ends_resident.argtypes = [vp, vp, vp, i64, i32, C.c_float, vp, P(vp), P(i64)]
+    L.gwamd_align_overlaps_resident.restype = i32
+    L.gwamd_align_overlaps_resident.argtypes = [vp, vp, vp, i32, i32, P(vp)]
+    L.gwamd_internal_gather_overlap_regions.restype = i32
+    L.gwamd_internal_gather_overlap_regions.argtypes = [vp, vp, vp, i64, i64, vp, vp]
     L.gwamd_extend_overlap_by_sequence_similarity.restype = i32
     L.gwamd_extend_overlap_by_sequence_similarity.argtypes = [P(Overlap), C.c_char_p, i64, C.c_char_p, i64, i32,
                                                               C.c_float]
@@ -146,11 +180,91 @@ def _take(L, handle):
         L.gwamd_text_list_free(handle)
 
 
+class DeviceReads:
+    """A read set resident on one device (gwamd_device_reads): the packed bases
+    and the offsets, uploaded once.  rescue_overlap_ends and align_overlaps take
+    one per side in place of the sequences and then move only the overlaps.
+
+    reads: sequences (str or bytes), or (name, sequence) records as read_fasta
+    returns them.  allocator: a cudaaligner.DeviceAllocator whose pool the
+    device bytes are counted against until close()."""
+
+    def __init__(self, reads, device_id=0, allocator=None):
+        self._lib = load_library()
+        self._handle = C.c_void_p()
+        seqs = [r[1] if isinstance(r, tuple) else r for r in reads]
+        bases, offsets = _pack(seqs)
+        _check(self._lib.gwamd_device_reads_create(bases, offsets, len(seqs), int(device_id),
+                                                   allocator._handle if allocator is not None else None,
+                                                   C.byref(self._handle)))
+        self._allocator = allocator  # the handle holds bytes of its pool
+        n, b, d = C.c_int64(), C.c_int64(), C.c_int32()
+        _check(self._lib.gwamd_device_reads_info(self._handle, C.byref(n), C.byref(b), C.byref(d)))
+        self.number_of_reads, self.number_of_basepairs, self.device_id = n.value, b.value, d.value
+
+    def __len__(self):
+        return self.number_of_reads
+
+    def close(self):
+        """Frees the device memory."""
+        h, self._handle = self._handle, C.c_void_p()
+        if h:
+            self._lib.gwamd_device_reads_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _handles(query_reads, target_reads):
+    """The two handles when both sides are DeviceReads, None when neither is."""
+    resident = [isinstance(r, DeviceReads) for r in (query_reads, target_reads)]
+    if not any(resident):
+        return None
+    if not all(resident):
+        raise TypeError("query_reads and target_reads must both be DeviceReads, or neither")
+    if not query_reads._handle or not target_reads._handle:
+        raise ValueError("DeviceReads is closed")
+    return query_reads._handle, target_reads._handle
+
+
+def gather_overlap_regions(overlaps, query_reads, target_reads, stride):
+    """Test hook: gather_overlap_regions_kernel on two DeviceReads.  Returns
+    (seqs, lens): 2 n stride bytes with overlap i's query region at 2 i stride
+    and its target region (reverse-complemented for '-') at (2 i + 1) stride,
+    and the 2 n lengths.  Bytes past a region's length are not defined."""
+    L = load_library()
+    q, t = _handles(query_reads, target_reads)
+    arr = _overlap_array(overlaps)
+    n = len(overlaps)
+    seqs = np.zeros(max(2 * n * max(int(stride), 0), 1), np.uint8)
+    lens = np.zeros(max(2 * n, 1), np.int32)
+    _check(L.gwamd_internal_gather_overlap_regions(q, t, arr, n, int(stride), seqs.ctypes.data_as(C.c_void_p),
+                                                   lens.ctypes.data_as(C.c_void_p)))
+    return seqs[:2 * n * int(stride)].tobytes(), lens[:2 * n].tolist()
+
+
 def align_overlaps(overlaps, query_reads, target_reads, num_alignment_engines=1, device_id=0):
     """CIGAR of every overlap (align_overlaps, main.cu:125-175).
 
-    query_reads / target_reads: sequences indexed by the overlaps' read ids."""
+    query_reads / target_reads: sequences indexed by the overlaps' read ids, or
+    two DeviceReads on the current device (device_id is then not looked at):
+    the regions are gathered into the aligner on the device."""
     L = load_library()
+    handles = _handles(query_reads, target_reads)
+    if handles:
+        arr = _overlap_array(overlaps)
+        h = C.c_void_p()
+        _check(L.gwamd_align_overlaps_resident(*handles, arr, len(overlaps), num_alignment_engines, C.byref(h)))
+        return _take(L, h)
     qb, qo = _pack(query_reads)
     tb, to = _pack(target_reads)
     arr = _overlap_array(overlaps)
@@ -227,6 +341,19 @@ class Index:
             self._allocator = allocator  # the index holds bytes of its pool
         else:
             _check(self._lib.gwamd_index_create(*args, C.byref(self._handle)))
+        self._download()
+
+    @classmethod
+    def _from_handle(cls, handle, allocator=None):
+        """An Index around a gwamd_index the library made (IndexHostCopy.copy_index_to_device)."""
+        self = cls.__new__(cls)
+        self._lib = load_library()
+        self._handle = handle
+        self._allocator = allocator
+        self._download()
+        return self
+
+    def _download(self):
         try:
             info = IndexInfo()
             _check(self._lib.gwamd_index_info(self._handle, C.byref(info)))
@@ -379,16 +506,24 @@ def rescue_overlap_ends(overlaps, query_reads, target_reads, extension=100, requ
     Reverse overlap against the reverse complement of its target.
 
     query_reads / target_reads: sequences indexed by the overlaps' read ids;
-    one object given for both is uploaded once.  Unlike the reference, which
+    one object given for both is uploaded once.  Two DeviceReads on the current
+    device (device_id is then not looked at) are read where they lie.  Unlike the reference, which
     runs every round with 100 and 0.9 whatever it is given, extension (0..128)
     and required_similarity are honoured.  Returns a new list of Overlap.
     ValueError for a read id or a position beyond its read, a strand other
     than '+' and '-', an extension out of range and a NaN similarity."""
     L = load_library()
-    qb, qo = _pack(query_reads)
-    tb, to = (qb, qo) if target_reads is query_reads else _pack(target_reads)
+    handles = _handles(query_reads, target_reads)
     arr = _overlap_array(overlaps)
     p, n = C.c_void_p(), C.c_int64()
+    if handles:
+        _check(L.gwamd_rescue_overlap_ends_resident(*handles, arr, len(overlaps), int(extension),
+                                                    float(required_similarity),
+                                                    allocator._handle if allocator is not None else None,
+                                                    C.byref(p), C.byref(n)))
+        return _take_overlaps(L, p, n)
+    qb, qo = _pack(query_reads)
+    tb, to = (qb, qo) if target_reads is query_reads else _pack(target_reads)
     args = [qb, qo, len(query_reads), tb, to, len(target_reads), arr, len(overlaps), int(extension),
             float(required_similarity), int(device_id)]
     if allocator is not None:
@@ -411,3 +546,118 @@ def extend_overlap_by_sequence_similarity(overlap, query, target, extension, req
     _check(L.gwamd_extend_overlap_by_sequence_similarity(C.byref(o), q, len(q), t, len(t), int(extension),
                                                          float(required_similarity)))
     return o
+
+
+def _lengths(reads):
+    """A C array of the lengths of reads: sequences, (name, sequence) records or lengths."""
+    values = [r if isinstance(r, int) else len(r[1] if isinstance(r, tuple) else r) for r in reads]
+    return (C.c_int64 * max(len(values), 1))(*values), len(values)
+
+
+def index_descriptor_hash(first_read, number_of_reads):
+    """IndexDescriptor::get_hash (index_descriptor.cpp:43-59)."""
+    return int(load_library().gwamd_index_descriptor_hash(int(first_read), int(number_of_reads)))
+
+
+def group_reads_into_indices(reads, max_basepairs_per_index=1000000):
+    """(first_read, number_of_reads) of the indices the reads are cut into
+    (group_reads_into_indices, index_descriptor.cpp:76-109): consecutive reads
+    while their basepairs stay within the limit.  reads: sequences, (name,
+    sequence) records or lengths.  As in the reference the first descriptor is
+    (0, 0) when read 0 alone is over the limit."""
+    L = load_library()
+    arr, n = _lengths(reads)
+    p, count = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_group_reads_into_indices(arr, n, int(max_basepairs_per_index), C.byref(p), C.byref(count)))
+    try:
+        flat = (C.c_uint32 * (2 * count.value)).from_address(p.value) if count.value else []
+        return [(flat[2 * i], flat[2 * i + 1]) for i in range(count.value)]
+    finally:
+        L.gwamd_index_descriptors_free(p)
+
+
+def generate_batches_of_indices(query_indices_per_host_batch, query_indices_per_device_batch,
+                                target_indices_per_host_batch, target_indices_per_device_batch, query_reads,
+                                target_reads, query_basepairs_per_index, target_basepairs_per_index,
+                                same_query_and_target):
+    """generate_batches_of_indices (index_batcher.cu:24-88).  Returns a list of
+    host batches, each a dict of "query" and "target" (lists of (first_read,
+    number_of_reads)) and "device_batches" (a list of such dicts without
+    device batches).  One parser on both sides is one object given for
+    query_reads and target_reads.  ValueError for the four mismatches under
+    same_query_and_target and for a number of indices per batch below 1."""
+    L = load_library()
+    q, nq = _lengths(query_reads)
+    t, nt = (q, nq) if target_reads is query_reads else _lengths(target_reads)
+    p, count = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_generate_batches_of_indices(
+        int(query_indices_per_host_batch), int(query_indices_per_device_batch), int(target_indices_per_host_batch),
+        int(target_indices_per_device_batch), q, nq, t, nt, int(query_basepairs_per_index),
+        int(target_basepairs_per_index), int(bool(same_query_and_target)), C.byref(p), C.byref(count)))
+    try:
+        flat = list((C.c_int64 * count.value).from_address(p.value))
+    finally:
+        L.gwamd_batches_of_indices_free(p)
+    at = [0]
+
+    def take():
+        at[0] += 1
+        return flat[at[0] - 1]
+
+    def descriptors():
+        return [(take(), take()) for _ in range(take())]
+
+    batches = []
+    for _ in range(take()):
+        batch = {"query": descriptors(), "target": descriptors()}
+        batch["device_batches"] = [{"query": descriptors(), "target": descriptors()} for _ in range(take())]
+        batches.append(batch)
+    assert at[0] == len(flat)
+    return batches
+
+
+class IndexHostCopy:
+    """A copy of an Index in host memory (IndexHostCopyBase::create_cache,
+    index.hpp:109-182), from which copy_index_to_device makes an Index again
+    without building it: equal to the original in every array and getter."""
+
+    def __init__(self, index, first_read_id, kmer_size, window_size):
+        self._lib = load_library()
+        self._handle = C.c_void_p()
+        if not index._handle:
+            raise ValueError("index is closed")
+        _check(self._lib.gwamd_index_host_copy_create(index._handle, int(first_read_id), int(kmer_size),
+                                                      int(window_size), C.byref(self._handle)))
+        info, first, k, w = IndexInfo(), C.c_uint32(), C.c_int32(), C.c_int32()
+        _check(self._lib.gwamd_index_host_copy_info(self._handle, C.byref(info), C.byref(first), C.byref(k),
+                                                    C.byref(w)))
+        self.num_elements = int(info.num_elements)
+        self.number_of_reads = int(info.number_of_reads)
+        self.number_of_basepairs_in_longest_read = int(info.number_of_basepairs_in_longest_read)
+        self.first_read_id, self.kmer_size, self.window_size = first.value, k.value, w.value
+
+    def copy_index_to_device(self, device_id=0, allocator=None):
+        if not self._handle:
+            raise ValueError("host copy is closed")
+        h = C.c_void_p()
+        _check(self._lib.gwamd_index_host_copy_to_device(self._handle, int(device_id),
+                                                         allocator._handle if allocator is not None else None,
+                                                         C.byref(h)))
+        return Index._from_handle(h, allocator)
+
+    def close(self):
+        h, self._handle = self._handle, C.c_void_p()
+        if h:
+            self._lib.gwamd_index_host_copy_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

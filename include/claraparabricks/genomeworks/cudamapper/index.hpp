@@ -20,6 +20,7 @@
 #include <climits>
 #include <cstdint>
 #include <memory>
+#include <vector>
 
 namespace claraparabricks
 {
@@ -70,6 +71,41 @@ public:
                                                const std::uint64_t kmer_size, const std::uint64_t window_size,
                                                const bool hash_representations  = true,
                                                const double filtering_parameter = 1.0, const hipStream_t stream = 0);
+};
+
+/// A copy of an Index in host memory, from which the index is put back on a
+/// device without being computed again (reference index.hpp:109-182,
+/// cudamapper/src/index_host_copy.cu).
+class IndexHostCopyBase
+{
+public:
+    virtual ~IndexHostCopyBase() = default;
+
+    /// An Index on the current device with the arrays and the getters of the
+    /// index the copy was made from; Matcher::create_matcher accepts it.  The
+    /// device bytes are counted against the allocator's pool, as in create_index.
+    virtual std::unique_ptr<Index> copy_index_to_device(DefaultDeviceAllocator allocator,
+                                                        const hipStream_t stream = 0) const = 0;
+
+    virtual const std::vector<representation_t>& representations() const = 0;
+    virtual const std::vector<read_id_t>& read_ids() const = 0;
+    virtual const std::vector<position_in_read_t>& positions_in_reads() const = 0;
+    virtual const std::vector<SketchElement::DirectionOfRepresentation>& directions_of_reads() const = 0;
+    virtual const std::vector<representation_t>& unique_representations() const = 0;
+    virtual const std::vector<std::uint32_t>& first_occurrence_of_representations() const = 0;
+    virtual read_id_t number_of_reads() const = 0;
+    virtual position_in_read_t number_of_basepairs_in_longest_read() const = 0;
+    /// the first_read_id given to create_cache
+    virtual read_id_t first_read_id() const = 0;
+    virtual std::uint64_t kmer_size() const = 0;
+    virtual std::uint64_t window_size() const = 0;
+
+    /// Copies the six arrays and the scalars of an index made by
+    /// Index::create_index (std::invalid_argument for any other) to the host.
+    static std::unique_ptr<IndexHostCopyBase> create_cache(const Index& index, const read_id_t first_read_id,
+                                                           const std::uint64_t kmer_size,
+                                                           const std::uint64_t window_size,
+                                                           const hipStream_t stream = 0);
 };
 
 } // namespace cudamapper

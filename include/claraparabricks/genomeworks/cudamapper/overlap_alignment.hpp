@@ -1,9 +1,10 @@
 // The cudamapper caller of the global aligner: base-level alignment of overlap
 // regions and PAF output (reference cudamapper/src/main.cu:48-175,
 // cudamapper/src/cudamapper_utils.cpp:30-112).  Indexing and matching are in
-// index.hpp and matcher.hpp; chaining anchors into overlaps is outside this build.
+// index.hpp and matcher.hpp, chaining anchors into overlaps in overlapper.hpp.
 #pragma once
 
+#include <claraparabricks/genomeworks/cudamapper/device_reads.hpp>
 #include <claraparabricks/genomeworks/cudamapper/types.hpp>
 #include <claraparabricks/genomeworks/io/fasta_parser.hpp>
 #include <claraparabricks/genomeworks/utils/allocator.hpp>
@@ -31,6 +32,16 @@ namespace cudamapper
 void align_overlaps(DefaultDeviceAllocator allocator, std::vector<Overlap>& overlaps,
                     const io::FastaParser& query_parser, const io::FastaParser& target_parser,
                     int32_t num_alignment_engines, std::vector<std::string>& cigars);
+
+/// The same on reads that are resident on the current device
+/// (device_reads.hpp): the overlap regions are gathered into each aligner's
+/// sequence buffer by a kernel, so no base crosses the bus.  Same engines, same
+/// batch sizing, same CIGARs, and the same rule for an overlap longer than the
+/// aligner's limits (no CIGAR, a warning).  Throws std::invalid_argument for
+/// an overlap outside its reads and for reads on another device.
+void align_overlaps(DefaultDeviceAllocator allocator, std::vector<Overlap>& overlaps, const DeviceReads& query_reads,
+                    const DeviceReads& target_reads, int32_t num_alignment_engines,
+                    std::vector<std::string>& cigars);
 
 /// Overlaps in PAF, one line each, with "\tcg:Z:<cigar>" when cigars is not
 /// empty (cudamapper_utils.cpp:30-112).  Column 10 is num_residues_ x

@@ -10,6 +10,7 @@
 // it is, like every letter other than A, C, G and T.
 #pragma once
 
+#include <claraparabricks/genomeworks/cudamapper/device_reads.hpp>
 #include <claraparabricks/genomeworks/cudamapper/types.hpp>
 #include <claraparabricks/genomeworks/io/fasta_parser.hpp>
 #include <claraparabricks/genomeworks/types.hpp>
@@ -79,6 +80,16 @@ public:
     /// beyond its read or a strand that is neither Forward nor Reverse.
     static void rescue_overlap_ends(std::vector<Overlap>& overlaps, const io::FastaParser& query_parser,
                                     const io::FastaParser& target_parser, std::int32_t extension,
+                                    float required_similarity);
+
+    /// The same on reads that are resident on the current device
+    /// (device_reads.hpp): only the overlaps are uploaded.  Unlike the parser
+    /// overload this one honours extension (0..128) and required_similarity.
+    /// The same object may stand on both sides.  Throws std::invalid_argument
+    /// also for an extension out of range, a NaN similarity and reads on
+    /// another device than the current one.
+    static void rescue_overlap_ends(std::vector<Overlap>& overlaps, const DeviceReads& query_reads,
+                                    const DeviceReads& target_reads, std::int32_t extension,
                                     float required_similarity);
 };
 

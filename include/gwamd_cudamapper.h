@@ -29,6 +29,17 @@
  *   gwamd_extend_overlap_by_sequence_similarity
  *                          details::overlapper::extend_overlap_by_sequence_similarity(
  *                          overlap, query, target, extension, required_similarity) overlapper.hpp:35-47
+ *   gwamd_group_reads_into_indices
+ *                          group_reads_into_indices(parser, max_basepairs_per_index) index_descriptor.hpp:80-87
+ *   gwamd_generate_batches_of_indices
+ *                          generate_batches_of_indices(...)                    index_batcher.cuh:102-110
+ *   gwamd_device_reads_create
+ *                          no counterpart: the reads of one parser put on the device
+ *                          once (DeviceReads::create, device_reads.hpp)
+ *   gwamd_rescue_overlap_ends_resident
+ *                          Overlapper::rescue_overlap_ends on two DeviceReads  overlapper.hpp:95-106
+ *   gwamd_align_overlaps_resident
+ *                          align_overlaps on two DeviceReads                   main.cu:125-175
  *
  * Reads are passed as one byte array per side with n+1 offsets (read i is
  * bases[offsets[i], offsets[i+1])); names as NUL-separated strings with n+1
@@ -266,6 +277,114 @@ int32_t gwamd_rescue_overlap_ends_with_allocator(const char* query_bases, const 
 int32_t gwamd_extend_overlap_by_sequence_similarity(gwamd_overlap* overlap, const char* query, int64_t query_len,
                                                     const char* target, int64_t target_len, int32_t extension,
                                                     float required_similarity);
+
+/* ---- index descriptors and batches of indices (host only) -------------------------
+ *
+ * An index descriptor is the range of reads one index is built from.  The
+ * reads are given by their lengths (0 <= length < 2^31); basepairs per index
+ * is below 2^32.  GWAMD_E_INVALID_ARGUMENT for those, for a negative count or
+ * a NULL array with a positive one, for a NULL output, for a number of indices
+ * per batch below 1, and for the four cases of generate_batches_of_indices with
+ * same_query_and_target != 0: the two sides differ in indices per host batch,
+ * in indices per device batch, in the parser (here: query_lengths and
+ * target_lengths are not the same pointer and count) or in basepairs per
+ * index. */
+typedef struct gwamd_index_descriptor
+{
+    uint32_t first_read;
+    uint32_t number_of_reads;
+} gwamd_index_descriptor;
+
+/* group_reads_into_indices(parser, max_basepairs_per_index) (index_descriptor.cpp:76-109), in a
+ * library-owned array (gwamd_index_descriptors_free).  As there, the first descriptor is {0, 0}
+ * when read 0 alone is over the limit, and no reads give the one descriptor {0, 0}. */
+int32_t gwamd_group_reads_into_indices(const int64_t* lengths, int32_t n, int64_t max_basepairs,
+                                       gwamd_index_descriptor** descriptors, int64_t* count);
+void gwamd_index_descriptors_free(gwamd_index_descriptor* descriptors);
+/* IndexDescriptor::get_hash (index_descriptor.cpp:43-59): first_read | number_of_reads << 32 */
+uint64_t gwamd_index_descriptor_hash(uint32_t first_read, uint32_t number_of_reads);
+
+/* generate_batches_of_indices (index_batcher.cu:24-88), flattened into `count` 64-bit values in a
+ * library-owned array (gwamd_batches_of_indices_free).  With a list of descriptors written as its
+ * length followed by (first_read, number_of_reads) per descriptor, the array holds the number of
+ * host batches and then per host batch: its query descriptors, its target descriptors, the number
+ * of its device batches and, per device batch, its query and its target descriptors. */
+int32_t gwamd_generate_batches_of_indices(int32_t query_indices_per_host_batch, int32_t query_indices_per_device_batch,
+                                          int32_t target_indices_per_host_batch,
+                                          int32_t target_indices_per_device_batch, const int64_t* query_lengths,
+                                          int32_t num_queries, const int64_t* target_lengths, int32_t num_targets,
+                                          int64_t query_basepairs_per_index, int64_t target_basepairs_per_index,
+                                          int32_t same_query_and_target, int64_t** batches, int64_t* count);
+void gwamd_batches_of_indices_free(int64_t* batches);
+
+/* ---- host copy of an index ---------------------------------------------------------
+ *
+ * IndexHostCopyBase (reference index.hpp:109-182): the six arrays and the scalars of an
+ * index in host memory, from which the index goes back to a device without being built
+ * again.  The index that comes back equals the original in every array and getter and is
+ * accepted wherever a gwamd_index is.  GWAMD_E_INVALID_ARGUMENT for a NULL handle or
+ * output, a kmer_size outside 1..32, a window_size outside 1..255, a negative device_id. */
+typedef struct gwamd_index_host_copy gwamd_index_host_copy;
+
+/* IndexHostCopyBase::create_cache(index, first_read_id, kmer_size, window_size, stream) */
+int32_t gwamd_index_host_copy_create(const gwamd_index* index, uint32_t first_read_id, int32_t kmer_size,
+                                     int32_t window_size, gwamd_index_host_copy** out);
+/* copy_index_to_device(allocator, stream) on device_id; the bytes count against the pool (NULL: none) */
+int32_t gwamd_index_host_copy_to_device(const gwamd_index_host_copy* copy, int32_t device_id,
+                                        struct gwamd_device_allocator* allocator_or_null, gwamd_index** out);
+/* the sizes and getters of the copy (a NULL output other than info is skipped) */
+int32_t gwamd_index_host_copy_info(const gwamd_index_host_copy* copy, gwamd_index_info_t* info,
+                                   uint32_t* first_read_id, int32_t* kmer_size, int32_t* window_size);
+void gwamd_index_host_copy_free(gwamd_index_host_copy* copy);
+
+/* ---- reads resident on the device -----------------------------------------------
+ *
+ * The reference reads the parsers on the host in every call of
+ * rescue_overlap_ends and align_overlaps.  A gwamd_device_reads holds the
+ * packed bases and the n + 1 offsets of one read set on one device, uploaded
+ * once; the _resident entries below then move only the overlaps.  The bytes
+ * are counted against the allocator's pool (NULL: none) until the handle is
+ * freed.  The argument checks of gwamd_device_reads_create are those of the
+ * reads of gwamd_rescue_overlap_ends, and a negative device_id; the checks of
+ * the _resident entries are those of their host-read twins, with the lengths
+ * taken from the handle's host copy of the offsets, and in addition a NULL
+ * handle and a handle on another device than the current one, each
+ * GWAMD_E_INVALID_ARGUMENT.  The same handle may be given for both sides. */
+typedef struct gwamd_device_reads gwamd_device_reads;
+
+/* DeviceReads::create(allocator, parser, stream) (device_reads.hpp) on device_id */
+int32_t gwamd_device_reads_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t device_id,
+                                  struct gwamd_device_allocator* allocator_or_null, gwamd_device_reads** out);
+void gwamd_device_reads_free(gwamd_device_reads* reads);
+/* number of reads, of bases, and the device; a NULL output is skipped */
+int32_t gwamd_device_reads_info(const gwamd_device_reads* reads, int64_t* num_reads, int64_t* num_bases,
+                                int32_t* device_id);
+
+/* Overlapper::rescue_overlap_ends(overlaps, query_reads, target_reads, extension,
+ * required_similarity) (overlapper.hpp, the DeviceReads overload; reference overlapper.hpp:95-106) */
+int32_t gwamd_rescue_overlap_ends_resident(const gwamd_device_reads* query_reads,
+                                           const gwamd_device_reads* target_reads, const gwamd_overlap* overlaps,
+                                           int64_t n, int32_t extension, float required_similarity,
+                                           struct gwamd_device_allocator* allocator_or_null, gwamd_overlap** out,
+                                           int64_t* num_out);
+
+/* align_overlaps(allocator, overlaps, query_reads, target_reads, num_alignment_engines, cigars)
+ * (overlap_alignment.hpp, the DeviceReads overload; reference main.cu:125-175): the CIGARs of
+ * gwamd_align_overlaps, with the overlap regions gathered into the aligner on the device. */
+int32_t gwamd_align_overlaps_resident(const gwamd_device_reads* query_reads, const gwamd_device_reads* target_reads,
+                                      const gwamd_overlap* overlaps, int32_t n, int32_t num_alignment_engines,
+                                      gwamd_text_list** cigars);
+
+/* Test hook, not used by the library itself: gather_overlap_regions_kernel on n overlaps
+ * into a device buffer of 2 n stride bytes, copied to seqs_out (2 n stride bytes) and
+ * lens_out (2 n entries).  Overlap i's query region lies at seqs_out + 2 i stride, its target
+ * region, reverse-complemented for '-', at seqs_out + (2 i + 1) stride; bytes past a region's
+ * length are not defined.  Every argument is checked before any device call: NULL handles or
+ * outputs, a negative n, 2 n stride of 2^31 or more, overlaps outside their reads, a
+ * stride below 1 or shorter than a region.  n == 0 returns without a launch. */
+int32_t gwamd_internal_gather_overlap_regions(const gwamd_device_reads* query_reads,
+                                              const gwamd_device_reads* target_reads, const gwamd_overlap* overlaps,
+                                              int64_t n, int64_t stride, char* seqs_out, int32_t* lens_out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,227 @@
+"""The cudamapper command-line tool (claragenomicsanalysis_amd/lib/cudamapper,
+built from csrc/cudamapper_main.cpp; reference cudamapper/src/main.cu and
+application_parameters.cpp).
+
+CPU tests cover every check that ends before the device is touched.  GPU tests
+run the tool on a few reads cut from one random genome and compare its PAF,
+as a sorted list of lines (writer threads interleave index pairs), with the
+text composed here from the batches of tests/index_batcher_model.py and the
+package's own calls on host reads, in the tool's stage order: match and chain,
+fuse, rescue at 50 / 0.5, align, format."""
+import os
+import random
+import subprocess
+
+import pytest
+
+import index_batcher_model as batcher
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "claragenomicsanalysis_amd", "lib", "cudamapper")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+READS = os.path.join(GOLDEN, "20_reads.fasta")
+LONG_OPTIONS = ["--kmer-size", "--window-size", "--num-devices", "--max-cached-memory", "--index-size",
+                "--target-index-size", "--filtering-parameter", "--alignment-engines", "--min-residues",
+                "--min-overlap-length", "--min-bases-per-residue", "--min-overlap-fraction", "--rescue-overlap-ends",
+                "--drop-fused-overlaps", "--query-indices-in-host-memory", "--query-indices-in-device-memory",
+                "--target-indices-in-host-memory", "--target-indices-in-device-memory", "--version", "--help"]
+
+
+def run(args, env=None, timeout=120):
+    if not os.path.exists(CLI):
+        pytest.fail("cudamapper tool not built: run make -C claragenomicsanalysis_amd/csrc")
+    full = dict(os.environ)
+    full.update(env or {})
+    return subprocess.run([CLI] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout, env=full)
+
+
+# ---- checks that end before the device is touched ---------------------------------------------
+
+def test_help_exits_zero_and_names_every_long_option():
+    r = run(["-h"])
+    assert r.returncode == 0 and r.stdout == ""
+    for option in LONG_OPTIONS:
+        assert option in r.stderr, option
+    # the defaults of the reference, and what -R does here
+    for text in ("[15]", "[10]", "[30]", "[1e-5]", "[3]", "[250]", "[1000]", "[0.8]", "extension 50", "similarity 0.5"):
+        assert text in r.stderr, text
+    assert run(["--help"]).returncode == 0
+
+
+@pytest.mark.parametrize("args, message", [
+    (["-k", "33"], "kmer of size 33 is not allowed, maximum k = 32"),
+    (["-F", "1.5"], "--filtering-parameter must be in range [0.0, 1.0]"),
+    (["-F", "-0.1"], "--filtering-parameter must be in range [0.0, 1.0]"),
+    (["-m", "-1"], "--max-cached-memory must not be negative"),
+    (["-a", "-1"], "Number of alignment engines should be non-negative"),
+    (["-C", "2", "-c", "3"], "--target-indices-in-host-memory has to be larger or equal"),
+    (["-Q", "2", "-q", "3", "-C", "5", "-c", "1"], "--query-indices-in-host-memory has to be larger or equal"),
+    # the long option sets the target value (the reference's table maps it to -q)
+    (["-C", "2", "--target-indices-in-device-memory", "3"], "--target-indices-in-host-memory has to be larger or equal"),
+    (["-Q", "4", "-q", "2", "--target-indices-in-device-memory", "5"],
+     "--target-indices-in-host-memory has to be larger or equal"),
+])
+def test_invalid_options(args, message):
+    r = run(args + [READS, READS])
+    assert r.returncode != 0 and r.stdout == ""
+    assert message in r.stderr
+
+
+def test_fewer_than_two_files():
+    for args in ([], [READS], ["-k", "15"]):
+        r = run(args)
+        assert r.returncode != 0 and "Invalid inputs" in r.stderr and "Usage:" in r.stderr
+
+
+def test_a_missing_file(tmp_path):
+    r = run([READS, tmp_path / "missing.fasta"])
+    assert r.returncode != 0 and "missing.fasta" in r.stderr and r.stdout == ""
+    r = run([tmp_path / "missing.fasta", READS])
+    assert r.returncode != 0 and "missing.fasta" in r.stderr
+
+
+def test_equal_paths_switch_on_all_to_all(tmp_path):
+    # (without a device the run ends after the notes, with an error; with one it maps no reads:
+    # all of them are shorter than k + w - 1 and the parser drops them)
+    r = run([READS, READS])
+    assert "all_to_all" in r.stderr and "Query index size used for both files" in r.stderr
+    assert "-C / --target-indices-in-host-memory not set, using -Q" in r.stderr and ": 10" in r.stderr
+    assert "-c / --target-indices-in-device-memory not set, using -q" in r.stderr and ": 5" in r.stderr
+    assert "number of reads: 0" in r.stderr
+    other = os.path.join(GOLDEN, "10_reads.fasta")
+    r = run(["-C", "7", "-c", "7", other, READS])
+    assert "all_to_all" not in r.stderr and "not set" not in r.stderr
+    assert "10_reads.fasta, number of reads: 0" in r.stderr and "20_reads.fasta, number of reads: 0" in r.stderr
+
+
+# ---- the tool on the GPU --------------------------------------------------------------------------
+
+K, W = 15, 5
+COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def write_fasta(path, prefix, reads):
+    with open(path, "w") as f:
+        for i, s in enumerate(reads):
+            f.write(">%s%d some description\n" % (prefix, i))
+            for k in range(0, len(s), 70):
+                f.write(s[k:k + 70] + "\n")
+
+
+@pytest.fixture(scope="module")
+def files(tmp_path_factory):
+    """Fewer than 20 reads of 300 to 2,000 bases per file, cut from one random genome, both strands."""
+    rng = random.Random(77)
+    genome = "".join(rng.choice("ACGT") for _ in range(7000))
+    root = tmp_path_factory.mktemp("cudamapper")
+    paths = {}
+    for name, count in (("a", 16), ("b", 11)):
+        reads = []
+        for i in range(count):
+            length = rng.randint(300, 2000)
+            start = rng.randint(0, len(genome) - length)
+            read = genome[start:start + length]
+            reads.append(read[::-1].translate(COMPLEMENT) if i % 3 == 1 else read)
+        reads.append("ACGT" * 4)  # shorter than k + w - 1: the parser drops it
+        paths[name] = str(root / (name + ".fasta"))
+        write_fasta(paths[name], name, reads)
+    return paths
+
+
+def expected_lines(query_path, target_path, index_bases, target_index_bases, per, rescue=False, drop=False,
+                   engines=0):
+    from claragenomicsanalysis_amd import (Index, match_overlaps, post_process_overlaps, rescue_overlap_ends)
+    from claragenomicsanalysis_amd.cudamapper import align_overlaps, format_paf, read_fasta
+    same = query_path == target_path
+    queries = read_fasta(query_path, K + W - 1)
+    targets = queries if same else read_fasta(target_path, K + W - 1)
+    query_lengths = [len(s) for _, s in queries]
+    target_lengths = query_lengths if same else [len(s) for _, s in targets]
+    if same:
+        target_index_bases = index_bases
+    batches = batcher.generate_batches_of_indices(per[0], per[1], per[2], per[3], query_lengths, target_lengths,
+                                                  index_bases, target_index_bases, same)
+    query_seqs, target_seqs = [s for _, s in queries], [s for _, s in targets]
+    lines, pairs = [], 0
+    for batch in batches:
+        for device_batch in batch["device_batches"]:
+            for q in device_batch["query"]:
+                for t in device_batch["target"]:
+                    if same and t[0] < q[0]:  # the tool's skip rule
+                        continue
+                    pairs += 1
+                    with Index(queries, K, W, q[0], q[0] + q[1], True, 1.0) as qi, \
+                            Index(targets, K, W, t[0], t[0] + t[1], True, 1.0) as ti:
+                        overlaps = match_overlaps(qi, ti, 3, 250, 1000, 0.8)
+                    overlaps = post_process_overlaps(overlaps, drop)
+                    if rescue:
+                        overlaps = rescue_overlap_ends(overlaps, query_seqs, target_seqs, 50, 0.5)
+                    cigars = align_overlaps(overlaps, query_seqs, target_seqs, engines) if engines else None
+                    lines += format_paf(overlaps, cigars, queries, targets, K).splitlines()
+    return sorted(lines), pairs, len(batches)
+
+
+def tool_lines(query_path, target_path, options, env):
+    full = {"GWAMD_DIAG": "1"}
+    full.update({k: str(v) for k, v in env.items()})
+    r = run(["-k", K, "-w", W, "-F", "1.0"] + options + [query_path, target_path], env=full)
+    assert r.returncode == 0, r.stderr
+    return sorted(r.stdout.splitlines()), r.stderr
+
+
+@pytest.mark.gpu
+def test_one_index_per_side(files):
+    want, pairs, batches = expected_lines(files["a"], files["a"], 30000000, 30000000, (10, 5, 10, 5), rescue=True,
+                                          engines=2)
+    assert pairs == 1 and batches == 1 and len(want) > 10
+    got, log = tool_lines(files["a"], files["a"], ["-R", "-a", "2"], {})
+    assert got == want
+    assert "took batch 1 out of 1" in log and all("cg:Z:" in text for text in got)
+    assert {text.split("\t")[4] for text in got} == {"+", "-"}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("options, kw", [
+    ([], {}),
+    (["-R", "-D", "-a", "1"], dict(rescue=True, drop=True, engines=1)),
+], ids=["plain", "rescued-dropped-aligned"])
+def test_all_to_all_over_several_indices(files, options, kw):
+    per = (2, 1, 2, 1)
+    want, pairs, batches = expected_lines(files["a"], files["a"], 4000, 4000, per, **kw)
+    # the triangle: n (n + 1) / 2 pairs of n >= 3 indices, in several host batches
+    from claragenomicsanalysis_amd.cudamapper import read_fasta
+    n = len(batcher.group_reads_into_indices([len(s) for _, s in read_fasta(files["a"], K + W - 1)], 4000))
+    assert n >= 3 and pairs == n * (n + 1) // 2 and batches >= 3 and len(want) > 10
+    got, log = tool_lines(files["a"], files["a"], ["-Q", 2, "-q", 1] + options,
+                          {"GWAMD_MAPPER_INDEX_BASES": 4000, "GWAMD_MAPPER_TARGET_INDEX_BASES": 9999})
+    assert got == want
+    assert "out of %d batches" % batches in log
+    # without the diagnostic switch the override is not read: one index per side
+    r = run(["-k", K, "-w", W, "-F", "1.0", files["a"], files["a"]],
+            env={"GWAMD_DIAG": "0", "GWAMD_MAPPER_INDEX_BASES": "4000"})
+    assert r.returncode == 0 and "out of 1 batches" in r.stderr
+    if not options:
+        assert sorted(r.stdout.splitlines()) == expected_lines(files["a"], files["a"], 30000000, 30000000,
+                                                               (10, 5, 10, 5))[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("options, kw", [
+    (["-a", "1"], dict(engines=1)),
+    (["-R"], dict(rescue=True)),
+], ids=["aligned", "rescued"])
+def test_separate_query_and_target_files(files, options, kw):
+    per = (2, 1, 3, 2)
+    want, pairs, batches = expected_lines(files["a"], files["b"], 5000, 3000, per, **kw)
+    assert pairs >= 9 and batches >= 2 and len(want) > 10
+    got, log = tool_lines(files["a"], files["b"], ["-Q", 2, "-q", 1, "-C", 3, "-c", 2] + options,
+                          {"GWAMD_MAPPER_INDEX_BASES": 5000, "GWAMD_MAPPER_TARGET_INDEX_BASES": 3000})
+    assert got == want
+    assert "all_to_all" not in log
+
+
+@pytest.mark.gpu
+def test_more_devices_than_visible_is_an_error_before_any_work(files):
+    r = run(["-d", "4096", files["a"], files["a"]])
+    assert r.returncode != 0 and r.stdout == ""
+    assert "--num-devices" in r.stderr and "visible" in r.stderr and "took batch" not in r.stderr

@@ -240,7 +240,9 @@ def gather_overlap_regions(overlaps, query_reads, target_reads, stride):
     """Test hook: gather_overlap_regions_kernel on two DeviceReads.  Returns
     (seqs, lens): 2 n stride bytes with overlap i's query region at 2 i stride
     and its target region (reverse-complemented for '-') at (2 i + 1) stride,
-    and the 2 n lengths.  Bytes past a region's length are not defined."""
+    and the 2 n lengths.  The hook clears the device buffer before the launch
+    and the kernel writes nothing outside a region, so the bytes of a slot past
+    its region's length are zero."""
     L = load_library()
     q, t = _handles(query_reads, target_reads)
     arr = _overlap_array(overlaps)

@@ -378,8 +378,9 @@ int32_t gwamd_align_overlaps_resident(const gwamd_device_reads* query_reads, con
 /* Test hook, not used by the library itself: gather_overlap_regions_kernel on n overlaps
  * into a device buffer of 2 n stride bytes, copied to seqs_out (2 n stride bytes) and
  * lens_out (2 n entries).  Overlap i's query region lies at seqs_out + 2 i stride, its target
- * region, reverse-complemented for '-', at seqs_out + (2 i + 1) stride; bytes past a region's
- * length are not defined.  Every argument is checked before any device call: NULL handles or
+ * region, reverse-complemented for '-', at seqs_out + (2 i + 1) stride.  The hook clears the
+ * device buffer before the launch and the kernel writes nothing outside a region, so the
+ * bytes of a slot past its region's length are zero.  Every argument is checked before any device call: NULL handles or
  * outputs, a negative n, 2 n stride of 2^31 or more, overlaps outside their reads, a
  * stride below 1 or shorter than a region.  n == 0 returns without a launch. */
 int32_t gwamd_internal_gather_overlap_regions(const gwamd_device_reads* query_reads,

@@ -7,7 +7,9 @@ run the tool on a few reads cut from one random genome and compare its PAF,
 as a sorted list of lines (writer threads interleave index pairs), with the
 text composed here from the batches of tests/index_batcher_model.py and the
 package's own calls on host reads, in the tool's stage order: match and chain,
-fuse, rescue at 50 / 0.5, align, format."""
+fuse, rescue at 50 / 0.5, align, format.  One run on long reads is compared
+with the plain models of tests/ and the aligner oracle instead, so that a fault
+shared by the tool and the package's calls would show."""
 import os
 import random
 import subprocess
@@ -225,3 +227,83 @@ def test_more_devices_than_visible_is_an_error_before_any_work(files):
     r = run(["-d", "4096", files["a"], files["a"]])
     assert r.returncode != 0 and r.stdout == ""
     assert "--num-devices" in r.stderr and "visible" in r.stderr and "took batch" not in r.stderr
+
+
+# ---- long reads, against the plain models -------------------------------------------------------
+
+def _mutate(rng, s, err):
+    """Deletions, substitutions and insertions, err / 3 of each."""
+    out = []
+    for c in s:
+        r = rng.random()
+        if r < err / 3:
+            continue
+        if r < 2 * err / 3:
+            out.append(rng.choice("ACGT"))
+        elif r < err:
+            out.append(c + rng.choice("ACGT"))
+        else:
+            out.append(c)
+    return "".join(out)
+
+
+def _paf_line(o, cigar, names, lengths, k):
+    # the columns of format_paf_impl (csrc/overlap_align.cpp): name, length, start, end, strand, name,
+    # length, start, end, residues x k, the longer span, mapping quality 255, then the cg:Z: tag
+    q, t, qs, qe, ts, te, strand, residues, _ = o
+    columns = [names[q], lengths[q], qs, qe, strand, names[t], lengths[t], ts, te, residues * k,
+               max(abs(ts - te), abs(qs - qe)), 255]
+    assert len(columns) == 12
+    return "\t".join(str(c) for c in columns) + ("\tcg:Z:" + cigar if cigar else "")
+
+
+@pytest.mark.gpu
+def test_long_reads_against_the_models(tmp_path):
+    """Six reads of 6 to 14 kb, all-to-all with -R -a 2 and one index per side: most overlaps have
+    regions of more than one 4,096-byte piece of the gather kernel.  The expected lines come from
+    the plain models of tests/ and the aligner oracle, stage by stage in the tool's order, and
+    from no GPU call of the package (read_fasta, which gives the tool's read order, is host code).
+
+    The CIGARs of this project, like the reference's convert_to_cigar, write a mismatch as M, so
+    'a CIGAR with I, D and X' is asserted as: I and D in the text and a mismatch among the
+    oracle's states of that overlap."""
+    import mapper_model
+    import overlapper_model
+    import rescue_model
+    from claragenomicsanalysis_amd.cudamapper import read_fasta
+    from oracle import oracle
+    rng = random.Random(123)
+    genome = "".join(rng.choice("ACGT") for _ in range(30000))
+    reads = []
+    for i in range(6):
+        length = rng.randint(6000, 14000)
+        start = rng.randint(0, len(genome) - length)
+        read = _mutate(rng, genome[start:start + length], 0.02)
+        reads.append(read[::-1].translate(COMPLEMENT) if i % 3 == 1 else read)
+    path = str(tmp_path / "long.fasta")
+    write_fasta(path, "long", reads)
+
+    records = read_fasta(path, K + W - 1)  # the tool's read ids: the parser shuffles
+    names, seqs = [n for n, _ in records], [s for _, s in records]
+    assert sorted(seqs) == sorted(reads)
+    index = mapper_model.Index(seqs, K, W, 0, len(seqs), True, 1.0)
+    anchors = mapper_model.match_anchors(index, index)
+    overlaps, _ = overlapper_model.get_overlaps(anchors, 3, 250, 1000, 0.8)
+    overlaps = overlapper_model.post_process_overlaps(overlaps)
+    overlaps = rescue_model.rescue_overlap_ends(overlaps, seqs, seqs, 50, 0.5)
+    mq = max(o[3] - o[2] for o in overlaps)
+    want, long_strands, mixed = [], [], 0
+    for o in overlaps:
+        qr, tr = seqs[o[0]][o[2]:o[3]], seqs[o[1]][o[4]:o[5]]
+        states = oracle.align(qr, tr[::-1].translate(COMPLEMENT) if o[6] == "-" else tr, oracle.ALIGN_HM, mq)
+        cigar = oracle.cigar(states)
+        want.append(_paf_line(o, cigar, names, [len(s) for s in seqs], K))
+        if min(o[3] - o[2], o[5] - o[4]) > 4096:
+            long_strands.append(o[6])
+        mixed += "I" in cigar and "D" in cigar and 1 in states
+    # what the input is there for, from the models alone
+    assert len(long_strands) >= 6 and long_strands.count("-") >= 2 and mixed >= 1
+
+    got, log = tool_lines(path, path, ["-R", "-a", "2"], {})
+    assert got == sorted(want)
+    assert "took batch 1 out of 1" in log

@@ -2,13 +2,16 @@
 (DeviceReads): rescue_overlap_ends and align_overlaps give, overlap by overlap
 and field by field, what their host-read forms give on the same input; the
 CIGARs also equal the aligner oracle's.  Both are integer results, compared
-exactly.  The argument checks that need a handle, and so a device, are here
+exactly.  Regions of more than one 4,096-byte piece of the gather kernel, the
+long-mode aligner kernel and the pipelined align_all() on device-added pairs
+have sets of their own.  The argument checks that need a handle, and so a device, are here
 too; those that need none are in test_resident_capi.py."""
 import ctypes as C
 import random
 
 import pytest
 
+import gather_cases
 import rescue_cases
 from claragenomicsanalysis_amd import DeviceReads, load_library, rescue_overlap_ends
 from claragenomicsanalysis_amd import cudamapper as cm
@@ -149,6 +152,130 @@ def test_an_overlap_past_the_aligners_limit_is_left_without_a_cigar_in_both_path
     assert resident == on_host
     assert resident[3] == "" and all(resident[:3]) and all(resident[4:])
     assert resident[:3] + resident[4:] == host[1][:5]
+
+
+# ---- alignment of regions longer than one piece of the gather kernel ------------------------------
+
+HM = 0  # the algorithm align_overlaps creates its aligners with (test_aligner_plan.HM)
+
+
+def aligner_plan(monkeypatch, env, max_q, max_t, batch):
+    """The plan report (test_aligner_plan.plan, with this device's facts) of the aligner that
+    align_overlaps creates for these three sizes; leaves `env` set until the test ends."""
+    from test_aligner_plan import ENV_NAMES, _lib, plan
+    for k in ENV_NAMES:  # (restored after the test)
+        monkeypatch.setenv(k, "")
+    p = plan(_lib(), env, [HM, max_q, max_t, batch, 0, 0, 0, 0, 0, 0, 0, 0])
+    assert "error" not in p and p["kernel"] == 1, p
+    return p
+
+
+def sprinkle(rng, s, count):
+    """Lower case, N and other letters that no complement changes, at `count` places."""
+    s = list(s)
+    for _ in range(count):
+        s[rng.randrange(len(s))] = rng.choice("NnacgtRY")
+    return "".join(s)
+
+
+def oracle_cigars(overlaps, queries, targets):
+    from oracle import oracle
+    mq = max(o.query_end - o.query_start for o in overlaps)
+    pairs = []
+    for o in overlaps:
+        tr = targets[o.target_read_id][o.target_start:o.target_end]
+        pairs.append((queries[o.query_read_id][o.query_start:o.query_end], rc(tr) if o.strand == "-" else tr))
+    return [oracle.cigar(states) for states in oracle.align_batch(pairs, oracle.ALIGN_HM, mq)[0]]
+
+
+@pytest.fixture(scope="module")
+def long_align_set():
+    """Ten overlaps whose regions have 4,100 to 13,000 bases, on both strands, at 5 % errors,
+    with lower case and N inside the regions of both sides."""
+    rng = random.Random(43)
+    targets = [sprinkle(rng, "".join(rng.choice("ACGT") for _ in range(13100)), 200) for _ in range(3)]
+    queries, overlaps = [], []
+    for i, length in enumerate((4200, 4300, 6000, 8191, 8200, 9000, 10000, 12000, 12289, 12800)):
+        t = targets[i % 3]
+        ts = rng.randint(0, len(t) - length)
+        strand = "+-"[i % 2]
+        region = t[ts:ts + length]
+        body = sprinkle(rng, mutate(rng, rc(region) if strand == "-" else region, 0.05), 8)
+        pre = "".join(rng.choice("ACGT") for _ in range(rng.randrange(40)))
+        queries.append(pre + body + "".join(rng.choice("ACGT") for _ in range(rng.randrange(40))))
+        overlaps.append(cm.Overlap(i, i % 3, len(pre), len(pre) + len(body), ts, ts + length, strand, i))
+    for o in overlaps:
+        for length in (o.query_end - o.query_start, o.target_end - o.target_start):
+            assert gather_cases.PIECE < 4100 <= length <= 13000
+        for region in (queries[o.query_read_id][o.query_start:o.query_end],
+                       targets[o.target_read_id][o.target_start:o.target_end]):
+            assert set("Nn") <= set(region) and set(region) & set("acgt")
+    host = {e: cm.align_overlaps(overlaps, queries, targets, num_alignment_engines=e) for e in (1, 2)}
+    return queries, targets, overlaps, host, oracle_cigars(overlaps, queries, targets)
+
+
+@pytest.mark.parametrize("engines", [1, 2])
+def test_long_regions_on_handles_equal_the_host_read_call_and_the_oracle(long_align_set, engines, monkeypatch):
+    queries, targets, overlaps, host, want = long_align_set
+    max_q = max(o.query_end - o.query_start for o in overlaps)
+    max_t = max(o.target_end - o.target_start for o in overlaps)
+    # the slots of the aligner's sequence buffer begin at every lead, not on 16-byte boundaries only
+    assert max(max_q, max_t) % 16 != 0
+    p = aligner_plan(monkeypatch, {}, max_q, max_t, len(overlaps) // engines)
+    assert p["stride"] == max(max_q, max_t) and not p["launch_long_mode"]
+    with DeviceReads(queries) as q, DeviceReads(targets) as t:
+        cigars = cm.align_overlaps(overlaps, q, t, num_alignment_engines=engines)
+    assert len(cigars) == len(overlaps) and all(cigars)
+    assert cigars == host[engines]
+    assert cigars == want
+    assert any("I" in c and "D" in c for c in cigars)
+
+
+def test_a_long_mode_overlap_on_handles_equals_the_host_read_call_and_the_oracle(monkeypatch):
+    # a query region past the short-mode limit of 16,384 bases: the long-mode Hirschberg-Myers
+    # kernel (striped sweeps, patterns in HBM) on sequences that the gather kernel wrote, the
+    # target reversed; two short overlaps share the call and the aligner
+    rng = random.Random(47)
+    big_t = sprinkle(rng, "".join(rng.choice("ACGT") for _ in range(17300)), 40)
+    big_q = sprinkle(rng, mutate(rng, rc(big_t[150:17150]), 0.03), 40)
+    small_t = "".join(rng.choice("ACGT") for _ in range(900))
+    queries = [mutate(rng, small_t[100:420], 0.05), big_q, mutate(rng, rc(small_t[500:800]), 0.05)]
+    targets = [small_t, big_t]
+    overlaps = [cm.Overlap(0, 0, 0, len(queries[0]), 100, 420, "+", 1),
+                cm.Overlap(1, 1, 0, len(big_q), 0, len(big_t), "-", 2),
+                cm.Overlap(2, 0, 0, len(queries[2]), 500, 800, "-", 3)]
+    assert 16384 < len(big_q) < 17300
+    p = aligner_plan(monkeypatch, {}, len(big_q), len(big_t), len(overlaps))
+    assert p["long_mode"] == 1 and p["launch_long_mode"] == 1
+    assert not aligner_plan(monkeypatch, {}, 16384, len(big_t), len(overlaps))["launch_long_mode"]
+    on_host = cm.align_overlaps(overlaps, queries, targets)
+    with DeviceReads(queries) as q, DeviceReads(targets) as t:
+        resident = cm.align_overlaps(overlaps, q, t)
+    assert all(resident) and resident == on_host
+    assert resident == oracle_cigars(overlaps, queries, targets)
+
+
+def test_pipelined_stages_on_device_added_pairs(monkeypatch):
+    # align_all() in stages on a batch whose sequences were gathered on the device: the stages
+    # upload the lengths only.  1,500 overlaps of about 300 bases and one engine make one batch
+    # of many grids' worth of pairs at one workgroup per CU, as in test_aligner_gpu.py
+    from claragenomicsanalysis_amd import synth
+    qs, ts = synth.pairs(79, 1500, 300, 330, 10, 10, 10)
+    queries = [q.decode() for q in qs]
+    strands = ["-" if i % 3 == 1 else "+" for i in range(len(ts))]
+    targets = [rc(t.decode()) if s == "-" else t.decode() for t, s in zip(ts, strands)]
+    overlaps = [cm.Overlap(i, i, 0, len(queries[i]), 0, len(targets[i]), strands[i], i) for i in range(len(qs))]
+    max_q, max_t = max(map(len, queries)), max(map(len, targets))
+    res = {}
+    for mode in ("1", "3"):
+        env = {"GWAMD_DIAG": "1", "GWAMD_ALIGNER_GRID": "1", "GWAMD_ALIGNER_PIPELINE": mode}
+        p = aligner_plan(monkeypatch, env, max_q, max_t, len(overlaps))
+        assert p["stages"] == int(mode) and len(overlaps) >= 4 * p["slots"]
+        with DeviceReads(queries) as q, DeviceReads(targets) as t:
+            res[mode] = cm.align_overlaps(overlaps, q, t, num_alignment_engines=1)
+        assert res[mode] == cm.align_overlaps(overlaps, queries, targets, num_alignment_engines=1)
+    assert res["3"] == res["1"]
+    assert res["1"] == oracle_cigars(overlaps, queries, targets)
 
 
 # ---- argument checks that need a handle ------------------------------------------------------

@@ -1,6 +1,7 @@
 """MI355X-native batched POA consensus/MSA, global alignment and cudamapper's
 minimizer index, anchor matcher, overlapper, overlap-end rescue, index
-batches and reads resident on the device.
+batches and reads resident on the device, and cudapolish: aligned overlaps cut
+into POA windows on the GPU, from reads and overlaps to a polished target.
 
 Python mirror of the reference's pygenomeworks bindings (genomeworks.cudapoa,
 genomeworks.cudaaligner) over the C ABI of libgwamd.so (include/*.h).  All
@@ -10,8 +11,11 @@ from ._lib import load_library, library_path  # noqa: F401
 from .cudamapper import (Index, match_anchors, get_overlaps, match_overlaps, post_process_overlaps,  # noqa: F401
                          rescue_overlap_ends, extend_overlap_by_sequence_similarity, DeviceReads,
                          group_reads_into_indices, generate_batches_of_indices, IndexHostCopy)
+from .cudapolish import (window_segments, window_segments_host, window_segments_resident,  # noqa: F401
+                         build_windows, polish)
 
 __all__ = ["load_library", "library_path", "Index", "match_anchors", "get_overlaps", "match_overlaps",
            "post_process_overlaps", "rescue_overlap_ends", "extend_overlap_by_sequence_similarity",
            "DeviceReads", "group_reads_into_indices", "generate_batches_of_indices",
-           "IndexHostCopy"]
+           "IndexHostCopy", "window_segments", "window_segments_host", "window_segments_resident",
+           "build_windows", "polish"]

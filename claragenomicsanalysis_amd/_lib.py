@@ -86,6 +86,8 @@ def _declare(L):
         cudaaligner._declare(L)
     from . import cudamapper
     cudamapper._declare(L)
+    from . import cudapolish
+    cudapolish._declare(L)
 
 
 def last_error():

@@ -373,7 +373,8 @@ public:
             chunk0_[0] = 0, chunk0_[1] = n;
             upload();
             launch(); // records pipe_->ev_k[0] / pipe_->ev_k[1] around the kernel
-            download();
+            if (!keep_on_device_)
+                download();
             GWAMD_HIP_CHECK(hipEventRecord(pipe_->ev_d[0], stream_));
             return StatusType::success;
         }
@@ -404,11 +405,14 @@ public:
             launch_range(i0, c, (k & 1) * half_slots, (k & 1) ? slots_ - half_slots : half_slots, st);
             GWAMD_HIP_CHECK(hipEventRecord(pipe_->ev_k[2 * k + 1], st));
             GWAMD_HIP_CHECK(hipStreamWaitEvent(pipe_->s_out, pipe_->ev_k[2 * k + 1], 0));
-            GWAMD_HIP_CHECK(hipMemcpyAsync(h_paths_.as<int8_t>() + size_t(i0) * max_result_,
-                                           d_paths_.data() + size_t(i0) * max_result_, size_t(c) * max_result_,
-                                           hipMemcpyDeviceToHost, pipe_->s_out));
-            GWAMD_HIP_CHECK(hipMemcpyAsync(h_plen_.as<int32_t>() + i0, d_plen_.data() + i0, size_t(c) * 4,
-                                           hipMemcpyDeviceToHost, pipe_->s_out));
+            if (!keep_on_device_)
+            {
+                GWAMD_HIP_CHECK(hipMemcpyAsync(h_paths_.as<int8_t>() + size_t(i0) * max_result_,
+                                               d_paths_.data() + size_t(i0) * max_result_, size_t(c) * max_result_,
+                                               hipMemcpyDeviceToHost, pipe_->s_out));
+                GWAMD_HIP_CHECK(hipMemcpyAsync(h_plen_.as<int32_t>() + i0, d_plen_.data() + i0, size_t(c) * 4,
+                                               hipMemcpyDeviceToHost, pipe_->s_out));
+            }
             GWAMD_HIP_CHECK(hipEventRecord(pipe_->ev_d[k], pipe_->s_out));
         }
         GWAMD_HIP_CHECK(hipEventRecord(pipe_->ev_join, pipe_->s_out)); // after every kernel and download
@@ -588,6 +592,12 @@ public:
         ScopedDevice dev(device_id_);
         GWAMD_HIP_CHECK(hipStreamSynchronize(stream_));
     }
+    // the internal view of the device path buffer (aligner_resident.hpp)
+    gwamd::aln::DevicePaths device_paths() const
+    {
+        return {d_paths_.data(), int64_t(d_paths_.size()), d_plen_.data(), max_result_, stream_};
+    }
+    void keep_paths_on_device(bool keep) { keep_on_device_ = keep; }
     const int8_t* host_paths() const { return h_paths_.as<int8_t>(); }
     const int32_t* host_path_lengths() const { return h_plen_.as<int32_t>(); }
     int32_t max_result_length() const { return max_result_; }
@@ -665,6 +675,7 @@ private:
     int32_t stride_ = 0, max_result_ = 0;
     int32_t max_diff_ = 0; // largest |query - target| of the batch
     bool device_added_ = false; // the batch's sequences were gathered on the device: no upload of h_seqs_
+    bool keep_on_device_ = false; // align_all() leaves the paths on the device (keep_paths_on_device)
     // stages of the last align_all() (0: none yet) and their first pairs
     int stages_                                 = 0;
     int32_t chunk0_[gwamd::aln::kMaxStages + 1] = {};
@@ -735,6 +746,22 @@ add_device_overlaps(claraparabricks::genomeworks::cudaaligner::Aligner& aligner,
     if (!impl)
         throw std::invalid_argument("add_device_overlaps: not an aligner of create_aligner");
     return impl->add_device_overlaps(query, target, overlaps, count);
+}
+
+DevicePaths device_paths(claraparabricks::genomeworks::cudaaligner::Aligner& aligner)
+{
+    auto* impl = dynamic_cast<claraparabricks::genomeworks::cudaaligner::AlignerGlobalHip*>(&aligner);
+    if (!impl)
+        throw std::invalid_argument("device_paths: not an aligner of create_aligner");
+    return impl->device_paths();
+}
+
+void keep_paths_on_device(claraparabricks::genomeworks::cudaaligner::Aligner& aligner, bool keep)
+{
+    auto* impl = dynamic_cast<claraparabricks::genomeworks::cudaaligner::AlignerGlobalHip*>(&aligner);
+    if (!impl)
+        throw std::invalid_argument("keep_paths_on_device: not an aligner of create_aligner");
+    impl->keep_paths_on_device(keep);
 }
 } // namespace aln
 } // namespace gwamd

@@ -24,5 +24,24 @@ add_device_overlaps(claraparabricks::genomeworks::cudaaligner::Aligner& aligner,
                     const gwamd::mapper::DeviceReads& target, const gwamd::mapper::OverlapRecord* overlaps,
                     int32_t count);
 
+// Where the aligner's kernels leave the paths of its batch: path i, emitted
+// end -> start, at paths + i * max_path_length (a multiple of 4), its length at
+// lengths[i]; `bytes` is the allocation behind paths.  Work queued on stream
+// after align_all() finds them complete.
+struct DevicePaths
+{
+    const int8_t* paths;
+    int64_t bytes;
+    const int32_t* lengths;
+    int32_t max_path_length;
+    hipStream_t stream;
+};
+DevicePaths device_paths(claraparabricks::genomeworks::cudaaligner::Aligner& aligner);
+
+// With keep == true align_all() leaves the paths on the device: nothing is
+// copied to the host, and the caller reads them through device_paths() and
+// calls reset() without sync_alignments().
+void keep_paths_on_device(claraparabricks::genomeworks::cudaaligner::Aligner& aligner, bool keep);
+
 } // namespace aln
 } // namespace gwamd

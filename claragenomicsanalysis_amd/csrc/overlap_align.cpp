@@ -16,6 +16,7 @@
 #include "aligner_resident.hpp"
 #include "host_common.hpp"
 #include "mapper_reads.hpp"
+#include "polish_windows.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -158,9 +159,14 @@ using RegionFn = std::function<Region(int32_t)>;
 // one step (reads resident on the device); without one, the pairs are added
 // one by one from the host pointers of their regions.
 using AddRangeFn = std::function<cudaaligner::StatusType(cudaaligner::Aligner&, int32_t, int32_t)>;
+// Called in place of sync_alignments and the CIGAR conversion after the
+// align_all() of the pairs [start, end): the caller works on the aligner's
+// device paths (aligner_resident.hpp) and no CIGAR is made.  Engines call it concurrently.
+using BatchFn = std::function<void(cudaaligner::Aligner&, int32_t, int32_t)>;
 
 void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, int32_t num_alignment_engines,
-                    const RegionFn& region, std::vector<std::string>& cigars, const AddRangeFn* add_range);
+                    const RegionFn& region, std::vector<std::string>& cigars, const AddRangeFn* add_range,
+                    const BatchFn* on_batch);
 
 // Overlaps longer than the aligner's limits (gwamd_aligner_max_lengths; the
 // reference has none) are left without a CIGAR, with a warning on stderr, so
@@ -168,7 +174,8 @@ void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, 
 // aligner sized for them (main.cu:125-175 sizes it by the longest overlap).
 // kept_out (may be null) receives the indices of the overlaps that are aligned, which is what add_range counts in.
 void run_engines(int32_t n, int32_t num_alignment_engines, const RegionFn& region, std::vector<std::string>& cigars,
-                 const AddRangeFn* add_range = nullptr, std::vector<int32_t>* kept_out = nullptr)
+                 const AddRangeFn* add_range = nullptr, std::vector<int32_t>* kept_out = nullptr,
+                 const BatchFn* on_batch = nullptr)
 {
     if (num_alignment_engines < 1)
         throw std::runtime_error("num_alignment_engines must be at least 1");
@@ -194,14 +201,15 @@ void run_engines(int32_t n, int32_t num_alignment_engines, const RegionFn& regio
         *kept_out = kept;
     std::vector<std::string> kept_cigars;
     run_engines_on(int32_t(kept.size()), max_q, max_t, num_alignment_engines,
-                   [&](int32_t k) { return region(kept[size_t(k)]); }, kept_cigars, add_range);
+                   [&](int32_t k) { return region(kept[size_t(k)]); }, kept_cigars, add_range, on_batch);
     cigars.assign(size_t(n), std::string());
     for (size_t k = 0; k < kept.size(); k++)
         cigars[size_t(kept[k])] = std::move(kept_cigars[k]);
 }
 
 void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, int32_t num_alignment_engines,
-                    const RegionFn& region, std::vector<std::string>& cigars, const AddRangeFn* add_range)
+                    const RegionFn& region, std::vector<std::string>& cigars, const AddRangeFn* add_range,
+                    const BatchFn* on_batch)
 {
     cigars.assign(size_t(n), std::string());
     if (n == 0)
@@ -242,6 +250,8 @@ void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, 
             auto aligner = cudaaligner::create_aligner(max_query_size, max_target_size, int32_t(batch_size),
                                                        cudaaligner::AlignmentType::global_alignment,
                                                        DefaultDeviceAllocator(), stream, device_id);
+            if (on_batch)
+                gwamd::aln::keep_paths_on_device(*aligner, true);
             while (true)
             {
                 int32_t start = 0, end = 0;
@@ -268,6 +278,12 @@ void run_engines_on(int32_t n, int32_t max_query_size, int32_t max_target_size, 
                         throw std::runtime_error("Experienced error type " + std::to_string(int(st)));
                 }
                 aligner->align_all();
+                if (on_batch)
+                {
+                    (*on_batch)(*aligner, start, end);
+                    aligner->reset();
+                    continue;
+                }
                 aligner->sync_alignments();
                 const auto& alignments = aligner->get_alignments();
                 for (int32_t i = 0; i < int32_t(alignments.size()); i++)
@@ -368,13 +384,21 @@ void align_overlaps(DefaultDeviceAllocator /*allocator*/, std::vector<Overlap>& 
 namespace
 {
 
-// align_overlaps on n checked records whose reads are resident on the current device
+// align_overlaps on n checked records whose reads are resident on the current
+// device.  With on_batch (see BatchFn) no CIGAR is made; the caller's two
+// vectors then receive the overlaps within the aligner's limits, which are the
+// pairs on_batch counts in, and their indices among the n.
 void align_resident(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target,
                     const gwamd::mapper::OverlapRecord* records, int32_t n, int32_t num_alignment_engines,
-                    std::vector<std::string>& cigars)
+                    std::vector<std::string>& cigars,
+                    std::vector<gwamd::mapper::OverlapRecord>* kept_records_out = nullptr,
+                    std::vector<int32_t>* kept_indices_out = nullptr, const BatchFn* on_batch = nullptr)
 {
-    std::vector<gwamd::mapper::OverlapRecord> kept_records; // the overlaps within the aligner's limits, in order
-    std::vector<int32_t> kept;
+    // the overlaps within the aligner's limits, in order, and their indices
+    std::vector<gwamd::mapper::OverlapRecord> own_records;
+    std::vector<int32_t> own_indices;
+    std::vector<gwamd::mapper::OverlapRecord>& kept_records = kept_records_out ? *kept_records_out : own_records;
+    std::vector<int32_t>& kept                              = kept_indices_out ? *kept_indices_out : own_indices;
     bool packed = false;
     std::mutex pack_mtx;
     const AddRangeFn add_range = [&](cudaaligner::Aligner& aligner, int32_t start, int32_t end) {
@@ -396,7 +420,7 @@ void align_resident(const gwamd::mapper::DeviceReads& query, const gwamd::mapper
                     return Region{nullptr, int32_t(o.query_end - o.query_start), nullptr,
                                   int32_t(o.target_end - o.target_start), o.relative_strand == '-'};
                 },
-                cigars, &add_range, &kept);
+                cigars, &add_range, &kept, on_batch);
 }
 
 void check_reads_on_current_device(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target)
@@ -459,6 +483,85 @@ void print_paf(const std::vector<Overlap>& overlaps, const std::vector<std::stri
 } // namespace cudamapper
 } // namespace genomeworks
 } // namespace claraparabricks
+
+// ---- cudapolish: the cut on the aligner's device paths -----------------------
+
+namespace gwamd
+{
+namespace polish
+{
+
+void window_segments_resident(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target,
+                              const OverlapRecord* overlaps, int32_t n, int32_t window_length,
+                              int32_t num_alignment_engines, std::vector<gwamd_window_segment>& out)
+{
+    namespace cm = claraparabricks::genomeworks::cudamapper;
+    namespace ca = claraparabricks::genomeworks::cudaaligner;
+    const RecordLayout layout = plan_records(overlaps, n, window_length);
+    out.assign(size_t(layout.total()), gwamd_window_segment{});
+    std::vector<OverlapRecord> kept_records;
+    std::vector<int32_t> kept;
+    // After the align_all() of the kept overlaps [start, end): their records
+    // go up, the cut runs on the aligner's stream over its device paths and
+    // the records of the range, contiguous on the device, come back into the
+    // places the layout of the whole call gives them.
+    const cm::BatchFn on_batch = [&](ca::Aligner& aligner, int32_t start, int32_t end) {
+        const int32_t count             = end - start;
+        const gwamd::aln::DevicePaths p = gwamd::aln::device_paths(aligner);
+        const RecordLayout batch        = plan_records(kept_records.data() + start, count, window_length);
+        gwamd::mapper::DevBuf<OverlapRecord> d_overlaps(size_t(count), nullptr);
+        gwamd::mapper::DevBuf<uint32_t> d_base(size_t(count), nullptr), d_status(size_t(count), nullptr);
+        gwamd::mapper::DevBuf<gwamd_window_segment> d_records(std::max<size_t>(size_t(batch.total()), 1), nullptr);
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_overlaps.data(), kept_records.data() + start,
+                                       size_t(count) * sizeof(OverlapRecord), hipMemcpyHostToDevice, p.stream));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_base.data(), batch.base.data(), size_t(count) * sizeof(uint32_t),
+                                       hipMemcpyHostToDevice, p.stream));
+        GWAMD_HIP_CHECK(hipMemsetAsync(d_records.data(), 0, d_records.size() * sizeof(gwamd_window_segment),
+                                       p.stream));
+        PathSource source;
+        source.paths        = p.paths;
+        source.paths_bytes  = p.bytes;
+        source.stride       = p.max_path_length;
+        source.lengths      = p.lengths;
+        source.max_length   = p.max_path_length;
+        source.end_to_start = true;
+        launch_window_cut(source, d_overlaps.data(), d_base.data(), d_records.data(), d_status.data(), count,
+                          window_length, p.stream);
+        std::vector<gwamd_window_segment> records(static_cast<size_t>(batch.total()));
+        std::vector<uint32_t> status(static_cast<size_t>(count));
+        if (!records.empty())
+            GWAMD_HIP_CHECK(hipMemcpyAsync(records.data(), d_records.data(),
+                                           records.size() * sizeof(gwamd_window_segment), hipMemcpyDeviceToHost,
+                                           p.stream));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(status.data(), d_status.data(), size_t(count) * sizeof(uint32_t),
+                                       hipMemcpyDeviceToHost, p.stream));
+        GWAMD_HIP_CHECK(hipStreamSynchronize(p.stream));
+        for (int32_t k = 0; k < count; k++)
+        {
+            const int32_t i      = kept[size_t(start + k)];
+            const uint32_t c     = batch.base[size_t(k) + 1] - batch.base[size_t(k)];
+            gwamd_window_segment* to = out.data() + layout.base[size_t(i)];
+            if (c > 0)
+                std::memcpy(static_cast<void*>(to), records.data() + batch.base[size_t(k)],
+                            size_t(c) * sizeof(gwamd_window_segment));
+            complete_records(to, c, uint32_t(i), overlaps[i], window_length,
+                             status[size_t(k)] ? GWAMD_SEGMENT_BAD_PATH : 0);
+        }
+    };
+    std::vector<std::string> no_cigars;
+    cm::align_resident(query, target, overlaps, n, num_alignment_engines, no_cigars, &kept_records, &kept, &on_batch);
+    // the overlaps the aligner's limits left out
+    std::vector<bool> aligned(static_cast<size_t>(n), false);
+    for (int32_t i : kept)
+        aligned[size_t(i)] = true;
+    for (int32_t i = 0; i < n; i++)
+        if (!aligned[size_t(i)])
+            complete_records(out.data() + layout.base[size_t(i)], layout.base[size_t(i) + 1] - layout.base[size_t(i)],
+                             uint32_t(i), overlaps[i], window_length, GWAMD_SEGMENT_NOT_ALIGNED);
+}
+
+} // namespace polish
+} // namespace gwamd
 
 // ---- C ABI ------------------------------------------------------------------
 

@@ -1,0 +1,677 @@
+// Host side of cudapolish (include/gwamd_polish.h,
+// claraparabricks/genomeworks/cudapolish/windows.hpp): the argument checks, the
+// layout of the records, the walk of one path on the host, the completion of
+// the records the kernel leaves (polish_windows.hip), the grouping into
+// cudapoa groups and the C ABI.  Every argument is checked here, before any
+// device call, so that the kernel is never given an overlap with start > end or
+// a record range it does not own.
+//
+// Who completes a record: the kernel stores q_begin, q_end, t_begin, t_end of
+// the windows that hold a match or mismatch state into records the host has
+// zeroed, and one status word per overlap; complete_records, on the host after
+// the copy back, writes overlap, window, flags and the reserved word of every
+// record.
+#include <claraparabricks/genomeworks/cudapolish/windows.hpp>
+
+#include "allocator_handle.hpp"
+#include "mapper_capi.hpp"
+#include "mapper_reads.hpp"
+#include "polish_windows.hpp"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+namespace gm = gwamd::mapper;
+namespace gp = gwamd::polish;
+namespace gw = claraparabricks::genomeworks;
+
+static_assert(sizeof(gw::cudapolish::WindowSegment) == sizeof(gwamd_window_segment) &&
+                  sizeof(gwamd_window_segment) == 32,
+              "a record is eight 32-bit words");
+static_assert(sizeof(gw::cudaaligner::AlignmentState) == 1, "states are bytes");
+
+struct gwamd_windows
+{
+    std::vector<char> bases;
+    std::vector<int64_t> sequence_offsets{0};
+    std::vector<int32_t> window_counts;
+    std::vector<uint32_t> window_target, window_index;
+    std::vector<int32_t> sequence_overlap, sequence_t_begin, sequence_t_end;
+    int64_t dropped_by_cap = 0;
+};
+
+namespace gwamd
+{
+namespace polish
+{
+
+namespace
+{
+
+uint32_t records_of(const OverlapRecord& o, uint32_t w)
+{
+    return o.target_end == o.target_start ? 0 : (o.target_end - 1) / w - o.target_start / w + 1;
+}
+
+} // namespace
+
+RecordLayout plan_records(const OverlapRecord* overlaps, int64_t n, int32_t window_length)
+{
+    if (window_length <= 0)
+        throw std::invalid_argument("window_length must be positive, got " + std::to_string(window_length));
+    RecordLayout layout;
+    layout.base.assign(size_t(n) + 1, 0);
+    int64_t total = 0;
+    for (int64_t i = 0; i < n; i++)
+    {
+        total += records_of(overlaps[i], uint32_t(window_length));
+        if (total >= (int64_t(1) << 31))
+            throw std::invalid_argument("more than 2^31 window records in one call");
+        layout.base[size_t(i) + 1] = uint32_t(total);
+    }
+    return layout;
+}
+
+void complete_records(gwamd_window_segment* records, uint32_t count, uint32_t index, const OverlapRecord& overlap,
+                      int32_t window_length, uint32_t flag)
+{
+    const uint32_t k0      = overlap.target_start / uint32_t(window_length);
+    const uint32_t reverse = overlap.relative_strand == '-' ? GWAMD_SEGMENT_REVERSE : 0;
+    for (uint32_t j = 0; j < count; j++)
+    {
+        gwamd_window_segment& r = records[j];
+        r.overlap               = index;
+        r.window                = k0 + j;
+        r.reserved              = 0;
+        r.flags                 = reverse;
+        // (a window with a match or mismatch state has q_end >= 1)
+        if (flag != 0 || r.q_end == 0)
+        {
+            r.q_begin = r.q_end = r.t_begin = r.t_end = 0;
+            r.flags |= GWAMD_SEGMENT_EMPTY | flag;
+        }
+    }
+}
+
+void walk_on_host(gwamd_window_segment* records, uint32_t count, uint32_t index, const OverlapRecord& overlap,
+                  const int8_t* states, int64_t num_states, int32_t window_length)
+{
+    const uint32_t w = uint32_t(window_length);
+    const uint32_t span_t = overlap.target_end - overlap.target_start;
+    const uint32_t span_q = overlap.query_end - overlap.query_start;
+    const bool reverse    = overlap.relative_strand == '-';
+    const uint32_t k0     = overlap.target_start / w;
+    std::memset(static_cast<void*>(records), 0, size_t(count) * sizeof(gwamd_window_segment));
+    uint32_t u = 0, v = 0;
+    bool fits = true;
+    uint32_t open = UINT32_MAX; // the window of the last match state
+    for (int64_t p = 0; p < num_states && fits; p++)
+    {
+        const int8_t s = states[p];
+        if (s < 0 || s > 3)
+            fits = false;
+        else if (s <= 1)
+        {
+            if (u >= span_t || v >= span_q)
+                fits = false;
+            else
+            {
+                const uint32_t t = reverse ? overlap.target_end - 1 - u : overlap.target_start + u;
+                const uint32_t q = overlap.query_start + v;
+                gwamd_window_segment& r = records[t / w - k0];
+                if (t / w != open)
+                {
+                    open      = t / w;
+                    r.q_begin = q;
+                    (reverse ? r.t_end : r.t_begin) = reverse ? t + 1 : t;
+                }
+                r.q_end = q + 1;
+                (reverse ? r.t_begin : r.t_end) = reverse ? t : t + 1;
+            }
+        }
+        if (fits)
+        {
+            u += s != 3;
+            v += s != 2;
+        }
+    }
+    fits = fits && u == span_t && v == span_q;
+    complete_records(records, count, index, overlap, window_length, fits ? 0 : GWAMD_SEGMENT_BAD_PATH);
+}
+
+namespace
+{
+
+// what every entry point asks of its overlaps before anything else
+void check_cut_overlaps(const gwamd_overlap* overlaps, int64_t n, std::vector<OverlapRecord>& records)
+{
+    if (n < 0 || n >= (int64_t(1) << 31))
+        throw std::invalid_argument("the number of overlaps must be between 0 and 2^31, got " + std::to_string(n));
+    if (n > 0 && !overlaps)
+        throw std::invalid_argument("overlaps is NULL");
+    records.resize(size_t(n));
+    if (n > 0)
+        std::memcpy(static_cast<void*>(records.data()), overlaps, size_t(n) * sizeof(gwamd_overlap));
+    for (int64_t i = 0; i < n; i++)
+    {
+        const OverlapRecord& o = records[size_t(i)];
+        if (o.query_start > o.query_end || o.target_start > o.target_end)
+            throw std::invalid_argument("overlap " + std::to_string(i) + ": positions are not start <= end");
+        if (o.query_end >= (1u << 31) || o.target_end >= (1u << 31))
+            throw std::invalid_argument("overlap " + std::to_string(i) + ": a position of 2^31 or more");
+        if (o.relative_strand != '+' && o.relative_strand != '-')
+            throw std::invalid_argument("overlap " + std::to_string(i) + ": relative_strand is neither '+' nor '-'");
+    }
+}
+
+void check_path_length(const OverlapRecord& o, int64_t i, int64_t length)
+{
+    if (length < 0)
+        throw std::invalid_argument("path " + std::to_string(i) + ": negative length");
+    if (length > int64_t(o.query_end - o.query_start) + int64_t(o.target_end - o.target_start))
+        throw std::invalid_argument("path " + std::to_string(i) + " is longer than its overlap's two spans together");
+}
+
+void hand_over(std::vector<gwamd_window_segment>& records, gwamd_window_segment** out, int64_t* num_out)
+{
+    if (records.empty())
+        return;
+    std::unique_ptr<gwamd_window_segment[]> h(new gwamd_window_segment[records.size()]);
+    std::memcpy(static_cast<void*>(h.get()), records.data(), records.size() * sizeof(gwamd_window_segment));
+    *num_out = int64_t(records.size());
+    *out     = h.release();
+}
+
+void clear_outputs(gwamd_window_segment** out, int64_t* num_out)
+{
+    if (out)
+        *out = nullptr;
+    if (num_out)
+        *num_out = 0;
+}
+
+template <typename T>
+void upload(gm::DevBuf<T>& d, const T* src, size_t count, const Budget& budget)
+{
+    d.alloc(count, budget);
+    if (count > 0)
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d.data(), src, count * sizeof(T), hipMemcpyHostToDevice, nullptr));
+}
+
+// One launch over checked overlaps whose paths are in host memory: `bytes`
+// bytes of path buffer (a multiple of 4), path i at offsets[i] or i * stride.
+void cut_on_device(const std::vector<OverlapRecord>& overlaps, const int8_t* paths, int64_t bytes,
+                   const std::vector<int64_t>* offsets, int64_t stride, const std::vector<int32_t>& lengths,
+                   int32_t max_length, bool end_to_start, int32_t window_length, const Budget& budget,
+                   std::vector<gwamd_window_segment>& out)
+{
+    const int64_t n           = int64_t(overlaps.size());
+    const RecordLayout layout = plan_records(overlaps.data(), n, window_length);
+    out.assign(size_t(layout.total()), gwamd_window_segment{});
+    gm::DevBuf<OverlapRecord> d_overlaps;
+    gm::DevBuf<uint32_t> d_base, d_status;
+    gm::DevBuf<int8_t> d_paths;
+    gm::DevBuf<int64_t> d_offsets;
+    gm::DevBuf<int32_t> d_lengths;
+    gm::DevBuf<gwamd_window_segment> d_records;
+    upload(d_overlaps, overlaps.data(), size_t(n), budget);
+    upload(d_base, layout.base.data(), size_t(n), budget);
+    d_paths.alloc(size_t(std::max<int64_t>(bytes, 16)), budget);
+    if (bytes > 0)
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_paths.data(), paths, size_t(bytes), hipMemcpyHostToDevice, nullptr));
+    if (offsets)
+        upload(d_offsets, offsets->data(), size_t(n), budget);
+    upload(d_lengths, lengths.data(), size_t(n), budget);
+    d_status.alloc(size_t(n), budget);
+    d_records.alloc(std::max<size_t>(out.size(), 1), budget);
+    GWAMD_HIP_CHECK(hipMemsetAsync(d_records.data(), 0, d_records.size() * sizeof(gwamd_window_segment), nullptr));
+    PathSource source;
+    source.paths        = d_paths.data();
+    source.paths_bytes  = bytes;
+    source.offsets      = offsets ? d_offsets.data() : nullptr;
+    source.stride       = stride;
+    source.lengths      = d_lengths.data();
+    source.max_length   = max_length;
+    source.end_to_start = end_to_start;
+    launch_window_cut(source, d_overlaps.data(), d_base.data(), d_records.data(), d_status.data(), n, window_length,
+                      nullptr);
+    std::vector<uint32_t> status(static_cast<size_t>(n));
+    if (!out.empty())
+        GWAMD_HIP_CHECK(hipMemcpyAsync(out.data(), d_records.data(), out.size() * sizeof(gwamd_window_segment),
+                                       hipMemcpyDeviceToHost, nullptr));
+    GWAMD_HIP_CHECK(hipMemcpyAsync(status.data(), d_status.data(), size_t(n) * sizeof(uint32_t),
+                                   hipMemcpyDeviceToHost, nullptr));
+    GWAMD_HIP_CHECK(hipStreamSynchronize(nullptr));
+    for (int64_t i = 0; i < n; i++)
+        complete_records(out.data() + layout.base[size_t(i)], layout.base[size_t(i) + 1] - layout.base[size_t(i)],
+                         uint32_t(i), overlaps[size_t(i)], window_length,
+                         status[size_t(i)] ? GWAMD_SEGMENT_BAD_PATH : 0);
+}
+
+// The cut of host paths (start -> end): each path is packed on a 16-byte
+// boundary of a buffer padded to a multiple of 16.
+void cut_host_paths(const std::vector<OverlapRecord>& overlaps, const int8_t* states, const int64_t* state_offsets,
+                    int32_t window_length, const Budget& budget, std::vector<gwamd_window_segment>& out)
+{
+    const size_t n = overlaps.size();
+    std::vector<int64_t> offsets(n);
+    std::vector<int32_t> lengths(n);
+    int64_t bytes = 0;
+    for (size_t i = 0; i < n; i++)
+    {
+        offsets[i] = bytes;
+        lengths[i] = int32_t(state_offsets[i + 1] - state_offsets[i]);
+        bytes += (int64_t(lengths[i]) + 15) / 16 * 16;
+    }
+    std::vector<int8_t> packed(static_cast<size_t>(bytes), 0);
+    for (size_t i = 0; i < n; i++)
+        if (lengths[i] > 0)
+            std::memcpy(packed.data() + offsets[i], states + state_offsets[i], size_t(lengths[i]));
+    cut_on_device(overlaps, packed.data(), bytes, &offsets, 0, lengths, INT32_MAX, false, window_length, budget, out);
+}
+
+void check_states(const std::vector<OverlapRecord>& overlaps, const int8_t* states, const int64_t* state_offsets)
+{
+    const int64_t n = int64_t(overlaps.size());
+    if (n > 0 && !state_offsets)
+        throw std::invalid_argument("state_offsets is NULL");
+    for (int64_t i = 0; i < n; i++)
+    {
+        if (state_offsets[i] < 0 || state_offsets[i] > state_offsets[i + 1])
+            throw std::invalid_argument("state_offsets must be non-decreasing");
+        check_path_length(overlaps[size_t(i)], i, state_offsets[i + 1] - state_offsets[i]);
+    }
+    if (n > 0 && state_offsets[n] > 0 && !states)
+        throw std::invalid_argument("states is NULL");
+}
+
+} // namespace
+
+} // namespace polish
+} // namespace gwamd
+
+// ---- grouping ---------------------------------------------------------------
+
+namespace
+{
+
+char complement(char c) { return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c; }
+
+void check_sequences(const char* side, const char* bases, const int64_t* offsets, int32_t n)
+{
+    gm::check_read_set(side, gm::ReadSet{bases, offsets, n});
+}
+
+std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const gm::ReadSet& queries,
+                                             const std::vector<gm::OverlapRecord>& overlaps,
+                                             const gwamd_window_segment* segments, int64_t num_segments,
+                                             int32_t window_length, int32_t max_sequences_per_window)
+{
+    if (window_length <= 0)
+        throw std::invalid_argument("window_length must be positive, got " + std::to_string(window_length));
+    if (max_sequences_per_window < 1)
+        throw std::invalid_argument("max_sequences_per_window must be at least 1");
+    if (num_segments < 0 || (num_segments > 0 && !segments))
+        throw std::invalid_argument("segments: bad count or NULL");
+    const int64_t w = window_length;
+    // the windows of every target, and the kept segments of each in the order given
+    std::vector<int64_t> first(size_t(targets.num_reads) + 1, 0);
+    for (int64_t r = 0; r < targets.num_reads; r++)
+        first[size_t(r) + 1] = first[size_t(r)] + (targets.offsets[r + 1] - targets.offsets[r] + w - 1) / w;
+    const int64_t num_windows = first[size_t(targets.num_reads)];
+    std::vector<std::vector<int64_t>> kept(static_cast<size_t>(num_windows));
+    auto out = std::make_unique<gwamd_windows>();
+    for (int64_t s = 0; s < num_segments; s++)
+    {
+        const gwamd_window_segment& seg = segments[s];
+        const std::string which         = "segment " + std::to_string(s);
+        if (seg.overlap >= overlaps.size())
+            throw std::invalid_argument(which + ": overlap index beyond the overlaps");
+        const gm::OverlapRecord& o = overlaps[seg.overlap];
+        if (int64_t(o.query_read_id) >= queries.num_reads || int64_t(o.target_read_id) >= targets.num_reads)
+            throw std::invalid_argument(which + ": read id of its overlap beyond the reads");
+        if (int64_t(seg.window) >= first[size_t(o.target_read_id) + 1] - first[o.target_read_id])
+            throw std::invalid_argument(which + ": window beyond the target's windows");
+        if (seg.flags & (GWAMD_SEGMENT_EMPTY | GWAMD_SEGMENT_BAD_PATH | GWAMD_SEGMENT_NOT_ALIGNED))
+            continue;
+        if (seg.q_begin > seg.q_end ||
+            int64_t(seg.q_end) > queries.offsets[o.query_read_id + 1] - queries.offsets[o.query_read_id])
+            throw std::invalid_argument(which + ": query range outside its read");
+        if ((int64_t(seg.q_end) - int64_t(seg.q_begin)) * 50 < w)
+            continue;
+        std::vector<int64_t>& list = kept[size_t(first[o.target_read_id] + seg.window)];
+        if (int64_t(list.size()) >= int64_t(max_sequences_per_window) - 1)
+            out->dropped_by_cap++;
+        else
+            list.push_back(s);
+    }
+    auto add = [&](const char* src, int64_t len, bool reverse, int32_t overlap, int32_t t_begin, int32_t t_end) {
+        const size_t at = out->bases.size();
+        out->bases.resize(at + size_t(len));
+        for (int64_t j = 0; j < len; j++)
+            out->bases[at + size_t(j)] = reverse ? complement(src[len - 1 - j]) : src[j];
+        out->sequence_offsets.push_back(int64_t(out->bases.size()));
+        out->sequence_overlap.push_back(overlap);
+        out->sequence_t_begin.push_back(t_begin);
+        out->sequence_t_end.push_back(t_end);
+    };
+    for (int64_t r = 0; r < targets.num_reads; r++)
+    {
+        const int64_t length = targets.offsets[r + 1] - targets.offsets[r];
+        for (int64_t k = 0; k < first[size_t(r) + 1] - first[size_t(r)]; k++)
+        {
+            const int64_t from = k * w, to = std::min((k + 1) * w, length);
+            add(targets.bases + targets.offsets[r] + from, to - from, false, -1, 0, int32_t(to - from));
+            const std::vector<int64_t>& list = kept[size_t(first[size_t(r)] + k)];
+            for (int64_t s : list)
+            {
+                const gwamd_window_segment& seg = segments[s];
+                const gm::OverlapRecord& o      = overlaps[seg.overlap];
+                add(queries.bases + queries.offsets[o.query_read_id] + seg.q_begin, int64_t(seg.q_end - seg.q_begin),
+                    (seg.flags & GWAMD_SEGMENT_REVERSE) != 0, int32_t(seg.overlap),
+                    int32_t(int64_t(seg.t_begin) - from), int32_t(int64_t(seg.t_end) - from));
+            }
+            out->window_counts.push_back(int32_t(list.size()) + 1);
+            out->window_target.push_back(uint32_t(r));
+            out->window_index.push_back(uint32_t(k));
+        }
+    }
+    return out;
+}
+
+struct PackedParser
+{
+    std::string bases;
+    std::vector<int64_t> offsets;
+    explicit PackedParser(const gw::io::FastaParser& parser)
+        : offsets(size_t(parser.get_num_seqences()) + 1, 0)
+    {
+        const uint32_t n = parser.get_num_seqences();
+        for (uint32_t i = 0; i < n; i++)
+        {
+            offsets[i + 1] = offsets[i] + int64_t(parser.get_sequence_by_id(i).seq.size());
+            bases += parser.get_sequence_by_id(i).seq;
+        }
+    }
+    gm::ReadSet view() const { return {bases.data(), offsets.data(), int64_t(offsets.size()) - 1}; }
+};
+
+std::vector<gm::OverlapRecord> as_records(const std::vector<gw::cudamapper::Overlap>& overlaps)
+{
+    static_assert(sizeof(gw::cudamapper::Overlap) == sizeof(gwamd_overlap), "overlaps are copied as bytes");
+    std::vector<gm::OverlapRecord> records;
+    gp::check_cut_overlaps(reinterpret_cast<const gwamd_overlap*>(overlaps.data()), int64_t(overlaps.size()),
+                           records);
+    return records;
+}
+
+std::vector<gw::cudapolish::WindowSegment> as_segments(const std::vector<gwamd_window_segment>& records)
+{
+    std::vector<gw::cudapolish::WindowSegment> out(records.size());
+    if (!records.empty())
+        std::memcpy(static_cast<void*>(out.data()), records.data(), records.size() * sizeof(gwamd_window_segment));
+    return out;
+}
+
+void check_on_current_device(const gm::DeviceReads& query, const gm::DeviceReads& target)
+{
+    int current = -1;
+    GWAMD_HIP_CHECK(hipGetDevice(&current));
+    if (query.device_id != current || target.device_id != current)
+        throw std::invalid_argument("the reads are on device " + std::to_string(query.device_id) + " and " +
+                                    std::to_string(target.device_id) + ", the current device is " +
+                                    std::to_string(current));
+}
+
+// the checks of the resident cut, then the cut
+void cut_resident(const gm::DeviceReads& query, const gm::DeviceReads& target,
+                  const std::vector<gm::OverlapRecord>& records, int32_t window_length, int32_t num_alignment_engines,
+                  std::vector<gwamd_window_segment>& out)
+{
+    gm::check_overlaps(query, target, records.data(), int64_t(records.size()));
+    if (num_alignment_engines < 1)
+        throw std::invalid_argument("num_alignment_engines must be at least 1");
+    (void)gp::plan_records(records.data(), int64_t(records.size()), window_length);
+    out.clear();
+    if (records.empty())
+        return;
+    check_on_current_device(query, target);
+    gp::window_segments_resident(query, target, records.data(), int32_t(records.size()), window_length,
+                                 num_alignment_engines, out);
+}
+
+} // namespace
+
+namespace claraparabricks
+{
+namespace genomeworks
+{
+namespace cudapolish
+{
+
+std::vector<WindowSegment> window_segments(DefaultDeviceAllocator allocator,
+                                           const std::vector<cudamapper::Overlap>& overlaps,
+                                           const std::vector<std::vector<cudaaligner::AlignmentState>>& paths,
+                                           int32_t window_length)
+{
+    if (paths.size() != overlaps.size())
+        throw std::invalid_argument("window_segments: one path per overlap expected");
+    const std::vector<gm::OverlapRecord> records = as_records(overlaps);
+    std::vector<int64_t> offsets(paths.size() + 1, 0);
+    for (size_t i = 0; i < paths.size(); i++)
+        offsets[i + 1] = offsets[i] + int64_t(paths[i].size());
+    std::vector<int8_t> states(static_cast<size_t>(offsets.back()));
+    for (size_t i = 0; i < paths.size(); i++)
+        if (!paths[i].empty())
+            std::memcpy(states.data() + offsets[i], paths[i].data(), paths[i].size());
+    gp::check_states(records, states.data(), offsets.data());
+    (void)gp::plan_records(records.data(), int64_t(records.size()), window_length);
+    std::vector<gwamd_window_segment> out;
+    if (!records.empty())
+        gp::cut_host_paths(records, states.data(), offsets.data(), window_length, allocator.budget(), out);
+    return as_segments(out);
+}
+
+std::vector<WindowSegment> window_segments(DefaultDeviceAllocator /*allocator*/,
+                                           const std::vector<cudamapper::Overlap>& overlaps,
+                                           const cudamapper::DeviceReads& query_reads,
+                                           const cudamapper::DeviceReads& target_reads, int32_t window_length,
+                                           int32_t num_alignment_engines)
+{
+    if (overlaps.size() > size_t(INT32_MAX))
+        throw std::invalid_argument("too many overlaps for one call");
+    std::vector<gwamd_window_segment> out;
+    cut_resident(*query_reads.impl().reads, *target_reads.impl().reads, as_records(overlaps), window_length,
+                 num_alignment_engines, out);
+    return as_segments(out);
+}
+
+Windows build_windows(const io::FastaParser& targets, const io::FastaParser& queries,
+                      const std::vector<cudamapper::Overlap>& overlaps, const std::vector<WindowSegment>& segments,
+                      int32_t window_length, int32_t max_sequences_per_window)
+{
+    const PackedParser t(targets), q(queries);
+    const std::unique_ptr<gwamd_windows> h =
+        group_windows(t.view(), q.view(), as_records(overlaps),
+                      reinterpret_cast<const gwamd_window_segment*>(segments.data()), int64_t(segments.size()),
+                      window_length, max_sequences_per_window);
+    Windows out;
+    out.bases          = std::move(h->bases);
+    out.target         = std::move(h->window_target);
+    out.window         = std::move(h->window_index);
+    out.dropped_by_cap = h->dropped_by_cap;
+    size_t s           = 0;
+    for (int32_t count : h->window_counts)
+    {
+        cudapoa::Group group;
+        std::vector<Windows::Sequence> meta;
+        for (int32_t j = 0; j < count; j++, s++)
+        {
+            group.push_back(cudapoa::Entry{out.bases.data() + h->sequence_offsets[s], nullptr,
+                                           int32_t(h->sequence_offsets[s + 1] - h->sequence_offsets[s])});
+            meta.push_back({h->sequence_overlap[s], h->sequence_t_begin[s], h->sequence_t_end[s]});
+        }
+        out.groups.push_back(std::move(group));
+        out.sequence.push_back(std::move(meta));
+    }
+    return out;
+}
+
+} // namespace cudapolish
+} // namespace genomeworks
+} // namespace claraparabricks
+
+// ---- C ABI ------------------------------------------------------------------
+
+extern "C" {
+
+int32_t gwamd_window_segments(const gwamd_overlap* overlaps, int64_t n, const int8_t* states,
+                              const int64_t* state_offsets, int32_t window_length, int32_t device_id,
+                              gwamd_device_allocator* allocator_or_null, gwamd_window_segment** out, int64_t* num_out)
+{
+    gp::clear_outputs(out, num_out);
+    return gm::guarded_map([&] {
+        if (!out || !num_out)
+            throw std::invalid_argument("out or num_out is NULL");
+        if (device_id < 0)
+            throw std::invalid_argument("device_id must not be negative");
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        gp::check_states(records, states, state_offsets);
+        (void)gp::plan_records(records.data(), n, window_length);
+        if (n == 0)
+            return int32_t(0);
+        gwamd::host::ScopedDevice dev(device_id);
+        std::vector<gwamd_window_segment> result;
+        gp::cut_host_paths(records, states, state_offsets, window_length,
+                           allocator_or_null ? allocator_or_null->alloc.budget() : nullptr, result);
+        gp::hand_over(result, out, num_out);
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_window_segments_host(const gwamd_overlap* overlap, const int8_t* states, int64_t num_states,
+                                   int32_t window_length, uint32_t overlap_index, gwamd_window_segment** out,
+                                   int64_t* num_out)
+{
+    gp::clear_outputs(out, num_out);
+    return gm::guarded_map([&] {
+        if (!out || !num_out)
+            throw std::invalid_argument("out or num_out is NULL");
+        if (!overlap)
+            throw std::invalid_argument("overlap is NULL");
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlap, 1, records);
+        gp::check_path_length(records[0], 0, num_states);
+        if (num_states > 0 && !states)
+            throw std::invalid_argument("states is NULL");
+        const gp::RecordLayout layout = gp::plan_records(records.data(), 1, window_length);
+        std::vector<gwamd_window_segment> result(static_cast<size_t>(layout.total()));
+        gp::walk_on_host(result.data(), uint32_t(result.size()), overlap_index, records[0], states, num_states,
+                         window_length);
+        gp::hand_over(result, out, num_out);
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_window_segments_resident(const gwamd_device_reads* query_reads, const gwamd_device_reads* target_reads,
+                                       const gwamd_overlap* overlaps, int32_t n, int32_t window_length,
+                                       int32_t num_alignment_engines, gwamd_window_segment** out, int64_t* num_out)
+{
+    gp::clear_outputs(out, num_out);
+    return gm::guarded_map([&] {
+        if (!out || !num_out)
+            throw std::invalid_argument("out or num_out is NULL");
+        if (!query_reads || !target_reads)
+            throw std::invalid_argument("query_reads or target_reads is NULL");
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        std::vector<gwamd_window_segment> result;
+        cut_resident(*query_reads->reads, *target_reads->reads, records, window_length, num_alignment_engines,
+                     result);
+        gp::hand_over(result, out, num_out);
+        return int32_t(0);
+    });
+}
+
+void gwamd_window_segments_free(gwamd_window_segment* segments) { delete[] segments; }
+
+int32_t gwamd_internal_window_segments_strided(const gwamd_overlap* overlaps, int64_t n, const int8_t* paths,
+                                               const int32_t* path_lengths, int64_t stride, int32_t window_length,
+                                               gwamd_window_segment** out, int64_t* num_out)
+{
+    gp::clear_outputs(out, num_out);
+    return gm::guarded_map([&] {
+        if (!out || !num_out)
+            throw std::invalid_argument("out or num_out is NULL");
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        if (stride < 4 || stride % 4 != 0 || stride >= (int64_t(1) << 31))
+            throw std::invalid_argument("stride must be a positive multiple of 4 below 2^31");
+        if (n > 0 && (!paths || !path_lengths))
+            throw std::invalid_argument("paths or path_lengths is NULL");
+        for (int64_t i = 0; i < n; i++)
+            if (path_lengths[i] < 0 || path_lengths[i] > stride)
+                throw std::invalid_argument("path " + std::to_string(i) + ": length outside 0..stride");
+        (void)gp::plan_records(records.data(), n, window_length);
+        if (n == 0)
+            return int32_t(0);
+        std::vector<gwamd_window_segment> result;
+        gp::cut_on_device(records, paths, n * stride, nullptr, stride,
+                          std::vector<int32_t>(path_lengths, path_lengths + n), int32_t(stride), true, window_length,
+                          nullptr, result);
+        gp::hand_over(result, out, num_out);
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_build_windows(const char* target_bases, const int64_t* target_offsets, int32_t num_targets,
+                            const char* query_bases, const int64_t* query_offsets, int32_t num_queries,
+                            const gwamd_overlap* overlaps, int64_t n, const gwamd_window_segment* segments,
+                            int64_t num_segments, int32_t window_length, int32_t max_sequences_per_window,
+                            gwamd_windows** out)
+{
+    if (out)
+        *out = nullptr;
+    return gm::guarded_map([&] {
+        if (!out)
+            throw std::invalid_argument("out is NULL");
+        check_sequences("target", target_bases, target_offsets, num_targets);
+        check_sequences("query", query_bases, query_offsets, num_queries);
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        *out = group_windows({target_bases, target_offsets, num_targets}, {query_bases, query_offsets, num_queries},
+                             records, segments, num_segments, window_length, max_sequences_per_window)
+                   .release();
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_windows_get(const gwamd_windows* windows, gwamd_windows_view* view)
+{
+    return gm::guarded_map([&] {
+        if (!windows || !view)
+            throw std::invalid_argument("windows or view is NULL");
+        view->num_windows      = int64_t(windows->window_counts.size());
+        view->num_sequences    = int64_t(windows->sequence_overlap.size());
+        view->num_bases        = int64_t(windows->bases.size());
+        view->dropped_by_cap   = windows->dropped_by_cap;
+        view->bases            = windows->bases.data();
+        view->sequence_offsets = windows->sequence_offsets.data();
+        view->window_counts    = windows->window_counts.data();
+        view->window_target    = windows->window_target.data();
+        view->window_index     = windows->window_index.data();
+        view->sequence_overlap = windows->sequence_overlap.data();
+        view->sequence_t_begin = windows->sequence_t_begin.data();
+        view->sequence_t_end   = windows->sequence_t_end.data();
+        return int32_t(0);
+    });
+}
+
+void gwamd_windows_free(gwamd_windows* windows) { delete windows; }
+
+} // extern "C"

@@ -1,0 +1,276 @@
+"""cudapolish: the step between cudamapper and cudapoa in a racon-style
+polisher, over the C ABI of include/gwamd_polish.h.
+
+window_segments cuts aligned overlaps at the target's window boundaries on the
+GPU (racon's find_breaking_points), window_segments_resident aligns the
+overlaps on resident reads and cuts them where the aligner leaves its paths on
+the device, build_windows groups the pieces into POA windows, and polish runs
+targets + reads + overlaps -> polished targets end to end.
+
+Path states are AlignmentState values, start -> end: 0 match and 1 mismatch
+advance both sequences, 3 (deletion) advances ONLY THE QUERY and 2 (insertion)
+ONLY THE TARGET, the reference's convention and the opposite of SAM's I / D.
+
+Not done: quality weights, racon's coverage trimming of consensus ends,
+positional (sub-graph) alignment of a segment within its window.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import load_library
+from .cudamapper import DeviceReads, _check, _handles, _overlap_array, _pack
+
+REVERSE, EMPTY, BAD_PATH, NOT_ALIGNED = 1, 2, 4, 8
+
+# gwamd_window_segment
+SEGMENT_DTYPE = np.dtype([(n, np.uint32) for n in ("overlap", "window", "q_begin", "q_end", "t_begin", "t_end",
+                                                   "flags", "reserved")])
+
+
+class _WindowsView(C.Structure):
+    """gwamd_windows_view."""
+    _fields_ = [("num_windows", C.c_int64), ("num_sequences", C.c_int64), ("num_bases", C.c_int64),
+                ("dropped_by_cap", C.c_int64), ("bases", C.c_void_p), ("sequence_offsets", C.c_void_p),
+                ("window_counts", C.c_void_p), ("window_target", C.c_void_p), ("window_index", C.c_void_p),
+                ("sequence_overlap", C.c_void_p), ("sequence_t_begin", C.c_void_p), ("sequence_t_end", C.c_void_p)]
+
+
+def _declare(L):
+    vp, i32, i64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32
+    P = C.POINTER
+    L.gwamd_window_segments.restype = i32
+    L.gwamd_window_segments.argtypes = [vp, i64, vp, vp, i32, i32, vp, P(vp), P(i64)]
+    L.gwamd_window_segments_host.restype = i32
+    L.gwamd_window_segments_host.argtypes = [vp, vp, i64, i32, u32, P(vp), P(i64)]
+    L.gwamd_window_segments_resident.restype = i32
+    L.gwamd_window_segments_resident.argtypes = [vp, vp, vp, i32, i32, i32, P(vp), P(i64)]
+    L.gwamd_window_segments_free.restype = None
+    L.gwamd_window_segments_free.argtypes = [vp]
+    L.gwamd_internal_window_segments_strided.restype = i32
+    L.gwamd_internal_window_segments_strided.argtypes = [vp, i64, vp, vp, i64, i32, P(vp), P(i64)]
+    L.gwamd_build_windows.restype = i32
+    L.gwamd_build_windows.argtypes = [C.c_char_p, vp, i32, C.c_char_p, vp, i32, vp, i64, vp, i64, i32, i32, P(vp)]
+    L.gwamd_windows_get.restype = i32
+    L.gwamd_windows_get.argtypes = [vp, P(_WindowsView)]
+    L.gwamd_windows_free.restype = None
+    L.gwamd_windows_free.argtypes = [vp]
+
+
+def _take_segments(L, p, n):
+    try:
+        out = np.empty(n.value, SEGMENT_DTYPE)
+        if n.value:
+            C.memmove(out.ctypes.data, p, n.value * SEGMENT_DTYPE.itemsize)
+        return out
+    finally:
+        L.gwamd_window_segments_free(p)
+
+
+_STATE_OF = {"m": 0, "mm": 1, "i": 2, "d": 3}  # the names CudaAlignment.alignment uses
+
+
+def _states(path):
+    return np.asarray([_STATE_OF[s] if isinstance(s, str) else s for s in path], dtype=np.int64).astype(np.int8)
+
+
+def _pack_paths(paths):
+    offsets = np.zeros(len(paths) + 1, np.int64)
+    for i, p in enumerate(paths):
+        offsets[i + 1] = offsets[i] + len(p)
+    states = np.zeros(max(int(offsets[-1]), 1), np.int8)
+    for i, p in enumerate(paths):
+        if len(p):
+            states[offsets[i]:offsets[i + 1]] = _states(p)
+    return states, offsets
+
+
+def window_segments(overlaps, paths, window_length, device_id=0, allocator=None):
+    """The records (a SEGMENT_DTYPE array) of every overlap, in overlap order:
+    overlap i owns those of windows target_start // w .. (target_end - 1) // w.
+
+    paths[i]: the AlignmentState values of overlap i, start -> end (or their
+    names "m", "mm", "i", "d" as CudaAlignment.alignment has them).  One kernel
+    launch; allocator: a cudaaligner.DeviceAllocator whose pool the device
+    arrays are counted against during the call.  ValueError for window_length
+    <= 0, an overlap with start > end, a path longer than the two spans
+    together and more than 2^31 records."""
+    L = load_library()
+    if len(paths) != len(overlaps):
+        raise ValueError("one path per overlap expected")
+    arr = _overlap_array(overlaps)
+    states, offsets = _pack_paths(paths)
+    p, n = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_window_segments(arr, len(overlaps), states.ctypes.data_as(C.c_void_p),
+                                   offsets.ctypes.data_as(C.c_void_p), int(window_length), int(device_id),
+                                   allocator._handle if allocator is not None else None, C.byref(p), C.byref(n)))
+    return _take_segments(L, p, n)
+
+
+def window_segments_host(overlap, path, window_length, overlap_index=0):
+    """The same walk for one overlap on the host, without a GPU."""
+    L = load_library()
+    arr = _overlap_array([overlap])
+    states = _states(list(path) + [0])
+    p, n = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_window_segments_host(arr, states.ctypes.data_as(C.c_void_p), len(path), int(window_length),
+                                        int(overlap_index), C.byref(p), C.byref(n)))
+    return _take_segments(L, p, n)
+
+
+def window_segments_resident(overlaps, query_reads, target_reads, window_length, num_alignment_engines=1):
+    """The overlaps aligned as cudamapper.align_overlaps aligns them on two
+    DeviceReads, and cut on the device from the aligner's own path buffer: only
+    the overlaps go up and the records come back.  An overlap beyond the
+    aligner's limits gets NOT_ALIGNED records."""
+    L = load_library()
+    handles = _handles(query_reads, target_reads)
+    if not handles:
+        raise TypeError("query_reads and target_reads must be DeviceReads")
+    arr = _overlap_array(overlaps)
+    p, n = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_window_segments_resident(*handles, arr, len(overlaps), int(window_length),
+                                            int(num_alignment_engines), C.byref(p), C.byref(n)))
+    return _take_segments(L, p, n)
+
+
+def _window_segments_strided(overlaps, paths, path_lengths, stride, window_length):
+    """Test hook: the cut of paths laid out as the aligner leaves them, end ->
+    start, path i at paths[i * stride:]; paths is a bytes-like of n * stride."""
+    L = load_library()
+    arr = _overlap_array(overlaps)
+    buf = np.frombuffer(bytes(paths) + b"\0", np.int8).copy()
+    lens = np.asarray(list(path_lengths) + [0], dtype=np.int32)
+    p, n = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_internal_window_segments_strided(arr, len(overlaps), buf.ctypes.data_as(C.c_void_p),
+                                                    lens.ctypes.data_as(C.c_void_p), int(stride), int(window_length),
+                                                    C.byref(p), C.byref(n)))
+    return _take_segments(L, p, n)
+
+
+def build_windows(targets, queries, overlaps, segments, window_length, max_sequences_per_window=100):
+    """(windows, dropped): one window per window_length bases of every target,
+    in target then window order, each a dict of "target", "window", "sequences"
+    (the backbone first) and per sequence "overlap" (-1: backbone), "t_begin"
+    and "t_end" relative to the window's first base.  A segment is kept when it
+    is not flagged and (q_end - q_begin) * 50 >= window_length; a REVERSE one
+    is reverse-complemented; at most max_sequences_per_window - 1 per window,
+    and dropped counts what that cap left out.  Host only."""
+    L = load_library()
+    tb, to = _pack(targets)
+    qb, qo = _pack(queries)
+    arr = _overlap_array(overlaps)
+    segs = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+    h = C.c_void_p()
+    _check(L.gwamd_build_windows(tb, to, len(targets), qb, qo, len(queries), arr, len(overlaps),
+                                 segs.ctypes.data_as(C.c_void_p), len(segs), int(window_length),
+                                 int(max_sequences_per_window), C.byref(h)))
+    try:
+        v = _WindowsView()
+        _check(L.gwamd_windows_get(h, C.byref(v)))
+
+        def array(address, count, dtype):
+            if not count:
+                return np.zeros(0, dtype)
+            return np.frombuffer(C.string_at(address, count * np.dtype(dtype).itemsize), dtype)
+
+        bases = C.string_at(v.bases, v.num_bases).decode("latin-1") if v.num_bases else ""
+        off = array(v.sequence_offsets, v.num_sequences + 1, np.int64)
+        counts = array(v.window_counts, v.num_windows, np.int32)
+        target = array(v.window_target, v.num_windows, np.uint32)
+        index = array(v.window_index, v.num_windows, np.uint32)
+        overlap = array(v.sequence_overlap, v.num_sequences, np.int32)
+        t_begin = array(v.sequence_t_begin, v.num_sequences, np.int32)
+        t_end = array(v.sequence_t_end, v.num_sequences, np.int32)
+        windows, s = [], 0
+        for i in range(v.num_windows):
+            c = int(counts[i])
+            windows.append({"target": int(target[i]), "window": int(index[i]),
+                            "sequences": [bases[off[j]:off[j + 1]] for j in range(s, s + c)],
+                            "overlap": overlap[s:s + c].tolist(), "t_begin": t_begin[s:s + c].tolist(),
+                            "t_end": t_end[s:s + c].tolist()})
+            s += c
+        return windows, int(v.dropped_by_cap)
+    finally:
+        L.gwamd_windows_free(h)
+
+
+def polish(targets, queries, overlaps, window_length=500, max_sequences_per_window=100, banded=True,
+           band_width=256, scores=(8, -6, -8), num_alignment_engines=1, device_id=0, max_gpu_mem=None,
+           return_windows=False):
+    """Polished targets from targets, reads and overlaps (query = read, target =
+    target): the overlaps are aligned and cut on the GPU
+    (window_segments_resident), grouped into windows (build_windows) and run
+    through CudaPoaBatch.  A window contributes its consensus when it has at
+    least three sequences and its POA status is success, its backbone
+    otherwise.  scores: (match, mismatch, gap).  max_gpu_mem: the bytes the POA
+    batch may take (default: half of the device's free memory); windows beyond
+    what it holds at once are processed in rounds.
+
+    Returns (polished, stats); stats counts "windows", "backbone_by_rule"
+    (fewer than three sequences), "backbone_by_status", "dropped_by_cap" and
+    carries the "max_sequence_size" the POA batch was made for.  With
+    return_windows the windows and each one's consensus (None for a backbone by
+    rule) and status are appended to the result."""
+    from .cudapoa import CudaPoaBatch
+    import torch
+
+    targets = [t[1] if isinstance(t, tuple) else t for t in targets]
+    queries = [q[1] if isinstance(q, tuple) else q for q in queries]
+    with torch.cuda.device(device_id):
+        q_reads = DeviceReads(queries, device_id=device_id)
+        t_reads = DeviceReads(targets, device_id=device_id)
+        try:
+            segments = window_segments_resident(overlaps, q_reads, t_reads, window_length, num_alignment_engines)
+        finally:
+            q_reads.close()
+            t_reads.close()
+    windows, dropped = build_windows(targets, queries, overlaps, segments, window_length, max_sequences_per_window)
+    stats = {"windows": len(windows), "backbone_by_rule": 0, "backbone_by_status": 0, "dropped_by_cap": dropped}
+    todo = [i for i, w in enumerate(windows) if len(w["sequences"]) >= 3]
+    stats["backbone_by_rule"] = len(windows) - len(todo)
+    longest = max([len(s) for i in todo for s in windows[i]["sequences"]] + [1])
+    # a sequence must be shorter than the batch's limit; sizes in steps of 64
+    max_sequence_size = (longest + 1 + 63) // 64 * 64
+    stats["max_sequence_size"] = max_sequence_size
+    consensus = [None] * len(windows)
+    status = [None] * len(windows)
+    if todo:
+        if max_gpu_mem is None:
+            max_gpu_mem = int(0.5 * torch.cuda.mem_get_info(device_id)[0])
+        batch = CudaPoaBatch(max_sequences_per_window, max_sequence_size, int(max_gpu_mem), device_id=device_id,
+                             gap_score=scores[2], mismatch_score=scores[1], match_score=scores[0],
+                             cuda_banded_alignment=banded, alignment_band_width=band_width)
+        held = []
+
+        def flush():
+            if not held:
+                return
+            batch.generate_poa()
+            cons, _, st = batch.get_consensus()
+            for j, i in enumerate(held):
+                consensus[i], status[i] = cons[j], st[j]
+            batch.reset()
+            del held[:]
+
+        for i in todo:
+            st, _ = batch.add_poa_group(windows[i]["sequences"])
+            if st == 1:  # exceeded_maximum_poas: process what the batch holds, then add again
+                flush()
+                st, _ = batch.add_poa_group(windows[i]["sequences"])
+            if st != 0:
+                status[i] = st
+                continue
+            held.append(i)
+        flush()
+    polished = ["" for _ in targets]
+    for i, w in enumerate(windows):
+        text = w["sequences"][0]
+        if consensus[i] is not None and status[i] == 0:
+            text = consensus[i]
+        elif len(w["sequences"]) >= 3:
+            stats["backbone_by_status"] += 1
+        polished[w["target"]] += text
+    if return_windows:
+        return polished, stats, windows, consensus, status
+    return polished, stats

@@ -11,7 +11,7 @@ parameters) and overlaps/s for the rescue of those overlaps' ends, then checks
 a 16-read subset against the plain-Python models (tests/mapper_model.py,
 tests/overlapper_model.py, tests/rescue_model.py).
 
-Each GPU step (index, match, overlap, rescue, verify) runs in a child process
+Each GPU step (index, match, overlap, rescue, windows, verify) runs in a child process
 of its own under a time limit; a step that fails or runs out of time ends the
 run.
 The timed calls are gwamd_index_create, gwamd_match_anchors (upload, kernels
@@ -24,6 +24,14 @@ overlaps of the overlap step, and next to it, once, the same overlaps through
 three rounds each of gwamd_extend_overlap_by_sequence_similarity on one host
 thread (the loop a caller without the kernel would write; the reverse
 complements it needs are made before the clock starts).
+
+The windows step times cudapolish's cut of those overlaps into target windows
+of 500 bases, host clock: (i) gwamd_window_segments_resident, which aligns the
+overlaps on resident reads and cuts them from the aligner's device paths; (ii)
+the route without the kernel: gwamd_align_overlaps_resident (the same
+alignments, the paths downloaded and turned into CIGARs) followed by
+gwamd_window_segments_host per overlap on one thread, the states expanded from
+the CIGARs before the clock starts.  It compares the two record for record.
 
     python scripts/mapper_throughput.py [--reads 2000] [--length 10000] [--steps 5] [--warmup 2]
 """
@@ -42,7 +50,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 K, W, FILTERING = 15, 10, 0.001
-STEP_TIMEOUT = {"index": 300, "match": 300, "overlap": 300, "rescue": 300, "verify": 300}
+STEP_TIMEOUT = {"index": 300, "match": 300, "overlap": 300, "rescue": 300, "windows": 900, "verify": 300}
+WINDOW_LENGTH = 500  # racon's default
 RESCUE_EXTENSION, RESCUE_SIMILARITY, RESCUE_ROUNDS = 100, 0.9, 3  # what the reference's rescue_overlap_ends runs with
 
 
@@ -134,6 +143,94 @@ def host_rescue(L, reads, overlaps, n):
     return out, time.perf_counter() - t0
 
 
+def states_of_cigars(cigars):
+    """The states (start -> end) the CIGARs stand for, concatenated, and their n + 1 offsets:
+    M is taken as match (the cut does not tell match from mismatch), I as 2, D as 3."""
+    import re
+    token = re.compile(r"(\d+)([MID])")
+    code = {"M": 0, "I": 2, "D": 3}
+    offsets = np.zeros(len(cigars) + 1, np.int64)
+    parts = []
+    for i, c in enumerate(cigars):
+        runs = token.findall(c)
+        counts = np.array([int(r[0]) for r in runs], np.int64)
+        parts.append(np.repeat(np.array([code[r[1]] for r in runs], np.int8), counts))
+        offsets[i + 1] = offsets[i] + int(counts.sum())
+    return (np.concatenate(parts) if parts else np.zeros(0, np.int8)), offsets
+
+
+def windows_step(L, args, bases, offsets, num_reads):
+    from claragenomicsanalysis_amd.cudamapper import Overlap, _take
+    from claragenomicsanalysis_amd.cudapolish import SEGMENT_DTYPE
+    h = create_index(L, bases, offsets, num_reads)
+    found, n = C.c_void_p(), C.c_int64()
+    if L.gwamd_match_overlaps(h, h, -1, 20, 50, 50, 0.9, C.byref(found), C.byref(n), None) != 0:
+        raise RuntimeError(L.gwamd_last_error().decode())
+    L.gwamd_index_free(h)
+    overlaps = (Overlap * max(n.value, 1))()
+    C.memmove(overlaps, found, C.sizeof(Overlap) * n.value)
+    L.gwamd_overlaps_free(found)
+    reads = C.c_void_p()
+    if L.gwamd_device_reads_create(bases, offsets, num_reads, 0, None, C.byref(reads)) != 0:
+        raise RuntimeError(L.gwamd_last_error().decode())
+
+    def check(rc):
+        if rc != 0:
+            raise RuntimeError(L.gwamd_last_error().decode())
+
+    def records(p, count):
+        out = np.empty(count, SEGMENT_DTYPE)
+        if count:
+            C.memmove(out.ctypes.data, p, count * SEGMENT_DTYPE.itemsize)
+        return out
+
+    resident_s, align_s, host_s = [], [], []
+    on_gpu = by_host = cigars = None
+    for step in range(args.warmup + args.steps):
+        p, m = C.c_void_p(), C.c_int64()
+        t0 = time.perf_counter()
+        check(L.gwamd_window_segments_resident(reads, reads, overlaps, n.value, WINDOW_LENGTH, 1, C.byref(p),
+                                               C.byref(m)))
+        resident_s.append(time.perf_counter() - t0)
+        on_gpu = records(p, m.value)
+        L.gwamd_window_segments_free(p)
+    for step in range(args.warmup + args.steps):
+        texts = C.c_void_p()
+        t0 = time.perf_counter()
+        check(L.gwamd_align_overlaps_resident(reads, reads, overlaps, n.value, 1, C.byref(texts)))
+        align_s.append(time.perf_counter() - t0)
+        if step + 1 < args.warmup + args.steps:
+            L.gwamd_text_list_free(texts)
+        else:
+            cigars = _take(L, texts)
+    L.gwamd_device_reads_free(reads)
+    states, state_offsets = states_of_cigars(cigars)
+    address = states.ctypes.data
+    host = L.gwamd_window_segments_host
+    for step in range(args.warmup + args.steps):
+        held = []
+        t0 = time.perf_counter()
+        for i in range(n.value):
+            p, m = C.c_void_p(), C.c_int64()
+            if host(C.byref(overlaps[i]), address + int(state_offsets[i]),
+                    int(state_offsets[i + 1] - state_offsets[i]), WINDOW_LENGTH, i, C.byref(p), C.byref(m)) != 0:
+                raise RuntimeError(L.gwamd_last_error().decode())
+            held.append((p, m.value))
+        host_s.append(time.perf_counter() - t0)
+        by_host = np.concatenate([records(p, count) for p, count in held]) if held else np.zeros(0, SEGMENT_DTYPE)
+        for p, _ in held:
+            L.gwamd_window_segments_free(p)
+    if on_gpu.tobytes() != by_host.tobytes():
+        raise RuntimeError("the cut on the GPU and the host walk differ")
+    flagged = int(np.count_nonzero(on_gpu["flags"] & 12))
+    med = lambda v: float(np.median(v[args.warmup:]))
+    print(json.dumps({"windows_overlaps": n.value, "windows_records": len(on_gpu), "windows_flagged_records": flagged,
+                      "windows_path_states": int(state_offsets[-1]), "windows_resident_s": round(med(resident_s), 6),
+                      "windows_align_download_s": round(med(align_s), 6),
+                      "windows_host_cut_s": round(med(host_s), 6),
+                      "windows_host_route_s": round(med(align_s) + med(host_s), 6)}))
+
+
 def overlap_fields(o):
     return (o.query_read_id, o.target_read_id, o.query_start, o.query_end, o.target_start, o.target_end, o.strand,
             o.num_residues, bool(o.overlap_complete))
@@ -211,6 +308,8 @@ def worker(args):
         wall = float(np.median([s[1] for s in samples]))
         print(json.dumps({"overlaps": n.value, "overlap_anchors": anchors.value, "overlap_event_s": round(ev, 6),
                           "overlap_wall_s": round(wall, 6), "overlap_anchors_per_s": round(anchors.value / ev, 1)}))
+    elif args.worker == "windows":
+        windows_step(L, args, bases, offsets, len(reads))
     elif args.worker == "rescue":
         from claragenomicsanalysis_amd.cudamapper import Overlap
         h = create_index(L, bases, offsets, len(reads))
@@ -286,7 +385,7 @@ def main():
     result = {"metric": "mapper_throughput", "reads": args.reads, "read_length": args.length, "kmer_size": K,
               "window_size": W, "hash_representations": True, "filtering_parameter": FILTERING,
               "steps": args.steps, "warmup": args.warmup}
-    for step in ("index", "match", "overlap", "rescue") + (() if args.no_verify else ("verify",)):
+    for step in ("index", "match", "overlap", "rescue", "windows") + (() if args.no_verify else ("verify",)):
         cmd = [sys.executable, os.path.abspath(__file__), "--worker", step, "--reads", str(args.reads), "--length",
                str(args.length), "--steps", str(args.steps), "--warmup", str(args.warmup)]
         try:

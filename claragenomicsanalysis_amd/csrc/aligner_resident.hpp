@@ -1,7 +1,8 @@
 // The aligner's internal entry for overlaps whose reads are resident on its
 // device (aligner_batch.cpp, AlignerGlobalHip::add_device_overlaps); used by
-// the overlap-alignment caller (overlap_align.cpp), not part of the public
-// Aligner interface.
+// the alignment engines (overlap_engines.hpp, overlap_align.cpp) and by
+// cudapolish's cut on the device paths (polish_windows_host.cpp), not part of
+// the public Aligner interface.
 #pragma once
 
 #include <claraparabricks/genomeworks/cudaaligner/aligner.hpp>

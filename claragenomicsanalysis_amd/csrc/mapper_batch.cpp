@@ -12,9 +12,9 @@
 #include "allocator_handle.hpp"
 #include "mapper_capi.hpp"
 #include "mapper_index_impl.hpp"
+#include "mapper_reads.hpp"
 
 #include <cstddef>
-#include <cstring>
 #include <vector>
 
 namespace gm = gwamd::mapper;
@@ -108,15 +108,9 @@ std::unique_ptr<Index> Index::create_index(DefaultDeviceAllocator allocator, con
     check_index_arguments(parser.get_num_seqences(), first_read_id, past_the_last_read_id, kmer_size, window_size,
                           filtering_parameter);
     const uint32_t n = past_the_last_read_id - first_read_id;
-    std::vector<int64_t> offsets(size_t(n) + 1, 0);
-    for (uint32_t i = 0; i < n; i++)
-        offsets[i + 1] = offsets[i] + int64_t(parser.get_sequence_by_id(first_read_id + i).seq.size());
-    check_read_lengths(offsets.data(), n);
-    std::string bases;
-    bases.reserve(size_t(offsets[n]));
-    for (uint32_t i = 0; i < n; i++)
-        bases += parser.get_sequence_by_id(first_read_id + i).seq;
-    return make_index(bases.data(), offsets.data(), first_read_id, n, int(kmer_size), int(window_size),
+    const gm::PackedReads packed(parser, first_read_id, past_the_last_read_id);
+    check_read_lengths(packed.offsets.data(), n);
+    return make_index(packed.bases.data(), packed.offsets.data(), first_read_id, n, int(kmer_size), int(window_size),
                       hash_representations, filtering_parameter, allocator.budget(), stream);
 }
 
@@ -132,12 +126,6 @@ std::unique_ptr<Matcher> Matcher::create_matcher(DefaultDeviceAllocator allocato
     m->view = {reinterpret_cast<Anchor*>(m->data.data()), std::ptrdiff_t(m->data.size())};
     return m;
 }
-
-static_assert(sizeof(Overlap) == sizeof(gm::OverlapRecord) &&
-                  offsetof(Overlap, relative_strand) == offsetof(gm::OverlapRecord, relative_strand) &&
-                  offsetof(Overlap, num_residues_) == offsetof(gm::OverlapRecord, num_residues) &&
-                  offsetof(Overlap, overlap_complete) == offsetof(gm::OverlapRecord, overlap_complete),
-              "OverlapRecord must match cudamapper::Overlap");
 
 OverlapperTriggered::OverlapperTriggered(DefaultDeviceAllocator allocator, const hipStream_t stream)
     : allocator_(allocator)
@@ -156,8 +144,7 @@ void OverlapperTriggered::get_overlaps(std::vector<Overlap>& fused_overlaps, con
     gm::get_overlaps(records, reinterpret_cast<const gm::AnchorRecord*>(d_anchors.data()), d_anchors.size(), params,
                      allocator_.budget(), stream_);
     fused_overlaps.resize(records.size());
-    if (!records.empty())
-        std::memcpy(static_cast<void*>(fused_overlaps.data()), records.data(), records.size() * sizeof(Overlap));
+    gm::from_records(records, fused_overlaps.data());
 }
 
 namespace
@@ -336,21 +323,10 @@ int32_t match(const gwamd_index* query_index, const gwamd_index* target_index, i
         gwamd::host::ScopedDevice dev(q.device_id);
         gm::DevBuf<gm::AnchorRecord> d;
         gm::match_anchors(d, q, t, max_anchors < 0 ? gm::kDefaultMaxAnchors : max_anchors, budget, nullptr);
-        if (d.size() == 0)
-            return int32_t(0);
-        std::unique_ptr<gwamd_anchor[]> h(new gwamd_anchor[d.size()]);
-        GWAMD_HIP_CHECK(hipMemcpy(h.get(), d.data(), d.size() * sizeof(gwamd_anchor), hipMemcpyDeviceToHost));
-        *num_anchors = int64_t(d.size());
-        *anchors     = h.release();
+        hand_over(d.data(), d.size(), anchors, num_anchors, true);
         return int32_t(0);
     });
 }
-
-static_assert(sizeof(gwamd_overlap) == sizeof(gm::OverlapRecord) && sizeof(gwamd_overlap) == sizeof(cm::Overlap) &&
-                  offsetof(gwamd_overlap, relative_strand) == offsetof(gm::OverlapRecord, relative_strand) &&
-                  offsetof(gwamd_overlap, num_residues) == offsetof(gm::OverlapRecord, num_residues) &&
-                  offsetof(gwamd_overlap, overlap_complete) == offsetof(gm::OverlapRecord, overlap_complete),
-              "gwamd_overlap must match cudamapper::Overlap");
 
 int32_t overlaps_of_anchors(const gwamd_anchor* anchors, int64_t n, int64_t min_residues, int64_t min_overlap_len,
                             int64_t min_bases_per_residue, float min_overlap_fraction, int32_t device_id,
@@ -564,8 +540,7 @@ int32_t gwamd_post_process_overlaps(const gwamd_overlap* in, int64_t n, int32_t 
         if (n > 0 && !in)
             throw std::invalid_argument("in is NULL");
         std::vector<cm::Overlap> overlaps(static_cast<size_t>(n));
-        if (n > 0)
-            std::memcpy(static_cast<void*>(overlaps.data()), in, size_t(n) * sizeof(gwamd_overlap));
+        gm::from_records(gm::to_records(in, n), overlaps.data());
         cm::Overlapper::post_process_overlaps(overlaps, drop_fused_overlaps != 0);
         hand_over(overlaps, out, num_out);
         return int32_t(0);

@@ -1,5 +1,7 @@
-// Reads resident on the device (mapper_reads.hpp): the upload, the argument
-// checks of everything that takes a DeviceReads, the C++ class
+// Reads resident on the device (mapper_reads.hpp): the upload, the one check
+// of a read set and the one check of overlaps against their reads that every
+// entry point of the mapper and of cudapolish forwards to, a parser packed
+// into bases and offsets, the C++ class
 // cudamapper::DeviceReads with the Overlapper::rescue_overlap_ends overload on
 // it, and their C ABI (include/gwamd_cudamapper.h).  Every argument is checked
 // here, on the host copy of the offsets, before any device call, so that no
@@ -36,25 +38,60 @@ void check_read_set(const char* side, const ReadSet& reads)
         throw std::invalid_argument(std::string(side) + " bases is NULL");
 }
 
-void check_overlaps(const DeviceReads& query, const DeviceReads& target, const OverlapRecord* overlaps, int64_t n)
+void check_overlap_count(const void* overlaps, int64_t n)
 {
     if (n < 0 || n >= (int64_t(1) << 31))
         throw std::invalid_argument("the number of overlaps must be between 0 and 2^31, got " + std::to_string(n));
     if (n > 0 && !overlaps)
         throw std::invalid_argument("overlaps is NULL");
+}
+
+void check_overlaps(const int64_t* query_offsets, int64_t num_queries, const int64_t* target_offsets,
+                    int64_t num_targets, const OverlapRecord* overlaps, int64_t n)
+{
+    check_overlap_count(overlaps, n);
     for (int64_t i = 0; i < n; i++)
     {
         const OverlapRecord& o  = overlaps[i];
         const std::string which = "overlap " + std::to_string(i);
-        if (int64_t(o.query_read_id) >= query.num_reads() || int64_t(o.target_read_id) >= target.num_reads())
+        if (int64_t(o.query_read_id) >= num_queries || int64_t(o.target_read_id) >= num_targets)
             throw std::invalid_argument(which + ": read id beyond the reads");
-        if (o.query_start > o.query_end || int64_t(o.query_end) > query.read_length(o.query_read_id))
+        const int64_t query_length  = query_offsets[size_t(o.query_read_id) + 1] - query_offsets[o.query_read_id];
+        const int64_t target_length = target_offsets[size_t(o.target_read_id) + 1] - target_offsets[o.target_read_id];
+        if (o.query_start > o.query_end || int64_t(o.query_end) > query_length)
             throw std::invalid_argument(which + ": query positions are not start <= end <= read length");
-        if (o.target_start > o.target_end || int64_t(o.target_end) > target.read_length(o.target_read_id))
+        if (o.target_start > o.target_end || int64_t(o.target_end) > target_length)
             throw std::invalid_argument(which + ": target positions are not start <= end <= read length");
         if (o.relative_strand != '+' && o.relative_strand != '-')
             throw std::invalid_argument(which + ": relative_strand is neither '+' nor '-'");
     }
+}
+
+void check_on_current_device(const DeviceReads& query, const DeviceReads& target)
+{
+    int current = -1;
+    GWAMD_HIP_CHECK(hipGetDevice(&current));
+    if (query.device_id != current || target.device_id != current)
+        throw std::invalid_argument("the reads are on device " + std::to_string(query.device_id) + " and " +
+                                    std::to_string(target.device_id) + ", the current device is " +
+                                    std::to_string(current));
+}
+
+PackedReads::PackedReads(const claraparabricks::genomeworks::io::FastaParser& parser)
+    : PackedReads(parser, 0, parser.get_num_seqences())
+{
+}
+
+PackedReads::PackedReads(const claraparabricks::genomeworks::io::FastaParser& parser, uint32_t first,
+                         uint32_t past_the_last)
+    : offsets(size_t(past_the_last - first) + 1, 0)
+{
+    const uint32_t n = past_the_last - first;
+    for (uint32_t i = 0; i < n; i++)
+        offsets[i + 1] = offsets[i] + int64_t(parser.get_sequence_by_id(first + i).seq.size());
+    bases.reserve(size_t(offsets[n]));
+    for (uint32_t i = 0; i < n; i++)
+        bases += parser.get_sequence_by_id(first + i).seq;
 }
 
 std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, int device_id, const Budget& budget,
@@ -91,55 +128,16 @@ std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, int device_
 namespace
 {
 
-void check_rescue_numbers(int32_t extension, float required_similarity)
-{
-    if (extension < 0 || extension > gm::kMaxRescueExtension)
-        throw std::invalid_argument("extension must be between 0 and " + std::to_string(gm::kMaxRescueExtension) +
-                                    ", got " + std::to_string(extension));
-    if (required_similarity != required_similarity)
-        throw std::invalid_argument("required_similarity is not a number");
-}
-
-// the last check: the only one that asks the runtime
-void check_on_current_device(const gm::DeviceReads& query, const gm::DeviceReads& target)
-{
-    int current = -1;
-    GWAMD_HIP_CHECK(hipGetDevice(&current));
-    if (query.device_id != current || target.device_id != current)
-        throw std::invalid_argument("the reads are on device " + std::to_string(query.device_id) + " and " +
-                                    std::to_string(target.device_id) + ", the current device is " +
-                                    std::to_string(current));
-}
-
-static_assert(sizeof(cm::Overlap) == sizeof(gm::OverlapRecord) && sizeof(gwamd_overlap) == sizeof(gm::OverlapRecord),
-              "overlaps are copied as bytes (field offsets: mapper_batch.cpp)");
-
 void rescue_resident(const gm::DeviceReads& query, const gm::DeviceReads& target, gm::OverlapRecord* records,
                      int64_t n, int32_t extension, float required_similarity, const gm::Budget& budget)
 {
     gm::check_overlaps(query, target, records, n);
-    check_rescue_numbers(extension, required_similarity);
+    gm::check_rescue_numbers(extension, required_similarity);
     if (n == 0)
         return;
-    check_on_current_device(query, target);
+    gm::check_on_current_device(query, target);
     gm::rescue_overlap_ends(records, n, query, target, extension, required_similarity, budget, nullptr);
 }
-
-struct PackedReads
-{
-    std::string bases;
-    std::vector<int64_t> offsets;
-    explicit PackedReads(const claraparabricks::genomeworks::io::FastaParser& parser)
-        : offsets(size_t(parser.get_num_seqences()) + 1, 0)
-    {
-        const uint32_t n = parser.get_num_seqences();
-        for (uint32_t i = 0; i < n; i++)
-            offsets[i + 1] = offsets[i] + int64_t(parser.get_sequence_by_id(i).seq.size());
-        bases.reserve(size_t(offsets[n]));
-        for (uint32_t i = 0; i < n; i++)
-            bases += parser.get_sequence_by_id(i).seq;
-    }
-};
 
 } // namespace
 
@@ -156,8 +154,8 @@ DeviceReads::~DeviceReads() = default;
 std::unique_ptr<DeviceReads> DeviceReads::create(DefaultDeviceAllocator allocator, const io::FastaParser& parser,
                                                  hipStream_t stream)
 {
-    const PackedReads packed(parser);
-    const gm::ReadSet reads{packed.bases.data(), packed.offsets.data(), int64_t(packed.offsets.size()) - 1};
+    const gm::PackedReads packed(parser);
+    const gm::ReadSet reads = packed.view();
     gm::check_read_set("parser", reads);
     int device_id = 0;
     GWAMD_HIP_CHECK(hipGetDevice(&device_id));
@@ -175,13 +173,10 @@ void Overlapper::rescue_overlap_ends(std::vector<Overlap>& overlaps, const Devic
                                      const DeviceReads& target_reads, const std::int32_t extension,
                                      const float required_similarity)
 {
-    std::vector<gm::OverlapRecord> records(overlaps.size());
-    if (!overlaps.empty())
-        std::memcpy(static_cast<void*>(records.data()), overlaps.data(), overlaps.size() * sizeof(Overlap));
+    std::vector<gm::OverlapRecord> records = gm::to_records(overlaps.data(), int64_t(overlaps.size()));
     rescue_resident(*query_reads.impl().reads, *target_reads.impl().reads, records.data(), int64_t(records.size()),
                     extension, required_similarity, nullptr);
-    if (!overlaps.empty())
-        std::memcpy(static_cast<void*>(overlaps.data()), records.data(), overlaps.size() * sizeof(Overlap));
+    gm::from_records(records, overlaps.data());
 }
 
 } // namespace cudamapper
@@ -256,14 +251,8 @@ int32_t gwamd_rescue_overlap_ends_resident(const gwamd_device_reads* query_reads
             throw std::invalid_argument("out or num_out is NULL");
         if (!query_reads || !target_reads)
             throw std::invalid_argument("query_reads or target_reads is NULL");
-        if (n < 0 || n >= (int64_t(1) << 31))
-            throw std::invalid_argument("the number of overlaps must be between 0 and 2^31, got " +
-                                        std::to_string(n));
-        if (n > 0 && !overlaps)
-            throw std::invalid_argument("overlaps is NULL");
-        std::vector<gm::OverlapRecord> records(static_cast<size_t>(n));
-        if (n > 0)
-            std::memcpy(static_cast<void*>(records.data()), overlaps, size_t(n) * sizeof(gwamd_overlap));
+        gm::check_overlap_count(overlaps, n);
+        std::vector<gm::OverlapRecord> records = gm::to_records(overlaps, n);
         rescue_resident(*query_reads->reads, *target_reads->reads, records.data(), n, extension, required_similarity,
                         allocator_or_null ? allocator_or_null->alloc.budget() : nullptr);
         gm::hand_over(records, out, num_out);
@@ -278,18 +267,14 @@ int32_t gwamd_internal_gather_overlap_regions(const gwamd_device_reads* query_re
     return gm::guarded_map([&] {
         if (!query_reads || !target_reads)
             throw std::invalid_argument("query_reads or target_reads is NULL");
-        if (n < 0 || n >= (int64_t(1) << 31))
-            throw std::invalid_argument("the number of overlaps must be between 0 and 2^31, got " +
-                                        std::to_string(n));
-        if (n > 0 && (!overlaps || !seqs_out || !lens_out))
-            throw std::invalid_argument("overlaps, seqs_out or lens_out is NULL");
+        gm::check_overlap_count(overlaps, n);
+        if (n > 0 && (!seqs_out || !lens_out))
+            throw std::invalid_argument("seqs_out or lens_out is NULL");
         if (stride < 1 || stride >= (int64_t(1) << 31) || 2 * n * stride >= (int64_t(1) << 31))
             throw std::invalid_argument("stride must be at least 1 and 2 n stride below 2^31");
         const gm::DeviceReads& query  = *query_reads->reads;
         const gm::DeviceReads& target = *target_reads->reads;
-        std::vector<gm::OverlapRecord> records(static_cast<size_t>(n));
-        if (n > 0)
-            std::memcpy(static_cast<void*>(records.data()), overlaps, size_t(n) * sizeof(gwamd_overlap));
+        const std::vector<gm::OverlapRecord> records = gm::to_records(overlaps, n);
         gm::check_overlaps(query, target, records.data(), n);
         for (int64_t i = 0; i < n; i++)
             if (int64_t(records[size_t(i)].query_end - records[size_t(i)].query_start) > stride ||
@@ -297,7 +282,7 @@ int32_t gwamd_internal_gather_overlap_regions(const gwamd_device_reads* query_re
                 throw std::invalid_argument("overlap " + std::to_string(i) + ": a region is longer than stride");
         if (n == 0)
             return int32_t(0);
-        check_on_current_device(query, target);
+        gm::check_on_current_device(query, target);
         gm::DevBuf<gm::OverlapRecord> d_records(size_t(n), nullptr);
         gm::DevBuf<char> d_seqs(size_t(2 * n * stride), nullptr);
         gm::DevBuf<int32_t> d_lens(size_t(2 * n), nullptr);

@@ -1,7 +1,8 @@
 // The reads of one parser resident on a device (mapper_reads.cpp): packed bases
 // and n + 1 offsets, uploaded once and then read in place by the overlap-end
 // rescue (mapper_rescue.hip) and by the gather of overlap regions into the
-// aligner's sequence buffer (mapper_gather.hip).
+// aligner's sequence buffer (mapper_gather.hip).  Also what every caller checks
+// its reads and overlaps with, on the host, before any device call.
 #pragma once
 
 #include <claraparabricks/genomeworks/cudamapper/device_reads.hpp>
@@ -10,6 +11,7 @@
 
 #include <cstdint>
 #include <memory>
+#include <string>
 #include <vector>
 
 namespace gwamd
@@ -45,9 +47,37 @@ std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, int device_
 // something to read, offsets that fall and a read of 2^31 bases or more.
 void check_read_set(const char* side, const ReadSet& reads);
 
-// Throws std::invalid_argument unless every overlap names reads of the two
-// sets, has start <= end <= read length on both and a strand of '+' or '-'.
-void check_overlaps(const DeviceReads& query, const DeviceReads& target, const OverlapRecord* overlaps, int64_t n);
+// Throws std::invalid_argument for a count outside [0, 2^31) and for NULL overlaps with n > 0.
+void check_overlap_count(const void* overlaps, int64_t n);
+
+// The above, and throws std::invalid_argument unless every overlap names reads
+// of the two sets (their n + 1 offsets and counts, checked by the caller), has
+// start <= end <= read length on both and a strand of '+' or '-'.
+void check_overlaps(const int64_t* query_offsets, int64_t num_queries, const int64_t* target_offsets,
+                    int64_t num_targets, const OverlapRecord* overlaps, int64_t n);
+inline void check_overlaps(const ReadSet& query, const ReadSet& target, const OverlapRecord* overlaps, int64_t n)
+{
+    check_overlaps(query.offsets, query.num_reads, target.offsets, target.num_reads, overlaps, n);
+}
+inline void check_overlaps(const DeviceReads& query, const DeviceReads& target, const OverlapRecord* overlaps, int64_t n)
+{
+    check_overlaps(query.offsets.data(), query.num_reads(), target.offsets.data(), target.num_reads(), overlaps, n);
+}
+
+// The last check of a call on resident reads, the only one that asks the
+// runtime: throws std::invalid_argument unless both are on the current device.
+void check_on_current_device(const DeviceReads& query, const DeviceReads& target);
+
+// The reads [first, past_the_last) of a parser (all of them by default) packed
+// into bases and n + 1 offsets that begin at 0
+struct PackedReads
+{
+    std::string bases;
+    std::vector<int64_t> offsets;
+    explicit PackedReads(const claraparabricks::genomeworks::io::FastaParser& parser);
+    PackedReads(const claraparabricks::genomeworks::io::FastaParser& parser, uint32_t first, uint32_t past_the_last);
+    ReadSet view() const { return {bases.data(), offsets.data(), int64_t(offsets.size()) - 1}; }
+};
 
 // rescue_overlap_ends on reads that are resident: only the overlaps travel.
 void rescue_overlap_ends(OverlapRecord* overlaps, int64_t n, const DeviceReads& query, const DeviceReads& target,

@@ -1,7 +1,7 @@
 // Internal declarations of cudapolish's window cut (polish_windows.hip: the
 // kernel and its launch; polish_windows_host.cpp: the checks, the record
-// layout, the host walk, the grouping and the C ABI; overlap_align.cpp: the
-// cut on the aligner's device paths).
+// layout, the host walk, the one cut launch, the cut on the aligner's device
+// paths through the engines of overlap_engines.hpp, the grouping and the C ABI).
 #pragma once
 
 #include "../../include/gwamd_polish.h"
@@ -73,8 +73,8 @@ void walk_on_host(gwamd_window_segment* records, uint32_t count, uint32_t index,
                   const int8_t* states, int64_t num_states, int32_t window_length);
 
 // The checked overlaps aligned on resident reads by num_alignment_engines
-// engines and cut on each aligner's stream from its device paths
-// (overlap_align.cpp); out receives every record, completed.
+// engines (overlap_engines.hpp) and cut on each aligner's stream from its
+// device paths; out receives every record, completed.
 void window_segments_resident(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target,
                               const OverlapRecord* overlaps, int32_t n, int32_t window_length,
                               int32_t num_alignment_engines, std::vector<gwamd_window_segment>& out);

@@ -1,8 +1,10 @@
 // Host side of cudapolish (include/gwamd_polish.h,
 // claraparabricks/genomeworks/cudapolish/windows.hpp): the argument checks, the
 // layout of the records, the walk of one path on the host, the completion of
-// the records the kernel leaves (polish_windows.hip), the grouping into
-// cudapoa groups and the C ABI.  Every argument is checked here, before any
+// the records the kernel leaves (polish_windows.hip), the one launch of the
+// cut (cut_launch) for paths from the host and for the aligner's device paths
+// (window_segments_resident, on the engines of overlap_engines.hpp), the
+// grouping into cudapoa groups and the C ABI.  Every argument is checked here, before any
 // device call, so that the kernel is never given an overlap with start > end or
 // a record range it does not own.
 //
@@ -16,6 +18,7 @@
 #include "allocator_handle.hpp"
 #include "mapper_capi.hpp"
 #include "mapper_reads.hpp"
+#include "overlap_engines.hpp"
 #include "polish_windows.hpp"
 
 #include <algorithm>
@@ -147,15 +150,12 @@ namespace
 {
 
 // what every entry point asks of its overlaps before anything else
-void check_cut_overlaps(const gwamd_overlap* overlaps, int64_t n, std::vector<OverlapRecord>& records)
+// (there are no reads to check them against; positions of 2^31 or more are refused here only)
+template <typename T>
+void check_cut_overlaps(const T* overlaps, int64_t n, std::vector<OverlapRecord>& records)
 {
-    if (n < 0 || n >= (int64_t(1) << 31))
-        throw std::invalid_argument("the number of overlaps must be between 0 and 2^31, got " + std::to_string(n));
-    if (n > 0 && !overlaps)
-        throw std::invalid_argument("overlaps is NULL");
-    records.resize(size_t(n));
-    if (n > 0)
-        std::memcpy(static_cast<void*>(records.data()), overlaps, size_t(n) * sizeof(gwamd_overlap));
+    gm::check_overlap_count(overlaps, n);
+    records = gm::to_records(overlaps, n);
     for (int64_t i = 0; i < n; i++)
     {
         const OverlapRecord& o = records[size_t(i)];
@@ -176,16 +176,6 @@ void check_path_length(const OverlapRecord& o, int64_t i, int64_t length)
         throw std::invalid_argument("path " + std::to_string(i) + " is longer than its overlap's two spans together");
 }
 
-void hand_over(std::vector<gwamd_window_segment>& records, gwamd_window_segment** out, int64_t* num_out)
-{
-    if (records.empty())
-        return;
-    std::unique_ptr<gwamd_window_segment[]> h(new gwamd_window_segment[records.size()]);
-    std::memcpy(static_cast<void*>(h.get()), records.data(), records.size() * sizeof(gwamd_window_segment));
-    *num_out = int64_t(records.size());
-    *out     = h.release();
-}
-
 void clear_outputs(gwamd_window_segment** out, int64_t* num_out)
 {
     if (out)
@@ -195,11 +185,56 @@ void clear_outputs(gwamd_window_segment** out, int64_t* num_out)
 }
 
 template <typename T>
-void upload(gm::DevBuf<T>& d, const T* src, size_t count, const Budget& budget)
+void upload(gm::DevBuf<T>& d, const T* src, size_t count, const Budget& budget, hipStream_t stream)
 {
     d.alloc(count, budget);
     if (count > 0)
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d.data(), src, count * sizeof(T), hipMemcpyHostToDevice, nullptr));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d.data(), src, count * sizeof(T), hipMemcpyHostToDevice, stream));
+}
+
+// The records of one launch, completed, where `layout` puts them, and what
+// the kernel said of each overlap's path (0 or 1, it does not fit)
+struct CutRecords
+{
+    RecordLayout layout;
+    std::vector<gwamd_window_segment> records;
+    std::vector<uint32_t> status;
+};
+
+// The one launch of the cut: n > 0 checked overlaps in host memory whose paths
+// `source` names on the device.  The overlaps and the record bases go up, the
+// records are zeroed, the kernel runs on stream, records and status come back
+// and complete_records writes the rest; the records of overlap i carry
+// index[i] (null: i).  Returns after the stream has been synchronized.
+CutRecords cut_launch(const PathSource& source, const OverlapRecord* overlaps, int64_t n, const int32_t* index,
+                      int32_t window_length, const Budget& budget, hipStream_t stream)
+{
+    CutRecords out;
+    out.layout = plan_records(overlaps, n, window_length);
+    out.records.assign(size_t(out.layout.total()), gwamd_window_segment{});
+    out.status.assign(size_t(n), 0);
+    const std::vector<uint32_t>& base = out.layout.base;
+    gm::DevBuf<OverlapRecord> d_overlaps;
+    gm::DevBuf<uint32_t> d_base;
+    upload(d_overlaps, overlaps, size_t(n), budget, stream);
+    upload(d_base, base.data(), size_t(n), budget, stream);
+    gm::DevBuf<uint32_t> d_status(size_t(n), budget);
+    gm::DevBuf<gwamd_window_segment> d_records(std::max<size_t>(out.records.size(), 1), budget);
+    GWAMD_HIP_CHECK(hipMemsetAsync(d_records.data(), 0, d_records.size() * sizeof(gwamd_window_segment), stream));
+    launch_window_cut(source, d_overlaps.data(), d_base.data(), d_records.data(), d_status.data(), n, window_length,
+                      stream);
+    if (!out.records.empty())
+        GWAMD_HIP_CHECK(hipMemcpyAsync(out.records.data(), d_records.data(),
+                                       out.records.size() * sizeof(gwamd_window_segment), hipMemcpyDeviceToHost,
+                                       stream));
+    GWAMD_HIP_CHECK(hipMemcpyAsync(out.status.data(), d_status.data(), size_t(n) * sizeof(uint32_t),
+                                   hipMemcpyDeviceToHost, stream));
+    GWAMD_HIP_CHECK(hipStreamSynchronize(stream));
+    for (int64_t i = 0; i < n; i++)
+        complete_records(out.records.data() + base[size_t(i)], base[size_t(i) + 1] - base[size_t(i)],
+                         index ? uint32_t(index[i]) : uint32_t(i), overlaps[i], window_length,
+                         out.status[size_t(i)] ? GWAMD_SEGMENT_BAD_PATH : 0);
+    return out;
 }
 
 // One launch over checked overlaps whose paths are in host memory: `bytes`
@@ -209,26 +244,15 @@ void cut_on_device(const std::vector<OverlapRecord>& overlaps, const int8_t* pat
                    int32_t max_length, bool end_to_start, int32_t window_length, const Budget& budget,
                    std::vector<gwamd_window_segment>& out)
 {
-    const int64_t n           = int64_t(overlaps.size());
-    const RecordLayout layout = plan_records(overlaps.data(), n, window_length);
-    out.assign(size_t(layout.total()), gwamd_window_segment{});
-    gm::DevBuf<OverlapRecord> d_overlaps;
-    gm::DevBuf<uint32_t> d_base, d_status;
-    gm::DevBuf<int8_t> d_paths;
+    const size_t n = overlaps.size();
+    gm::DevBuf<int8_t> d_paths(size_t(std::max<int64_t>(bytes, 16)), budget);
     gm::DevBuf<int64_t> d_offsets;
     gm::DevBuf<int32_t> d_lengths;
-    gm::DevBuf<gwamd_window_segment> d_records;
-    upload(d_overlaps, overlaps.data(), size_t(n), budget);
-    upload(d_base, layout.base.data(), size_t(n), budget);
-    d_paths.alloc(size_t(std::max<int64_t>(bytes, 16)), budget);
     if (bytes > 0)
         GWAMD_HIP_CHECK(hipMemcpyAsync(d_paths.data(), paths, size_t(bytes), hipMemcpyHostToDevice, nullptr));
     if (offsets)
-        upload(d_offsets, offsets->data(), size_t(n), budget);
-    upload(d_lengths, lengths.data(), size_t(n), budget);
-    d_status.alloc(size_t(n), budget);
-    d_records.alloc(std::max<size_t>(out.size(), 1), budget);
-    GWAMD_HIP_CHECK(hipMemsetAsync(d_records.data(), 0, d_records.size() * sizeof(gwamd_window_segment), nullptr));
+        upload(d_offsets, offsets->data(), n, budget, nullptr);
+    upload(d_lengths, lengths.data(), n, budget, nullptr);
     PathSource source;
     source.paths        = d_paths.data();
     source.paths_bytes  = bytes;
@@ -237,19 +261,7 @@ void cut_on_device(const std::vector<OverlapRecord>& overlaps, const int8_t* pat
     source.lengths      = d_lengths.data();
     source.max_length   = max_length;
     source.end_to_start = end_to_start;
-    launch_window_cut(source, d_overlaps.data(), d_base.data(), d_records.data(), d_status.data(), n, window_length,
-                      nullptr);
-    std::vector<uint32_t> status(static_cast<size_t>(n));
-    if (!out.empty())
-        GWAMD_HIP_CHECK(hipMemcpyAsync(out.data(), d_records.data(), out.size() * sizeof(gwamd_window_segment),
-                                       hipMemcpyDeviceToHost, nullptr));
-    GWAMD_HIP_CHECK(hipMemcpyAsync(status.data(), d_status.data(), size_t(n) * sizeof(uint32_t),
-                                   hipMemcpyDeviceToHost, nullptr));
-    GWAMD_HIP_CHECK(hipStreamSynchronize(nullptr));
-    for (int64_t i = 0; i < n; i++)
-        complete_records(out.data() + layout.base[size_t(i)], layout.base[size_t(i) + 1] - layout.base[size_t(i)],
-                         uint32_t(i), overlaps[size_t(i)], window_length,
-                         status[size_t(i)] ? GWAMD_SEGMENT_BAD_PATH : 0);
+    out = cut_launch(source, overlaps.data(), int64_t(n), nullptr, window_length, budget, nullptr).records;
 }
 
 // The cut of host paths (start -> end): each path is packed on a 16-byte
@@ -291,6 +303,48 @@ void check_states(const std::vector<OverlapRecord>& overlaps, const int8_t* stat
 
 } // namespace
 
+void window_segments_resident(const gwamd::mapper::DeviceReads& query, const gwamd::mapper::DeviceReads& target,
+                              const OverlapRecord* overlaps, int32_t n, int32_t window_length,
+                              int32_t num_alignment_engines, std::vector<gwamd_window_segment>& out)
+{
+    namespace ga              = gwamd::aln;
+    const RecordLayout layout = plan_records(overlaps, n, window_length);
+    out.assign(size_t(layout.total()), gwamd_window_segment{});
+    const ga::ResidentOverlaps pairs(overlaps, n);
+    // After the align_all() of the kept overlaps [start, end): the cut runs on
+    // the aligner's stream over its device paths, and the records of the range
+    // go to the places the layout of the whole call gives them.
+    const ga::RangeFn cut = [&](claraparabricks::genomeworks::cudaaligner::Aligner& aligner, int32_t start,
+                                int32_t end) {
+        const ga::DevicePaths p = ga::device_paths(aligner);
+        PathSource source;
+        source.paths        = p.paths;
+        source.paths_bytes  = p.bytes;
+        source.stride       = p.max_path_length;
+        source.lengths      = p.lengths;
+        source.max_length   = p.max_path_length;
+        source.end_to_start = true;
+        const CutRecords batch = cut_launch(source, pairs.kept_records.data() + start, end - start,
+                                            pairs.kept.data() + start, window_length, nullptr, p.stream);
+        for (int32_t k = 0; k < end - start; k++)
+        {
+            const uint32_t from = batch.layout.base[size_t(k)], count = batch.layout.base[size_t(k) + 1] - from;
+            if (count > 0)
+                std::memcpy(static_cast<void*>(out.data() + layout.base[size_t(pairs.kept[size_t(start + k)])]),
+                            batch.records.data() + from, size_t(count) * sizeof(gwamd_window_segment));
+        }
+    };
+    ga::run_engines(pairs.lengths, pairs.kept, num_alignment_engines, {pairs.add(query, target), cut, true});
+    // the overlaps the aligner's limits left out
+    std::vector<bool> aligned(static_cast<size_t>(n), false);
+    for (int32_t i : pairs.kept)
+        aligned[size_t(i)] = true;
+    for (int32_t i = 0; i < n; i++)
+        if (!aligned[size_t(i)])
+            complete_records(out.data() + layout.base[size_t(i)], layout.base[size_t(i) + 1] - layout.base[size_t(i)],
+                             uint32_t(i), overlaps[i], window_length, GWAMD_SEGMENT_NOT_ALIGNED);
+}
+
 } // namespace polish
 } // namespace gwamd
 
@@ -300,11 +354,6 @@ namespace
 {
 
 char complement(char c) { return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c; }
-
-void check_sequences(const char* side, const char* bases, const int64_t* offsets, int32_t n)
-{
-    gm::check_read_set(side, gm::ReadSet{bases, offsets, n});
-}
 
 std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const gm::ReadSet& queries,
                                              const std::vector<gm::OverlapRecord>& overlaps,
@@ -383,29 +432,10 @@ std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const g
     return out;
 }
 
-struct PackedParser
-{
-    std::string bases;
-    std::vector<int64_t> offsets;
-    explicit PackedParser(const gw::io::FastaParser& parser)
-        : offsets(size_t(parser.get_num_seqences()) + 1, 0)
-    {
-        const uint32_t n = parser.get_num_seqences();
-        for (uint32_t i = 0; i < n; i++)
-        {
-            offsets[i + 1] = offsets[i] + int64_t(parser.get_sequence_by_id(i).seq.size());
-            bases += parser.get_sequence_by_id(i).seq;
-        }
-    }
-    gm::ReadSet view() const { return {bases.data(), offsets.data(), int64_t(offsets.size()) - 1}; }
-};
-
 std::vector<gm::OverlapRecord> as_records(const std::vector<gw::cudamapper::Overlap>& overlaps)
 {
-    static_assert(sizeof(gw::cudamapper::Overlap) == sizeof(gwamd_overlap), "overlaps are copied as bytes");
     std::vector<gm::OverlapRecord> records;
-    gp::check_cut_overlaps(reinterpret_cast<const gwamd_overlap*>(overlaps.data()), int64_t(overlaps.size()),
-                           records);
+    gp::check_cut_overlaps(overlaps.data(), int64_t(overlaps.size()), records);
     return records;
 }
 
@@ -415,16 +445,6 @@ std::vector<gw::cudapolish::WindowSegment> as_segments(const std::vector<gwamd_w
     if (!records.empty())
         std::memcpy(static_cast<void*>(out.data()), records.data(), records.size() * sizeof(gwamd_window_segment));
     return out;
-}
-
-void check_on_current_device(const gm::DeviceReads& query, const gm::DeviceReads& target)
-{
-    int current = -1;
-    GWAMD_HIP_CHECK(hipGetDevice(&current));
-    if (query.device_id != current || target.device_id != current)
-        throw std::invalid_argument("the reads are on device " + std::to_string(query.device_id) + " and " +
-                                    std::to_string(target.device_id) + ", the current device is " +
-                                    std::to_string(current));
 }
 
 // the checks of the resident cut, then the cut
@@ -439,7 +459,7 @@ void cut_resident(const gm::DeviceReads& query, const gm::DeviceReads& target,
     out.clear();
     if (records.empty())
         return;
-    check_on_current_device(query, target);
+    gm::check_on_current_device(query, target);
     gp::window_segments_resident(query, target, records.data(), int32_t(records.size()), window_length,
                                  num_alignment_engines, out);
 }
@@ -494,7 +514,7 @@ Windows build_windows(const io::FastaParser& targets, const io::FastaParser& que
                       const std::vector<cudamapper::Overlap>& overlaps, const std::vector<WindowSegment>& segments,
                       int32_t window_length, int32_t max_sequences_per_window)
 {
-    const PackedParser t(targets), q(queries);
+    const gm::PackedReads t(targets), q(queries);
     const std::unique_ptr<gwamd_windows> h =
         group_windows(t.view(), q.view(), as_records(overlaps),
                       reinterpret_cast<const gwamd_window_segment*>(segments.data()), int64_t(segments.size()),
@@ -549,7 +569,7 @@ int32_t gwamd_window_segments(const gwamd_overlap* overlaps, int64_t n, const in
         std::vector<gwamd_window_segment> result;
         gp::cut_host_paths(records, states, state_offsets, window_length,
                            allocator_or_null ? allocator_or_null->alloc.budget() : nullptr, result);
-        gp::hand_over(result, out, num_out);
+        gm::hand_over(result, out, num_out);
         return int32_t(0);
     });
 }
@@ -573,7 +593,7 @@ int32_t gwamd_window_segments_host(const gwamd_overlap* overlap, const int8_t* s
         std::vector<gwamd_window_segment> result(static_cast<size_t>(layout.total()));
         gp::walk_on_host(result.data(), uint32_t(result.size()), overlap_index, records[0], states, num_states,
                          window_length);
-        gp::hand_over(result, out, num_out);
+        gm::hand_over(result, out, num_out);
         return int32_t(0);
     });
 }
@@ -593,7 +613,7 @@ int32_t gwamd_window_segments_resident(const gwamd_device_reads* query_reads, co
         std::vector<gwamd_window_segment> result;
         cut_resident(*query_reads->reads, *target_reads->reads, records, window_length, num_alignment_engines,
                      result);
-        gp::hand_over(result, out, num_out);
+        gm::hand_over(result, out, num_out);
         return int32_t(0);
     });
 }
@@ -624,7 +644,7 @@ int32_t gwamd_internal_window_segments_strided(const gwamd_overlap* overlaps, in
         gp::cut_on_device(records, paths, n * stride, nullptr, stride,
                           std::vector<int32_t>(path_lengths, path_lengths + n), int32_t(stride), true, window_length,
                           nullptr, result);
-        gp::hand_over(result, out, num_out);
+        gm::hand_over(result, out, num_out);
         return int32_t(0);
     });
 }
@@ -640,12 +660,14 @@ int32_t gwamd_build_windows(const char* target_bases, const int64_t* target_offs
     return gm::guarded_map([&] {
         if (!out)
             throw std::invalid_argument("out is NULL");
-        check_sequences("target", target_bases, target_offsets, num_targets);
-        check_sequences("query", query_bases, query_offsets, num_queries);
+        const gm::ReadSet targets{target_bases, target_offsets, num_targets};
+        const gm::ReadSet queries{query_bases, query_offsets, num_queries};
+        gm::check_read_set("target", targets);
+        gm::check_read_set("query", queries);
         std::vector<gm::OverlapRecord> records;
         gp::check_cut_overlaps(overlaps, n, records);
-        *out = group_windows({target_bases, target_offsets, num_targets}, {query_bases, query_offsets, num_queries},
-                             records, segments, num_segments, window_length, max_sequences_per_window)
+        *out = group_windows(targets, queries, records, segments, num_segments, window_length,
+                             max_sequences_per_window)
                    .release();
         return int32_t(0);
     });

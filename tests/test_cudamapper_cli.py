@@ -248,7 +248,7 @@ def _mutate(rng, s, err):
 
 
 def _paf_line(o, cigar, names, lengths, k):
-    # the columns of format_paf_impl (csrc/overlap_align.cpp): name, length, start, end, strand, name,
+    # the columns of format_paf_impl (csrc/paf_format.cpp): name, length, start, end, strand, name,
     # length, start, end, residues x k, the longer span, mapping quality 255, then the cg:Z: tag
     q, t, qs, qe, ts, te, strand, residues, _ = o
     columns = [names[q], lengths[q], qs, qe, strand, names[t], lengths[t], ts, te, residues * k,

@@ -221,6 +221,31 @@ def test_resident_route(cudapolish, resident_input):
     assert not any(r[6] & (pm.BAD_PATH | pm.NOT_ALIGNED) for r in one)
 
 
+def test_resident_route_with_an_overlap_past_the_aligners_limit(cudapolish, resident_input):
+    """One overlap in the middle of the list is left out by the aligner's limits: every overlap
+    after it has another index among the aligned ones than in the call, and with two engines one
+    batch begins past the first aligned overlap."""
+    from claragenomicsanalysis_amd.cudaaligner import max_lengths
+    from claragenomicsanalysis_amd.cudamapper import DeviceReads
+    from oracle import oracle
+    targets, queries, overlaps = resident_input
+    limit = max_lengths("hirschberg_myers")[0]
+    queries = queries + ["ACGT" * (limit // 4) + "A"]
+    assert len(queries[-1]) == limit + 1
+    at = len(overlaps) // 2
+    overlaps = overlaps[:at] + [(len(queries) - 1, 0, 0, limit + 1, 0, 100, "+")] + overlaps[at:]
+    with DeviceReads(queries) as q, DeviceReads(targets) as t:
+        one = pc.as_tuples(cudapolish.window_segments_resident(overlaps, q, t, 16, num_alignment_engines=1))
+        two = pc.as_tuples(cudapolish.window_segments_resident(overlaps, q, t, 16, num_alignment_engines=2))
+    assert one == two
+    aligned = [i != at for i in range(len(overlaps))]
+    paths = pc.oracle_paths(oracle, queries, targets, overlaps[:at]) + [[]] + \
+        pc.oracle_paths(oracle, queries, targets, overlaps[at + 1:])
+    expected = pm.window_segments(overlaps, paths, 16, aligned)
+    assert [r for r in expected if r[0] == at] == [(at, j, 0, 0, 0, 0, pm.EMPTY | pm.NOT_ALIGNED, 0) for j in range(7)]
+    assert one == expected
+
+
 def test_cpp_interface(tmp_path):
     import subprocess
     r = subprocess.run([pc.build_cpp_check(tmp_path), "gpu"], capture_output=True, text=True, timeout=120)

@@ -12,10 +12,10 @@ from .cudamapper import (Index, match_anchors, get_overlaps, match_overlaps, pos
                          rescue_overlap_ends, extend_overlap_by_sequence_similarity, DeviceReads,
                          group_reads_into_indices, generate_batches_of_indices, IndexHostCopy)
 from .cudapolish import (window_segments, window_segments_host, window_segments_resident,  # noqa: F401
-                         build_windows, polish)
+                         build_windows, build_window_slices, trim_consensus, polish)
 
 __all__ = ["load_library", "library_path", "Index", "match_anchors", "get_overlaps", "match_overlaps",
            "post_process_overlaps", "rescue_overlap_ends", "extend_overlap_by_sequence_similarity",
            "DeviceReads", "group_reads_into_indices", "generate_batches_of_indices",
            "IndexHostCopy", "window_segments", "window_segments_host", "window_segments_resident",
-           "build_windows", "polish"]
+           "build_windows", "build_window_slices", "trim_consensus", "polish"]

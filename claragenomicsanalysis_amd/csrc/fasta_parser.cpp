@@ -20,18 +20,28 @@ namespace
 class FastaParserMem : public FastaParser
 {
 public:
-    explicit FastaParserMem(std::vector<FastaSequence> reads)
+    explicit FastaParserMem(std::vector<FastaSequence> reads, std::vector<std::string> qualities = {})
         : reads_(std::move(reads))
+        , qualities_(std::move(qualities))
     {
+        if (!qualities_.empty() && qualities_.size() != reads_.size())
+            throw std::invalid_argument("one quality string per record expected");
     }
     number_of_reads_t get_num_seqences() const override { return number_of_reads_t(reads_.size()); }
     const FastaSequence& get_sequence_by_id(read_id_t sequence_id) const override
     {
         return reads_.at(sequence_id);
     }
+    const std::string& get_quality_by_id(read_id_t sequence_id) const override
+    {
+        if (qualities_.empty())
+            return FastaParser::get_quality_by_id(sequence_id);
+        return qualities_.at(sequence_id);
+    }
 
 private:
     std::vector<FastaSequence> reads_;
+    std::vector<std::string> qualities_; // empty, or one per record
 };
 
 std::string first_word(const std::string& header)
@@ -41,8 +51,9 @@ std::string first_word(const std::string& header)
 }
 
 // FASTA and FASTQ records as kseq reads them: '>' or '@' header, sequence
-// lines up to the next header ('+' separator and quality lines for FASTQ)
-std::vector<FastaSequence> read_records(const std::string& path)
+// lines up to the next header ('+' separator and quality lines for FASTQ).
+// qualities receives one string per record, empty for a FASTA record.
+std::vector<FastaSequence> read_records(const std::string& path, std::vector<std::string>& qualities)
 {
     std::ifstream in(path);
     if (!in.good())
@@ -60,6 +71,7 @@ std::vector<FastaSequence> read_records(const std::string& path)
         {
             fastq = line[0] == '@';
             out.push_back(FastaSequence{first_word(line), std::string()});
+            qualities.emplace_back();
             if (fastq)
             {
                 // sequence lines up to '+', then as many quality characters
@@ -69,9 +81,9 @@ std::vector<FastaSequence> read_records(const std::string& path)
                         line.pop_back();
                     out.back().seq += line;
                 }
-                size_t qual = 0;
-                while (qual < out.back().seq.size() && std::getline(in, line))
-                    qual += line.size() - (line.size() && line.back() == '\r' ? 1 : 0);
+                std::string& qual = qualities.back();
+                while (qual.size() < out.back().seq.size() && std::getline(in, line))
+                    qual.append(line, 0, line.size() - (line.size() && line.back() == '\r' ? 1 : 0));
             }
         }
         else if (!out.empty() && !fastq)
@@ -87,18 +99,37 @@ std::vector<FastaSequence> read_records(const std::string& path)
 std::unique_ptr<FastaParser> create_kseq_fasta_parser(const std::string& fasta_file,
                                                       number_of_basepairs_t min_sequence_length, bool shuffle)
 {
-    std::vector<FastaSequence> all = read_records(fasta_file);
-    std::vector<FastaSequence> kept;
+    std::vector<std::string> all_qualities;
+    std::vector<FastaSequence> all = read_records(fasta_file, all_qualities);
+    std::vector<size_t> kept;
     kept.reserve(all.size());
-    for (auto& r : all)
-        if (number_of_basepairs_t(r.seq.size()) >= min_sequence_length)
-            kept.push_back(std::move(r));
+    for (size_t i = 0; i < all.size(); i++)
+        if (number_of_basepairs_t(all[i].seq.size()) >= min_sequence_length)
+            kept.push_back(i);
     if (shuffle) // kseqpp_fasta_parser.cpp:58-63: deterministic order
     {
+        // the permutation std::shuffle gives the records themselves: it looks at positions only
         std::mt19937 g(0);
         std::shuffle(kept.begin(), kept.end(), g);
     }
-    return std::make_unique<FastaParserMem>(std::move(kept));
+    std::vector<FastaSequence> reads;
+    std::vector<std::string> qualities;
+    reads.reserve(kept.size());
+    qualities.reserve(kept.size());
+    for (size_t i : kept)
+    {
+        reads.push_back(std::move(all[i]));
+        qualities.push_back(std::move(all_qualities[i]));
+    }
+    return std::make_unique<FastaParserMem>(std::move(reads), std::move(qualities));
+}
+
+std::unique_ptr<FastaParser> create_fasta_parser_from_sequences(std::vector<FastaSequence> records,
+                                                                std::vector<std::string> qualities)
+{
+    if (qualities.size() != records.size())
+        throw std::invalid_argument("one quality string per record expected");
+    return std::make_unique<FastaParserMem>(std::move(records), std::move(qualities));
 }
 
 std::unique_ptr<FastaParser> create_fasta_parser_from_sequences(std::vector<FastaSequence> records)

@@ -16,12 +16,14 @@
 // where they stick out of it, are written byte by byte, so nothing outside
 // [A, A + len) is ever written and neighbouring slots never meet.  The word
 // loads reach at most 3 bytes before and 4 bytes after the region, which
-// DeviceReads pads for (kReadsPad).
+// DeviceReads pads for (kReadsPad).  The chunk helpers are shared with the POA
+// input gather (mapper_gather.hpp).
 //
 // One wave owns one piece of kPieceChunks chunks (4 KiB) of one sequence, a
 // lane one chunk per step, so a 50 kb region is spread over a dozen waves and
 // does not serialise a launch of 200-base ones.  A wave whose piece begins past
 // its sequence's end leaves at once.  No LDS, no barrier.
+#include "mapper_gather.hpp"
 #include "mapper_prims.hpp"
 #include "mapper_reads.hpp"
 
@@ -33,44 +35,7 @@ namespace
 {
 
 constexpr uint32_t kWaves       = kThreads / 64;
-constexpr uint32_t kChunk       = 16;
-constexpr uint32_t kPieceChunks = 256; // per wave: four steps of 64 lanes
 constexpr uint32_t kOverlapWords = sizeof(OverlapRecord) / sizeof(uint32_t);
-
-__device__ inline uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-
-__device__ inline uint8_t complement(uint8_t c)
-{
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
-}
-
-// 0xff in every byte of v that equals c
-__device__ inline uint32_t bytes_equal(uint32_t v, uint32_t c)
-{
-    const uint32_t x = v ^ (c * 0x01010101u);
-    // the high bit of a byte stays clear only when the byte is zero (no carry crosses a byte)
-    const uint32_t nonzero = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
-    return ((nonzero ^ 0x80808080u) >> 7) * 0xffu;
-}
-
-// complement() of the four bytes of v: 'A' ^ 'T' == 0x15, 'C' ^ 'G' == 0x04
-__device__ inline uint32_t complement4(uint32_t v)
-{
-    const uint32_t at = bytes_equal(v, 'A') | bytes_equal(v, 'T');
-    const uint32_t cg = bytes_equal(v, 'C') | bytes_equal(v, 'G');
-    return v ^ (at & 0x15151515u) ^ (cg & 0x04040404u);
-}
-
-// src[0, 16) for any src, from the five aligned words that hold it
-__device__ inline uint4 load16(const uint8_t* src)
-{
-    const uintptr_t address = reinterpret_cast<uintptr_t>(src);
-    const uint32_t* w       = reinterpret_cast<const uint32_t*>(address & ~uintptr_t(3));
-    const uint32_t shift    = uint32_t(address & 3);
-    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-    return uint4{__builtin_amdgcn_alignbyte(w1, w0, shift), __builtin_amdgcn_alignbyte(w2, w1, shift),
-                 __builtin_amdgcn_alignbyte(w3, w2, shift), __builtin_amdgcn_alignbyte(w4, w3, shift)};
-}
 
 __global__ __launch_bounds__(kThreads) void gather_overlap_regions_kernel(
     const uint8_t* __restrict__ query_bases, const int64_t* __restrict__ query_offsets,
@@ -114,9 +79,8 @@ __global__ __launch_bounds__(kThreads) void gather_overlap_regions_kernel(
             else
             {
                 // bytes j .. j + 15 of the reverse complement are source bytes len - 1 - j down to len - 16 - j
-                const uint4 s = load16(src + (len - kChunk - j));
-                v = uint4{complement4(__builtin_bswap32(s.w)), complement4(__builtin_bswap32(s.z)),
-                          complement4(__builtin_bswap32(s.y)), complement4(__builtin_bswap32(s.x))};
+                const uint4 s = reverse16(load16(src + (len - kChunk - j)));
+                v             = uint4{complement4(s.x), complement4(s.y), complement4(s.z), complement4(s.w)};
             }
             *reinterpret_cast<uint4*>(dst + j) = v;
         }

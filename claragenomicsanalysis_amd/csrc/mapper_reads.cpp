@@ -38,6 +38,19 @@ void check_read_set(const char* side, const ReadSet& reads)
         throw std::invalid_argument(std::string(side) + " bases is NULL");
 }
 
+void check_qualities(const ReadSet& reads, const char* qualities)
+{
+    if (reads.num_reads == 0)
+        return;
+    const int64_t first = reads.offsets[0], last = reads.offsets[reads.num_reads];
+    if (!qualities && last > first)
+        throw std::invalid_argument("qualities is NULL");
+    for (int64_t i = first; i < last; i++)
+        if (qualities[i] < 33 || qualities[i] > 126)
+            throw std::invalid_argument("quality character " + std::to_string(int(uint8_t(qualities[i]))) +
+                                        " at base " + std::to_string(i - first) + " is outside 33..126");
+}
+
 void check_overlap_count(const void* overlaps, int64_t n)
 {
     if (n < 0 || n >= (int64_t(1) << 31))
@@ -94,8 +107,41 @@ PackedReads::PackedReads(const claraparabricks::genomeworks::io::FastaParser& pa
         bases += parser.get_sequence_by_id(first + i).seq;
 }
 
-std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, int device_id, const Budget& budget,
-                                               hipStream_t stream)
+void PackedReads::pack_qualities(const claraparabricks::genomeworks::io::FastaParser& parser)
+{
+    const uint32_t n = uint32_t(offsets.size() - 1);
+    qualities.clear();
+    qualities.reserve(bases.size());
+    for (uint32_t i = 0; i < n; i++)
+    {
+        const std::string& q = parser.get_quality_by_id(i);
+        if (int64_t(q.size()) != offsets[i + 1] - offsets[i])
+            throw std::invalid_argument("read " + std::to_string(i) + " has " + std::to_string(q.size()) +
+                                        " quality characters for " + std::to_string(offsets[i + 1] - offsets[i]) +
+                                        " bases");
+        qualities += q;
+    }
+}
+
+namespace
+{
+
+// kReadsPad zero bytes, `total` bytes of src, zeros up to a multiple of 16, kReadsPad zero bytes
+void upload_padded(DevBuf<uint8_t>& storage, const char* src, size_t total, const Budget& budget, hipStream_t stream)
+{
+    const size_t padded = (total + 15) / 16 * 16;
+    // padded at both ends: the gather kernels read whole aligned words (kReadsPad)
+    storage.alloc(kReadsPad + padded + kReadsPad, budget);
+    GWAMD_HIP_CHECK(hipMemsetAsync(storage.data(), 0, kReadsPad, stream));
+    GWAMD_HIP_CHECK(hipMemsetAsync(storage.data() + kReadsPad + total, 0, padded - total + kReadsPad, stream));
+    if (total > 0)
+        GWAMD_HIP_CHECK(hipMemcpyAsync(storage.data() + kReadsPad, src, total, hipMemcpyHostToDevice, stream));
+}
+
+} // namespace
+
+std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, const char* qualities, int device_id,
+                                               const Budget& budget, hipStream_t stream)
 {
     auto d       = std::make_unique<DeviceReads>();
     d->device_id = device_id;
@@ -106,16 +152,14 @@ std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, int device_
     const int64_t first = d->offsets.front();
     for (int64_t& o : d->offsets)
         o -= first;
-    const size_t total  = size_t(d->offsets.back());
-    const size_t padded = (total + 15) / 16 * 16;
-    // padded at both ends: the gather kernel reads whole aligned words (kReadsPad)
-    d->storage.alloc(kReadsPad + padded + kReadsPad, budget);
+    const size_t total = size_t(d->offsets.back());
+    upload_padded(d->storage, reads.bases + first, total, budget, stream);
+    if (qualities)
+    {
+        upload_padded(d->qual_storage, qualities + first, total, budget, stream);
+        d->has_qualities = true;
+    }
     d->d_offsets.alloc(d->offsets.size(), budget);
-    GWAMD_HIP_CHECK(hipMemsetAsync(d->storage.data(), 0, kReadsPad, stream));
-    GWAMD_HIP_CHECK(hipMemsetAsync(d->storage.data() + kReadsPad + total, 0, padded - total + kReadsPad, stream));
-    if (total > 0)
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d->storage.data() + kReadsPad, reads.bases + first, total,
-                                       hipMemcpyHostToDevice, stream));
     GWAMD_HIP_CHECK(hipMemcpyAsync(d->d_offsets.data(), d->offsets.data(), d->offsets.size() * sizeof(int64_t),
                                    hipMemcpyHostToDevice, stream));
     GWAMD_HIP_CHECK(hipStreamSynchronize(stream)); // the caller's arrays may go
@@ -165,6 +209,23 @@ std::unique_ptr<DeviceReads> DeviceReads::create(DefaultDeviceAllocator allocato
     return out;
 }
 
+std::unique_ptr<DeviceReads> DeviceReads::create(DefaultDeviceAllocator allocator, const io::FastaParser& parser,
+                                                 with_qualities_t, hipStream_t stream)
+{
+    gm::PackedReads packed(parser);
+    packed.pack_qualities(parser);
+    const gm::ReadSet reads = packed.view();
+    gm::check_read_set("parser", reads);
+    gm::check_qualities(reads, packed.qualities.data());
+    int device_id = 0;
+    GWAMD_HIP_CHECK(hipGetDevice(&device_id));
+    std::unique_ptr<DeviceReads> out(new DeviceReads());
+    out->impl_        = std::make_unique<Impl>();
+    out->impl_->reads = gm::make_device_reads(reads, packed.qualities.data(), device_id, allocator.budget(), stream);
+    return out;
+}
+
+bool DeviceReads::has_qualities() const { return impl_->reads->has_qualities; }
 number_of_reads_t DeviceReads::number_of_reads() const { return number_of_reads_t(impl_->reads->num_reads()); }
 std::int64_t DeviceReads::number_of_basepairs() const { return impl_->reads->num_bases(); }
 std::int32_t DeviceReads::device_id() const { return impl_->reads->device_id; }
@@ -185,10 +246,12 @@ void Overlapper::rescue_overlap_ends(std::vector<Overlap>& overlaps, const Devic
 
 // ---- C ABI ------------------------------------------------------------------
 
-extern "C" {
+namespace
+{
 
-int32_t gwamd_device_reads_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t device_id,
-                                  gwamd_device_allocator* allocator_or_null, gwamd_device_reads** out)
+int32_t create_device_reads(const char* bases, const char* qualities, bool with_qualities, const int64_t* offsets,
+                            int32_t num_reads, int32_t device_id, gwamd_device_allocator* allocator_or_null,
+                            gwamd_device_reads** out)
 {
     if (out)
         *out = nullptr;
@@ -199,12 +262,45 @@ int32_t gwamd_device_reads_create(const char* bases, const int64_t* offsets, int
             throw std::invalid_argument("device_id must not be negative");
         const gm::ReadSet reads{bases, offsets, num_reads};
         gm::check_read_set("device", reads);
+        static const char none = 0; // a set without a base has no quality to point at
+        if (with_qualities)
+        {
+            gm::check_qualities(reads, qualities);
+            if (!qualities)
+                qualities = &none;
+        }
         gwamd::host::ScopedDevice dev(device_id);
         auto h   = std::make_unique<gwamd_device_reads>();
-        h->reads = gm::make_device_reads(reads, device_id,
+        h->reads = gm::make_device_reads(reads, with_qualities ? qualities : nullptr, device_id,
                                          allocator_or_null ? allocator_or_null->alloc.budget() : nullptr, nullptr);
         *out     = h.release();
         return int32_t(0);
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t gwamd_device_reads_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t device_id,
+                                  gwamd_device_allocator* allocator_or_null, gwamd_device_reads** out)
+{
+    return create_device_reads(bases, nullptr, false, offsets, num_reads, device_id, allocator_or_null, out);
+}
+
+int32_t gwamd_device_reads_create_with_qualities(const char* bases, const char* qualities, const int64_t* offsets,
+                                                 int32_t num_reads, int32_t device_id,
+                                                 gwamd_device_allocator* allocator_or_null, gwamd_device_reads** out)
+{
+    return create_device_reads(bases, qualities, true, offsets, num_reads, device_id, allocator_or_null, out);
+}
+
+int32_t gwamd_device_reads_has_qualities(const gwamd_device_reads* reads)
+{
+    return gm::guarded_map([&] {
+        if (!reads)
+            throw std::invalid_argument("reads is NULL");
+        return int32_t(reads->reads->has_qualities ? 1 : 0);
     });
 }
 

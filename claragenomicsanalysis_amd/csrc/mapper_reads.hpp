@@ -20,32 +20,49 @@ namespace mapper
 {
 
 // Bytes allocated, and zeroed, before the first base and after the last one.
-// gather_overlap_regions_kernel reads the bases as aligned 32-bit words, five
-// per 16 bytes it writes: a word may begin up to 3 bytes before a region and
-// end up to 4 bytes after it, so both ends of the buffer are padded.
+// gather_overlap_regions_kernel and gather_poa_slices_kernel read the bases
+// (the latter the qualities too) as aligned 32-bit words, five per 16 bytes
+// they write: a word may begin up to 3 bytes before a region and end up to 4
+// bytes after it, so both ends of each buffer are padded.
 constexpr size_t kReadsPad = 16;
 
 struct DeviceReads
 {
     DevBuf<uint8_t> storage;      // kReadsPad, the bases, up to 15 bytes to a multiple of 16, kReadsPad
+    DevBuf<uint8_t> qual_storage; // the quality characters in the same layout, when the set has them
     DevBuf<int64_t> d_offsets;    // num_reads + 1
     std::vector<int64_t> offsets; // the host's copy: lengths are checked without a device call
-    int device_id = 0;
+    int device_id      = 0;
+    bool has_qualities = false;
 
     const uint8_t* bases() const { return storage.data() + kReadsPad; }
+    // quality character of base i at qualities()[i]; null for a set without qualities
+    const uint8_t* qualities() const { return has_qualities ? qual_storage.data() + kReadsPad : nullptr; }
     int64_t num_reads() const { return int64_t(offsets.size()) - 1; }
     int64_t num_bases() const { return offsets.back(); }
     int64_t read_length(uint32_t id) const { return offsets[size_t(id) + 1] - offsets[id]; }
 };
 
-// The reads on the current device, which is device_id.  The arguments are
-// validated by the caller (check_read_set).
-std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, int device_id, const Budget& budget,
-                                               hipStream_t stream);
+// The reads on the current device, which is device_id, with their quality
+// characters (one per base, at the base's own offset) unless qualities is
+// null.  The arguments are validated by the caller (check_read_set,
+// check_qualities).
+std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, const char* qualities, int device_id,
+                                               const Budget& budget, hipStream_t stream);
+inline std::unique_ptr<DeviceReads> make_device_reads(const ReadSet& reads, int device_id, const Budget& budget,
+                                                      hipStream_t stream)
+{
+    return make_device_reads(reads, nullptr, device_id, budget, stream);
+}
 
 // Throws std::invalid_argument for a negative count, a NULL array with
 // something to read, offsets that fall and a read of 2^31 bases or more.
 void check_read_set(const char* side, const ReadSet& reads);
+
+// Throws std::invalid_argument unless every quality character of the checked
+// reads, qualities[offsets[0], offsets[num_reads]), is a printable 33..126
+// (Phred + 33), and for NULL qualities with a base to describe.
+void check_qualities(const ReadSet& reads, const char* qualities);
 
 // Throws std::invalid_argument for a count outside [0, 2^31) and for NULL overlaps with n > 0.
 void check_overlap_count(const void* overlaps, int64_t n);
@@ -74,9 +91,13 @@ struct PackedReads
 {
     std::string bases;
     std::vector<int64_t> offsets;
+    std::string qualities; // filled by pack_qualities
     explicit PackedReads(const claraparabricks::genomeworks::io::FastaParser& parser);
     PackedReads(const claraparabricks::genomeworks::io::FastaParser& parser, uint32_t first, uint32_t past_the_last);
     ReadSet view() const { return {bases.data(), offsets.data(), int64_t(offsets.size()) - 1}; }
+    // The parser's quality strings packed like the bases.  Throws std::invalid_argument
+    // for a record whose quality string has not its sequence's length.
+    void pack_qualities(const claraparabricks::genomeworks::io::FastaParser& parser);
 };
 
 // rescue_overlap_ends on reads that are resident: only the overlaps travel.

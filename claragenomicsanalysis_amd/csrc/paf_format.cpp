@@ -128,26 +128,53 @@ int32_t gwamd_format_paf(const char* query_names, const int64_t* query_name_offs
     });
 }
 
-int32_t gwamd_read_fasta(const char* path, uint32_t min_sequence_length, int32_t shuffle, gwamd_text_list** names,
-                         gwamd_text_list** sequences)
+namespace
 {
-    *names     = nullptr;
-    *sequences = nullptr;
+
+// qualities: null for gwamd_read_fasta
+int32_t read_fasta(const char* path, uint32_t min_sequence_length, int32_t shuffle, gwamd_text_list** names,
+                   gwamd_text_list** sequences, gwamd_text_list** qualities)
+{
     return gm::guarded_map([&] {
         namespace io = claraparabricks::genomeworks::io;
         auto parser  = io::create_kseq_fasta_parser(path ? path : "", min_sequence_length, shuffle != 0);
         auto nl      = std::make_unique<gwamd_text_list>();
         auto sl      = std::make_unique<gwamd_text_list>();
+        auto ql      = std::make_unique<gwamd_text_list>();
         for (uint32_t i = 0; i < parser->get_num_seqences(); i++)
         {
             const auto& r = parser->get_sequence_by_id(i);
             nl->items.push_back(r.name);
             sl->items.push_back(r.seq);
+            if (qualities)
+                ql->items.push_back(parser->get_quality_by_id(i));
         }
         *names     = nl.release();
         *sequences = sl.release();
+        if (qualities)
+            *qualities = ql.release();
         return 0;
     });
+}
+
+} // namespace
+
+int32_t gwamd_read_fasta(const char* path, uint32_t min_sequence_length, int32_t shuffle, gwamd_text_list** names,
+                         gwamd_text_list** sequences)
+{
+    *names     = nullptr;
+    *sequences = nullptr;
+    return read_fasta(path, min_sequence_length, shuffle, names, sequences, nullptr);
+}
+
+int32_t gwamd_read_fasta_with_qualities(const char* path, uint32_t min_sequence_length, int32_t shuffle,
+                                        gwamd_text_list** names, gwamd_text_list** sequences,
+                                        gwamd_text_list** qualities)
+{
+    if (!names || !sequences || !qualities)
+        return gm::guarded_map([]() -> int32_t { throw std::invalid_argument("an output list is NULL"); });
+    *names = *sequences = *qualities = nullptr;
+    return read_fasta(path, min_sequence_length, shuffle, names, sequences, qualities);
 }
 
 int32_t gwamd_text_list_create(const char* const* texts, const int64_t* lengths, int32_t n, gwamd_text_list** out)

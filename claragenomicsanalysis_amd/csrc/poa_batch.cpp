@@ -10,10 +10,14 @@
 // (poa_kernels.hip), not the reference's slab.
 #include <claraparabricks/genomeworks/cudapoa/batch.hpp>
 #include <claraparabricks/genomeworks/cudapoa/utils.hpp>
+#include <claraparabricks/genomeworks/cudapolish/windows.hpp>
 
 #include "gwamd_cudapoa.h"
+#include "gwamd_polish.h"
 #include "host_common.hpp"
+#include "mapper_reads.hpp"
 #include "poa_batch_internal.hpp"
+#include "polish_gather.hpp"
 #include "poa_common.hpp"
 #include "poa_plan.hpp"
 
@@ -175,6 +179,45 @@ public:
         return StatusType::success;
     }
 
+    // add_poa_group for sequences that are slices of reads resident on this
+    // batch's device (gwamd_poa_add_poa_group_resident): the same bookkeeping
+    // without the bytes, which upload() has the device write.  The slices are
+    // checked by the caller; the read sets outlive the batch's use of them.
+    StatusType add_poa_group_resident(std::vector<StatusType>& per_seq_status,
+                                      const gwamd::mapper::DeviceReads* const* sets, const gwamd_read_slice* slices,
+                                      int32_t n)
+    {
+        int32_t max_len = 0;
+        for (int32_t i = 0; i < n; i++)
+            max_len = std::max(max_len, int32_t(slices[i].end - slices[i].begin));
+        if (!reserve_buf(max_len))
+            return StatusType::exceeded_maximum_poas;
+        per_seq_status.clear();
+        StatusType st = add_poa();
+        if (st != StatusType::success)
+            return st;
+        for (int32_t i = 0; i < n; i++)
+        {
+            const gwamd_read_slice& sl = slices[i];
+            const int32_t len          = int32_t(sl.end - sl.begin);
+            st                         = seq_status(len);
+            per_seq_status.push_back(st);
+            if (st != StatusType::success)
+                continue;
+            const gwamd::mapper::DeviceReads& set = *sets[sl.set];
+            const int64_t at                      = set.offsets[sl.read] + int64_t(sl.begin);
+            resident_.push_back(ResidentSeq{num_seqs_, sl.set, sl.read, sl.begin, sl.end, sl.flags});
+            h_jobs_.reserve(resident_.size() * sizeof(gwamd::polish::SliceJob), stream_);
+            h_jobs_.as<gwamd::polish::SliceJob>()[resident_.size() - 1] =
+                gwamd::polish::SliceJob{set.bases() + at, set.has_qualities ? set.qualities() + at : nullptr,
+                                        int64_t(num_bases_), uint32_t(len), sl.flags & 1u};
+            h_jobs_.used_     = resident_.size() * sizeof(gwamd::polish::SliceJob);
+            resident_max_len_ = std::max(resident_max_len_, len);
+            book_seq(len);
+        }
+        return StatusType::success;
+    }
+
     int32_t get_total_poas() const override { return poa_count_; }
 
     void generate_poa() override
@@ -189,8 +232,15 @@ public:
     {
         ScopedDevice dev(device_id_);
         const size_t nb = num_bases_;
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.data(), h_seqs_.as<uint8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_wts_.data(), h_wts_.as<int8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
+        if (resident_.empty())
+        {
+            GWAMD_HIP_CHECK(
+                hipMemcpyAsync(d_seqs_.data(), h_seqs_.as<uint8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
+            GWAMD_HIP_CHECK(
+                hipMemcpyAsync(d_wts_.data(), h_wts_.as<int8_t>(), nb + 16, hipMemcpyHostToDevice, stream_));
+        }
+        else
+            upload_mixed_inputs();
         GWAMD_HIP_CHECK(hipMemcpyAsync(d_len_.data(), h_len_.as<int32_t>(), size_t(num_seqs_) * 4,
                                        hipMemcpyHostToDevice, stream_));
         GWAMD_HIP_CHECK(hipMemcpyAsync(d_off_.data(), h_off_.as<int64_t>(), size_t(num_seqs_) * 8,
@@ -216,6 +266,18 @@ public:
         if (kind == gwamd::poa::kOrderAndHead)
             bufs_.head = reinterpret_cast<int32_t*>(d_win_.data() + lay_.head_off);
     }
+
+    // Test hook (gwamd_internal_poa_download_inputs): the packed bases and
+    // weights as upload() left them on the device, num_bases + 16 bytes each
+    size_t input_bytes() const { return num_bases_ + 16; }
+    void download_inputs(uint8_t* seqs_out, int8_t* wts_out)
+    {
+        ScopedDevice dev(device_id_);
+        GWAMD_HIP_CHECK(hipMemcpyAsync(seqs_out, d_seqs_.data(), input_bytes(), hipMemcpyDeviceToHost, stream_));
+        GWAMD_HIP_CHECK(hipMemcpyAsync(wts_out, d_wts_.data(), input_bytes(), hipMemcpyDeviceToHost, stream_));
+        GWAMD_HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    int32_t device_id() const { return device_id_; }
 
     void launch()
     {
@@ -421,6 +483,10 @@ public:
         next_scores_offset_ = 0;
         avail_scorebuf_     = cap_.scorebuf_alloc;
         generated_          = false;
+        resident_.clear();
+        host_runs_.clear();
+        resident_max_len_ = 0;
+        h_jobs_.used_     = 0;
     }
 
     // --- C ABI support ------------------------------------------------------
@@ -554,18 +620,40 @@ private:
         return StatusType::success;
     }
 
-    // cudapoa_batch.cuh:490-539
-    StatusType add_seq_to_poa(const char* seq, const int8_t* weights, int32_t seq_len)
+    // The checks of add_seq_to_poa (cudapoa_batch.cuh:490-503) on the window being filled
+    StatusType seq_status(int32_t seq_len) const
     {
         if (seq_len > bs_.max_sequence_size)
             return StatusType::exceeded_maximum_sequence_size;
-        gwamd::poa::WindowDesc& wd = h_win_.as<gwamd::poa::WindowDesc>()[poa_count_ - 1];
-        if (wd.num_seqs >= bs_.max_sequences_per_poa)
+        if (h_win_.as<gwamd::poa::WindowDesc>()[poa_count_ - 1].num_seqs >= bs_.max_sequences_per_poa)
             return StatusType::exceeded_maximum_sequences_per_poa;
+        return StatusType::success;
+    }
+
+    // ... and its counters (cudapoa_batch.cuh:505-539): the sequence takes
+    // [num_bases_, num_bases_ + seq_len) of the packed arrays, wherever its bytes come from
+    void book_seq(int32_t seq_len)
+    {
+        h_win_.as<gwamd::poa::WindowDesc>()[poa_count_ - 1].num_seqs++;
+        h_len_.reserve(size_t(num_seqs_ + 1) * 4, stream_);
+        h_off_.reserve(size_t(num_seqs_ + 1) * 8, stream_);
+        h_len_.as<int32_t>()[num_seqs_] = seq_len;
+        h_off_.as<int64_t>()[num_seqs_] = int64_t(num_bases_);
+        num_bases_ += size_t(seq_len);
+        num_seqs_++;
+        h_len_.used_ = size_t(num_seqs_) * 4;
+        h_off_.used_ = size_t(num_seqs_) * 8;
+    }
+
+    // cudapoa_batch.cuh:490-539
+    StatusType add_seq_to_poa(const char* seq, const int8_t* weights, int32_t seq_len)
+    {
+        const StatusType st = seq_status(seq_len);
+        if (st != StatusType::success)
+            return st;
         if (weights != nullptr)
             for (int32_t i = 0; i < seq_len; i++)
                 detail::check_non_negative(weights[i], "Base weights need to be non-negative");
-        wd.num_seqs++;
         const size_t need = num_bases_ + size_t(seq_len) + 16;
         h_seqs_.reserve(need, stream_);
         h_wts_.reserve(need, stream_);
@@ -577,17 +665,54 @@ private:
             std::memcpy(h_wts_.as<int8_t>() + num_bases_, weights, size_t(seq_len));
         std::memset(h_seqs_.as<uint8_t>() + num_bases_ + seq_len, 0, 16);
         std::memset(h_wts_.as<int8_t>() + num_bases_ + seq_len, 0, 16);
-        h_len_.reserve(size_t(num_seqs_ + 1) * 4, stream_);
-        h_off_.reserve(size_t(num_seqs_ + 1) * 8, stream_);
-        h_len_.as<int32_t>()[num_seqs_] = seq_len;
-        h_off_.as<int64_t>()[num_seqs_] = int64_t(num_bases_);
-        num_bases_ += size_t(seq_len);
+        // the bytes the host holds, as runs: what upload() copies when the batch has resident sequences too
+        if (!host_runs_.empty() && host_runs_.back().second == num_bases_)
+            host_runs_.back().second += size_t(seq_len);
+        else if (seq_len > 0)
+            host_runs_.emplace_back(num_bases_, num_bases_ + size_t(seq_len));
+        book_seq(seq_len);
         h_seqs_.used_ = h_wts_.used_ = num_bases_ + 16;
-        num_seqs_++;
-        h_len_.used_ = size_t(num_seqs_) * 4;
-        h_off_.used_ = size_t(num_seqs_) * 8;
         return StatusType::success;
     }
+
+    // upload() of the packed bases and weights of a batch with resident
+    // sequences.  Every byte of [0, num_bases_) has one writer: the copy of
+    // the host run it lies in, or the kernel for the resident sequence it
+    // belongs to, which writes no byte outside its sequence
+    // (polish_gather.hip); the 16 zero bytes after the last base are set here.
+    // All on the batch's stream, so the POA kernels see them done.
+    void upload_mixed_inputs()
+    {
+        const size_t nb = num_bases_;
+        for (const auto& run : host_runs_)
+        {
+            const size_t bytes = run.second - run.first;
+            GWAMD_HIP_CHECK(hipMemcpyAsync(d_seqs_.data() + run.first, h_seqs_.as<uint8_t>() + run.first, bytes,
+                                           hipMemcpyHostToDevice, stream_));
+            GWAMD_HIP_CHECK(hipMemcpyAsync(d_wts_.data() + run.first, h_wts_.as<int8_t>() + run.first, bytes,
+                                           hipMemcpyHostToDevice, stream_));
+        }
+        GWAMD_HIP_CHECK(hipMemsetAsync(d_seqs_.data() + nb, 0, 16, stream_));
+        GWAMD_HIP_CHECK(hipMemsetAsync(d_wts_.data() + nb, 0, 16, stream_));
+        const size_t jobs_b = resident_.size() * sizeof(gwamd::polish::SliceJob);
+        if (d_jobs_.size() < jobs_b)
+        {
+            GWAMD_HIP_CHECK(hipStreamSynchronize(stream_)); // an earlier launch may still read the old array
+            d_jobs_.alloc(std::max(jobs_b, 2 * d_jobs_.size()), gwamd::host::Budget());
+        }
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_jobs_.data(), h_jobs_.as<uint8_t>(), jobs_b, hipMemcpyHostToDevice, stream_));
+        gwamd::polish::gather_poa_slices(d_seqs_.data(), reinterpret_cast<int8_t*>(d_wts_.data()),
+                                         reinterpret_cast<const gwamd::polish::SliceJob*>(d_jobs_.data()),
+                                         int64_t(resident_.size()), resident_max_len_, stream_);
+    }
+
+    // A sequence added as a slice of a resident read (add_poa_group_resident)
+    struct ResidentSeq
+    {
+        int32_t sequence; // its index in the batch
+        int32_t set;
+        uint32_t read, begin, end, flags;
+    };
 
     int32_t device_id_;
     hipStream_t stream_;
@@ -613,6 +738,11 @@ private:
     gwamd::poa::Buffers bufs_{};
     gwamd::host::DevBuf<uint8_t> d_seqs_, d_wts_, d_len_, d_off_, d_win_, d_slab_, d_codes_;
     PinnedBuf h_seqs_, h_wts_, h_len_, h_off_, h_win_;
+    std::vector<ResidentSeq> resident_;                   // in sequence order
+    std::vector<std::pair<size_t, size_t>> host_runs_;    // [first, last) of the packed bytes the host holds
+    int32_t resident_max_len_ = 0;
+    PinnedBuf h_jobs_;                                    // one SliceJob per resident sequence, staged for the copy
+    gwamd::host::DevBuf<uint8_t> d_jobs_;
     std::vector<uint8_t> h_cons_, h_status_, h_msa_, h_msa_status_, h_g_bases_, h_g_in_e_raw_;
     std::vector<uint16_t> h_cov_, h_g_in_cnt_, h_g_in_w_;
     std::vector<int32_t> h_len_out_, h_msa_len_, h_g_in_e_, h_final_nodes_;
@@ -759,6 +889,75 @@ int32_t max_sequence_size(const Batch* batch) { return static_cast<const PoaBatc
 } // namespace genomeworks
 } // namespace claraparabricks
 
+// ---------------------------------------------------------------------------
+// Groups as slices of resident reads: the one check of the slices, on the
+// handles' host copies of the offsets and before any device call, behind the
+// C entry (gwamd_poa_add_poa_group_resident) and the C++ free function
+// (cudapolish::add_poa_group_resident, windows.hpp)
+// ---------------------------------------------------------------------------
+namespace
+{
+
+claraparabricks::genomeworks::cudapoa::StatusType
+add_resident_checked(claraparabricks::genomeworks::cudapoa::PoaBatch& batch,
+                     std::vector<claraparabricks::genomeworks::cudapoa::StatusType>& per_seq_status,
+                     const std::vector<const gwamd::mapper::DeviceReads*>& sets, const gwamd_read_slice* slices,
+                     int32_t n)
+{
+    if (n < 0)
+        throw std::invalid_argument("the number of slices must not be negative");
+    if (n > 0 && !slices)
+        throw std::invalid_argument("slices is NULL");
+    for (size_t s = 0; s < sets.size(); s++)
+        if (!sets[s])
+            throw std::invalid_argument("set " + std::to_string(s) + " is NULL");
+    for (int32_t i = 0; i < n; i++)
+    {
+        const gwamd_read_slice& sl = slices[i];
+        const std::string which    = "slice " + std::to_string(i);
+        if (sl.set < 0 || size_t(sl.set) >= sets.size())
+            throw std::invalid_argument(which + ": set index outside the sets");
+        const gwamd::mapper::DeviceReads& set = *sets[size_t(sl.set)];
+        if (int64_t(sl.read) >= set.num_reads())
+            throw std::invalid_argument(which + ": read id beyond the reads");
+        if (sl.begin > sl.end || int64_t(sl.end) > set.read_length(sl.read))
+            throw std::invalid_argument(which + ": positions are not begin <= end <= read length");
+        if (set.device_id != batch.device_id())
+            throw std::invalid_argument(which + ": its reads are on device " + std::to_string(set.device_id) +
+                                        ", the batch is on device " + std::to_string(batch.device_id()));
+    }
+    return batch.add_poa_group_resident(per_seq_status, sets.data(), slices, n);
+}
+
+} // namespace
+
+namespace claraparabricks
+{
+namespace genomeworks
+{
+namespace cudapolish
+{
+
+static_assert(sizeof(ReadSlice) == sizeof(gwamd_read_slice), "ReadSlice is gwamd_read_slice");
+
+cudapoa::StatusType add_poa_group_resident(cudapoa::Batch& batch, std::vector<cudapoa::StatusType>& per_seq_status,
+                                           const std::vector<const cudamapper::DeviceReads*>& sets,
+                                           const std::vector<ReadSlice>& slices)
+{
+    auto* own = dynamic_cast<cudapoa::PoaBatch*>(&batch);
+    if (!own)
+        throw std::invalid_argument("add_poa_group_resident: the batch does not come from cudapoa::create_batch");
+    std::vector<const gwamd::mapper::DeviceReads*> reads(sets.size());
+    for (size_t s = 0; s < sets.size(); s++)
+        reads[s] = sets[s] ? sets[s]->impl().reads.get() : nullptr;
+    return add_resident_checked(*own, per_seq_status, reads,
+                                reinterpret_cast<const gwamd_read_slice*>(slices.data()), int32_t(slices.size()));
+}
+
+} // namespace cudapolish
+} // namespace genomeworks
+} // namespace claraparabricks
+
 // ===========================================================================
 // C ABI (include/gwamd_cudapoa.h)
 // ===========================================================================
@@ -890,6 +1089,43 @@ int32_t gwamd_poa_add_poa_group(gwamd_poa_batch* batch, const char* const* seqs,
         for (size_t i = st.size(); i < size_t(n); i++)
             per_seq_status[i] = int32_t(rc);
         return int32_t(rc);
+    });
+}
+
+int32_t gwamd_poa_add_poa_group_resident(gwamd_poa_batch* batch, const gwamd_device_reads* const* sets,
+                                         int32_t num_sets, const gwamd_read_slice* slices, int32_t n,
+                                         int32_t* per_seq_status)
+{
+    return guarded([&] {
+        if (!batch)
+            throw std::invalid_argument("batch is NULL");
+        if (num_sets < 0)
+            throw std::invalid_argument("num_sets must not be negative");
+        if (num_sets > 0 && !sets)
+            throw std::invalid_argument("sets is NULL");
+        if (n > 0 && !per_seq_status)
+            throw std::invalid_argument("per_seq_status is NULL");
+        std::vector<const gwamd::mapper::DeviceReads*> reads(static_cast<size_t>(num_sets));
+        for (int32_t s = 0; s < num_sets; s++)
+            reads[size_t(s)] = sets[s] ? sets[s]->reads.get() : nullptr;
+        std::vector<cp::StatusType> st;
+        const cp::StatusType rc = add_resident_checked(*batch->impl, st, reads, slices, n);
+        for (size_t i = 0; i < st.size(); i++)
+            per_seq_status[i] = int32_t(st[i]);
+        for (size_t i = st.size(); i < size_t(n); i++)
+            per_seq_status[i] = int32_t(rc);
+        return int32_t(rc);
+    });
+}
+
+int32_t gwamd_internal_poa_download_inputs(gwamd_poa_batch* batch, uint8_t* seqs_out, int8_t* wts_out)
+{
+    return guarded([&] {
+        if (!batch || !seqs_out != !wts_out)
+            throw std::invalid_argument("batch is NULL, or one of seqs_out and wts_out");
+        if (seqs_out) // both NULL: the count alone
+            batch->impl->download_inputs(seqs_out, wts_out);
+        return int32_t(batch->impl->input_bytes());
     });
 }
 

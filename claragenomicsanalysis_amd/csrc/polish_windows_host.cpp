@@ -37,14 +37,21 @@ static_assert(sizeof(gw::cudapolish::WindowSegment) == sizeof(gwamd_window_segme
               "a record is eight 32-bit words");
 static_assert(sizeof(gw::cudaaligner::AlignmentState) == 1, "states are bytes");
 
+struct gwamd_window_slices
+{
+    std::vector<gwamd_read_slice> slices;
+    std::vector<int32_t> window_counts;
+    std::vector<uint32_t> window_target, window_index;
+    std::vector<int32_t> sequence_overlap, sequence_t_begin, sequence_t_end;
+    int64_t dropped_by_cap = 0, dropped_by_quality = 0;
+};
+
+// the slices with their bases copied out of the host's reads
 struct gwamd_windows
 {
     std::vector<char> bases;
     std::vector<int64_t> sequence_offsets{0};
-    std::vector<int32_t> window_counts;
-    std::vector<uint32_t> window_target, window_index;
-    std::vector<int32_t> sequence_overlap, sequence_t_begin, sequence_t_end;
-    int64_t dropped_by_cap = 0;
+    gwamd_window_slices grouped;
 };
 
 namespace gwamd
@@ -355,10 +362,14 @@ namespace
 
 char complement(char c) { return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c; }
 
-std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const gm::ReadSet& queries,
-                                             const std::vector<gm::OverlapRecord>& overlaps,
-                                             const gwamd_window_segment* segments, int64_t num_segments,
-                                             int32_t window_length, int32_t max_sequences_per_window)
+// The grouping: which slices of the targets (set 0) and queries (set 1) make
+// up which window.  Only offsets are looked at, and the queries' quality
+// characters when they are given (racon's mean-quality rule, gwamd_polish.h).
+std::unique_ptr<gwamd_window_slices> group_slices(const gm::ReadSet& targets, const gm::ReadSet& queries,
+                                                  const char* query_qualities, int32_t quality_threshold_tenths,
+                                                  const std::vector<gm::OverlapRecord>& overlaps,
+                                                  const gwamd_window_segment* segments, int64_t num_segments,
+                                                  int32_t window_length, int32_t max_sequences_per_window)
 {
     if (window_length <= 0)
         throw std::invalid_argument("window_length must be positive, got " + std::to_string(window_length));
@@ -366,6 +377,8 @@ std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const g
         throw std::invalid_argument("max_sequences_per_window must be at least 1");
     if (num_segments < 0 || (num_segments > 0 && !segments))
         throw std::invalid_argument("segments: bad count or NULL");
+    if (query_qualities && quality_threshold_tenths < 0)
+        throw std::invalid_argument("quality_threshold_tenths must not be negative");
     const int64_t w = window_length;
     // the windows of every target, and the kept segments of each in the order given
     std::vector<int64_t> first(size_t(targets.num_reads) + 1, 0);
@@ -373,7 +386,7 @@ std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const g
         first[size_t(r) + 1] = first[size_t(r)] + (targets.offsets[r + 1] - targets.offsets[r] + w - 1) / w;
     const int64_t num_windows = first[size_t(targets.num_reads)];
     std::vector<std::vector<int64_t>> kept(static_cast<size_t>(num_windows));
-    auto out = std::make_unique<gwamd_windows>();
+    auto out = std::make_unique<gwamd_window_slices>();
     for (int64_t s = 0; s < num_segments; s++)
     {
         const gwamd_window_segment& seg = segments[s];
@@ -392,18 +405,28 @@ std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const g
             throw std::invalid_argument(which + ": query range outside its read");
         if ((int64_t(seg.q_end) - int64_t(seg.q_begin)) * 50 < w)
             continue;
+        if (query_qualities)
+        {
+            const char* q = query_qualities + queries.offsets[o.query_read_id];
+            int64_t sum   = 0;
+            for (uint32_t j = seg.q_begin; j < seg.q_end; j++)
+                sum += int64_t(uint8_t(q[j])) - 33;
+            if (sum * 10 < int64_t(quality_threshold_tenths) * (int64_t(seg.q_end) - int64_t(seg.q_begin)))
+            {
+                out->dropped_by_quality++;
+                continue;
+            }
+        }
         std::vector<int64_t>& list = kept[size_t(first[o.target_read_id] + seg.window)];
         if (int64_t(list.size()) >= int64_t(max_sequences_per_window) - 1)
             out->dropped_by_cap++;
         else
             list.push_back(s);
     }
-    auto add = [&](const char* src, int64_t len, bool reverse, int32_t overlap, int32_t t_begin, int32_t t_end) {
-        const size_t at = out->bases.size();
-        out->bases.resize(at + size_t(len));
-        for (int64_t j = 0; j < len; j++)
-            out->bases[at + size_t(j)] = reverse ? complement(src[len - 1 - j]) : src[j];
-        out->sequence_offsets.push_back(int64_t(out->bases.size()));
+    auto add = [&](int32_t set, uint32_t read, int64_t begin, int64_t end, bool reverse, int32_t overlap,
+                   int32_t t_begin, int32_t t_end) {
+        out->slices.push_back(
+            gwamd_read_slice{set, read, uint32_t(begin), uint32_t(end), reverse ? GWAMD_SLICE_REVERSE : 0u});
         out->sequence_overlap.push_back(overlap);
         out->sequence_t_begin.push_back(t_begin);
         out->sequence_t_end.push_back(t_end);
@@ -414,20 +437,42 @@ std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const g
         for (int64_t k = 0; k < first[size_t(r) + 1] - first[size_t(r)]; k++)
         {
             const int64_t from = k * w, to = std::min((k + 1) * w, length);
-            add(targets.bases + targets.offsets[r] + from, to - from, false, -1, 0, int32_t(to - from));
+            add(0, uint32_t(r), from, to, false, -1, 0, int32_t(to - from));
             const std::vector<int64_t>& list = kept[size_t(first[size_t(r)] + k)];
             for (int64_t s : list)
             {
                 const gwamd_window_segment& seg = segments[s];
                 const gm::OverlapRecord& o      = overlaps[seg.overlap];
-                add(queries.bases + queries.offsets[o.query_read_id] + seg.q_begin, int64_t(seg.q_end - seg.q_begin),
-                    (seg.flags & GWAMD_SEGMENT_REVERSE) != 0, int32_t(seg.overlap),
-                    int32_t(int64_t(seg.t_begin) - from), int32_t(int64_t(seg.t_end) - from));
+                add(1, o.query_read_id, seg.q_begin, seg.q_end, (seg.flags & GWAMD_SEGMENT_REVERSE) != 0,
+                    int32_t(seg.overlap), int32_t(int64_t(seg.t_begin) - from), int32_t(int64_t(seg.t_end) - from));
             }
             out->window_counts.push_back(int32_t(list.size()) + 1);
             out->window_target.push_back(uint32_t(r));
             out->window_index.push_back(uint32_t(k));
         }
+    }
+    return out;
+}
+
+// group_slices, and every slice's bases copied out of the host's reads
+std::unique_ptr<gwamd_windows> group_windows(const gm::ReadSet& targets, const gm::ReadSet& queries,
+                                             const std::vector<gm::OverlapRecord>& overlaps,
+                                             const gwamd_window_segment* segments, int64_t num_segments,
+                                             int32_t window_length, int32_t max_sequences_per_window)
+{
+    auto out     = std::make_unique<gwamd_windows>();
+    out->grouped = std::move(*group_slices(targets, queries, nullptr, 0, overlaps, segments, num_segments,
+                                           window_length, max_sequences_per_window));
+    for (const gwamd_read_slice& sl : out->grouped.slices)
+    {
+        const gm::ReadSet& set = sl.set == 0 ? targets : queries;
+        const char* src        = set.bases + set.offsets[sl.read] + sl.begin;
+        const int64_t len      = int64_t(sl.end) - int64_t(sl.begin);
+        const size_t at        = out->bases.size();
+        out->bases.resize(at + size_t(len));
+        for (int64_t j = 0; j < len; j++)
+            out->bases[at + size_t(j)] = (sl.flags & GWAMD_SLICE_REVERSE) ? complement(src[len - 1 - j]) : src[j];
+        out->sequence_offsets.push_back(int64_t(out->bases.size()));
     }
     return out;
 }
@@ -520,12 +565,13 @@ Windows build_windows(const io::FastaParser& targets, const io::FastaParser& que
                       reinterpret_cast<const gwamd_window_segment*>(segments.data()), int64_t(segments.size()),
                       window_length, max_sequences_per_window);
     Windows out;
+    const gwamd_window_slices& g = h->grouped;
     out.bases          = std::move(h->bases);
-    out.target         = std::move(h->window_target);
-    out.window         = std::move(h->window_index);
-    out.dropped_by_cap = h->dropped_by_cap;
+    out.target         = g.window_target;
+    out.window         = g.window_index;
+    out.dropped_by_cap = g.dropped_by_cap;
     size_t s           = 0;
-    for (int32_t count : h->window_counts)
+    for (int32_t count : g.window_counts)
     {
         cudapoa::Group group;
         std::vector<Windows::Sequence> meta;
@@ -533,7 +579,7 @@ Windows build_windows(const io::FastaParser& targets, const io::FastaParser& que
         {
             group.push_back(cudapoa::Entry{out.bases.data() + h->sequence_offsets[s], nullptr,
                                            int32_t(h->sequence_offsets[s + 1] - h->sequence_offsets[s])});
-            meta.push_back({h->sequence_overlap[s], h->sequence_t_begin[s], h->sequence_t_end[s]});
+            meta.push_back({g.sequence_overlap[s], g.sequence_t_begin[s], g.sequence_t_end[s]});
         }
         out.groups.push_back(std::move(group));
         out.sequence.push_back(std::move(meta));
@@ -678,22 +724,92 @@ int32_t gwamd_windows_get(const gwamd_windows* windows, gwamd_windows_view* view
     return gm::guarded_map([&] {
         if (!windows || !view)
             throw std::invalid_argument("windows or view is NULL");
-        view->num_windows      = int64_t(windows->window_counts.size());
-        view->num_sequences    = int64_t(windows->sequence_overlap.size());
+        const gwamd_window_slices& g = windows->grouped;
+        view->num_windows      = int64_t(g.window_counts.size());
+        view->num_sequences    = int64_t(g.sequence_overlap.size());
         view->num_bases        = int64_t(windows->bases.size());
-        view->dropped_by_cap   = windows->dropped_by_cap;
+        view->dropped_by_cap   = g.dropped_by_cap;
         view->bases            = windows->bases.data();
         view->sequence_offsets = windows->sequence_offsets.data();
-        view->window_counts    = windows->window_counts.data();
-        view->window_target    = windows->window_target.data();
-        view->window_index     = windows->window_index.data();
-        view->sequence_overlap = windows->sequence_overlap.data();
-        view->sequence_t_begin = windows->sequence_t_begin.data();
-        view->sequence_t_end   = windows->sequence_t_end.data();
+        view->window_counts    = g.window_counts.data();
+        view->window_target    = g.window_target.data();
+        view->window_index     = g.window_index.data();
+        view->sequence_overlap = g.sequence_overlap.data();
+        view->sequence_t_begin = g.sequence_t_begin.data();
+        view->sequence_t_end   = g.sequence_t_end.data();
         return int32_t(0);
     });
 }
 
 void gwamd_windows_free(gwamd_windows* windows) { delete windows; }
+
+int32_t gwamd_build_window_slices(const int64_t* target_offsets, int32_t num_targets, const int64_t* query_offsets,
+                                  int32_t num_queries, const char* query_qualities_or_null,
+                                  int32_t quality_threshold_tenths, const gwamd_overlap* overlaps, int64_t n,
+                                  const gwamd_window_segment* segments, int64_t num_segments, int32_t window_length,
+                                  int32_t max_sequences_per_window, gwamd_window_slices** out)
+{
+    if (out)
+        *out = nullptr;
+    return gm::guarded_map([&] {
+        if (!out)
+            throw std::invalid_argument("out is NULL");
+        // only offsets are read: the bases pointer stands for "somewhere"
+        static const char somewhere = 0;
+        const gm::ReadSet targets{&somewhere, target_offsets, num_targets};
+        const gm::ReadSet queries{&somewhere, query_offsets, num_queries};
+        gm::check_read_set("target", targets);
+        gm::check_read_set("query", queries);
+        if (query_qualities_or_null)
+            gm::check_qualities(queries, query_qualities_or_null);
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        *out = group_slices(targets, queries, query_qualities_or_null, quality_threshold_tenths, records, segments,
+                            num_segments, window_length, max_sequences_per_window)
+                   .release();
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_window_slices_get(const gwamd_window_slices* windows, gwamd_window_slices_view* view)
+{
+    return gm::guarded_map([&] {
+        if (!windows || !view)
+            throw std::invalid_argument("windows or view is NULL");
+        view->num_windows        = int64_t(windows->window_counts.size());
+        view->num_sequences      = int64_t(windows->slices.size());
+        view->dropped_by_cap     = windows->dropped_by_cap;
+        view->dropped_by_quality = windows->dropped_by_quality;
+        view->slices             = windows->slices.data();
+        view->window_counts      = windows->window_counts.data();
+        view->window_target      = windows->window_target.data();
+        view->window_index       = windows->window_index.data();
+        view->sequence_overlap   = windows->sequence_overlap.data();
+        view->sequence_t_begin   = windows->sequence_t_begin.data();
+        view->sequence_t_end     = windows->sequence_t_end.data();
+        return int32_t(0);
+    });
+}
+
+void gwamd_window_slices_free(gwamd_window_slices* windows) { delete windows; }
+
+int32_t gwamd_trim_consensus(const uint16_t* coverage, int32_t length, int32_t num_sequences, int32_t* begin,
+                             int32_t* past_the_end)
+{
+    return gm::guarded_map([&] {
+        if (!begin || !past_the_end || length < 0 || num_sequences < 1 || (length > 0 && !coverage))
+            throw std::invalid_argument("trim_consensus: NULL pointer, negative length or no sequence");
+        const int32_t average = (num_sequences - 1) / 2;
+        int32_t first = 0, last = length - 1;
+        while (first < length && int32_t(coverage[first]) < average)
+            first++;
+        while (last >= 0 && int32_t(coverage[last]) < average)
+            last--;
+        const bool trim = first < last;
+        *begin          = trim ? first : 0;
+        *past_the_end   = trim ? last + 1 : length;
+        return int32_t(0);
+    });
+}
 
 } // extern "C"

@@ -67,6 +67,8 @@ def _declare(L):
     L.gwamd_format_paf.argtypes = [C.c_char_p, vp, vp, i32, C.c_char_p, vp, vp, i32, vp, i32, vp, i32, P(vp)]
     L.gwamd_read_fasta.restype = i32
     L.gwamd_read_fasta.argtypes = [C.c_char_p, C.c_uint32, i32, P(vp), P(vp)]
+    L.gwamd_read_fasta_with_qualities.restype = i32
+    L.gwamd_read_fasta_with_qualities.argtypes = [C.c_char_p, C.c_uint32, i32, P(vp), P(vp), P(vp)]
     L.gwamd_text_list_create.restype = i32
     L.gwamd_text_list_create.argtypes = [vp, vp, i32, P(vp)]
     L.gwamd_text_list_size.restype = i32
@@ -130,6 +132,10 @@ def _declare(L):
     L.gwamd_index_host_copy_free.argtypes = [vp]
     L.gwamd_device_reads_create.restype = i32
     L.gwamd_device_reads_create.argtypes = [C.c_char_p, vp, i32, i32, vp, P(vp)]
+    L.gwamd_device_reads_create_with_qualities.restype = i32
+    L.gwamd_device_reads_create_with_qualities.argtypes = [C.c_char_p, C.c_char_p, vp, i32, i32, vp, P(vp)]
+    L.gwamd_device_reads_has_qualities.restype = i32
+    L.gwamd_device_reads_has_qualities.argtypes = [vp]
     L.gwamd_device_reads_free.restype = None
     L.gwamd_device_reads_free.argtypes = [vp]
     L.gwamd_device_reads_info.restype = i32
@@ -186,21 +192,37 @@ class DeviceReads:
     one per side in place of the sequences and then move only the overlaps.
 
     reads: sequences (str or bytes), or (name, sequence) records as read_fasta
-    returns them.  allocator: a cudaaligner.DeviceAllocator whose pool the
-    device bytes are counted against until close()."""
+    returns them.  qualities: one quality string (str or bytes, Phred + 33)
+    per read, each of its read's length, kept in a second device array of the
+    same layout for CudaPoaBatch.add_poa_group_resident's base weights;
+    ValueError, before any device call, for another count or length and for a
+    character outside 33..126.  allocator: a cudaaligner.DeviceAllocator whose
+    pool the device bytes are counted against until close()."""
 
-    def __init__(self, reads, device_id=0, allocator=None):
+    def __init__(self, reads, device_id=0, allocator=None, qualities=None):
         self._lib = load_library()
         self._handle = C.c_void_p()
         seqs = [r[1] if isinstance(r, tuple) else r for r in reads]
         bases, offsets = _pack(seqs)
-        _check(self._lib.gwamd_device_reads_create(bases, offsets, len(seqs), int(device_id),
-                                                   allocator._handle if allocator is not None else None,
-                                                   C.byref(self._handle)))
+        pool = allocator._handle if allocator is not None else None
+        if qualities is None:
+            _check(self._lib.gwamd_device_reads_create(bases, offsets, len(seqs), int(device_id), pool,
+                                                       C.byref(self._handle)))
+        else:
+            qualities = list(qualities)
+            if len(qualities) != len(seqs):
+                raise ValueError("%d quality strings for %d reads" % (len(qualities), len(seqs)))
+            for i, (q, r) in enumerate(zip(qualities, seqs)):
+                if len(q) != len(r):
+                    raise ValueError("read %d has %d quality characters for %d bases" % (i, len(q), len(r)))
+            quals, _ = _pack(qualities)
+            _check(self._lib.gwamd_device_reads_create_with_qualities(bases, quals, offsets, len(seqs),
+                                                                      int(device_id), pool, C.byref(self._handle)))
         self._allocator = allocator  # the handle holds bytes of its pool
         n, b, d = C.c_int64(), C.c_int64(), C.c_int32()
         _check(self._lib.gwamd_device_reads_info(self._handle, C.byref(n), C.byref(b), C.byref(d)))
         self.number_of_reads, self.number_of_basepairs, self.device_id = n.value, b.value, d.value
+        self.has_qualities = bool(_check(self._lib.gwamd_device_reads_has_qualities(self._handle)))
 
     def __len__(self):
         return self.number_of_reads
@@ -315,6 +337,16 @@ def read_fasta(path, min_sequence_length=0, shuffle=True):
     _check(L.gwamd_read_fasta(str(path).encode(), int(min_sequence_length), int(bool(shuffle)), C.byref(n),
                               C.byref(s)))
     return list(zip(_take(L, n), _take(L, s)))
+
+
+def read_fasta_with_qualities(path, min_sequence_length=0, shuffle=True):
+    """(records, qualities): read_fasta's records and each one's quality
+    string, of its sequence's length for a FASTQ record and "" for a FASTA one."""
+    L = load_library()
+    n, s, q = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(L.gwamd_read_fasta_with_qualities(str(path).encode(), int(min_sequence_length), int(bool(shuffle)),
+                                             C.byref(n), C.byref(s), C.byref(q)))
+    return list(zip(_take(L, n), _take(L, s))), _take(L, q)
 
 
 class Index:

@@ -111,6 +111,7 @@ class CudaPoaBatch:
                  max_nodes_per_window=None, max_nodes_per_window_banded=None, spoa_accurate=None, *args, **kwargs):
         self._lib = load_library()
         self._handle = C.c_void_p()
+        self._resident_sets = []  # the DeviceReads of add_poa_group_resident, until reset()
         if stream is None:
             st = None
         elif isinstance(stream, int):
@@ -171,6 +172,47 @@ class CudaPoaBatch:
         seq_status = (C.c_int32 * n)()
         rc = _check(self._lib.gwamd_poa_add_poa_group(self._handle, seqs, wptrs, lens, n, seq_status))
         return rc, list(seq_status)
+
+    def add_poa_group_resident(self, sets, slices):
+        """add_poa_group for sequences named as slices of reads resident on the
+        batch's device (gwamd_poa_add_poa_group_resident): sets is a list of
+        cudamapper.DeviceReads and a slice (set, read, begin, end, flags) is
+        bases [begin, end) of read `read` of sets[set], reverse-complemented
+        when bit 0 of flags is set.  upload() writes the bases on the device
+        and, as weights, quality - 33 of a set with qualities and 1 of a set
+        without.  Same statuses as add_poa_group on the same sequences.  The
+        batch keeps the DeviceReads alive until reset().  ValueError, with the
+        batch unchanged, for a slice outside its read or set and for a set on
+        another device."""
+        from .cudapolish import SLICE_DTYPE
+        handles = (C.c_void_p * max(len(sets), 1))()
+        for i, r in enumerate(sets):
+            if not getattr(r, "_handle", None):
+                raise ValueError("set %d is not an open DeviceReads" % i)
+            handles[i] = r._handle
+        n = len(slices)
+        if isinstance(slices, np.ndarray) and slices.dtype == SLICE_DTYPE:
+            arr = np.ascontiguousarray(slices)
+        else:  # (set, read, begin, end, flags) tuples
+            try:
+                arr = np.array([tuple(sl) for sl in slices], dtype=SLICE_DTYPE) if n else np.zeros(1, SLICE_DTYPE)
+            except OverflowError as e:
+                raise ValueError("a slice field is outside its 32-bit range: %s" % e)
+        seq_status = (C.c_int32 * max(n, 1))()
+        rc = _check(self._lib.gwamd_poa_add_poa_group_resident(self._handle, handles, len(sets),
+                                                               arr.ctypes.data_as(C.c_void_p), n, seq_status))
+        self._resident_sets.extend(sets)
+        return rc, list(seq_status)[:n]
+
+    def _download_inputs(self):
+        """Test hook: (bases, weights) of the batch's packed input as upload()
+        left it on the device, the 16 bytes after the last base included."""
+        count = _check(self._lib.gwamd_internal_poa_download_inputs(self._handle, None, None))
+        seqs = np.zeros(count, np.uint8)
+        wts = np.zeros(count, np.int8)
+        _check(self._lib.gwamd_internal_poa_download_inputs(self._handle, seqs.ctypes.data_as(C.c_void_p),
+                                                            wts.ctypes.data_as(C.c_void_p)))
+        return seqs.tobytes(), wts.tobytes()
 
     @property
     def total_poas(self):
@@ -344,6 +386,7 @@ class CudaPoaBatch:
 
     def reset(self):
         self._lib.gwamd_poa_reset(self._handle)
+        del self._resident_sets[:]
 
 
 class CudaPoaMultiBatch:

@@ -11,8 +11,15 @@ Path states are AlignmentState values, start -> end: 0 match and 1 mismatch
 advance both sequences, 3 (deletion) advances ONLY THE QUERY and 2 (insertion)
 ONLY THE TARGET, the reference's convention and the opposite of SAM's I / D.
 
-Not done: quality weights, racon's coverage trimming of consensus ends,
-positional (sub-graph) alignment of a segment within its window.
+With device_windows (or qualities) polish names the window sequences as
+slices of the reads already resident on the GPU (build_window_slices,
+CudaPoaBatch.add_poa_group_resident): no window base is copied on the host or
+sent to the device a second time, and base qualities become POA weights on the
+device.  Segments of low mean quality are dropped as racon drops them, and
+trim_consensus is racon's coverage trimming of a window's consensus ends.
+
+Not done: positional (sub-graph) alignment of a segment within its window, a
+command-line polisher.
 """
 import ctypes as C
 
@@ -26,6 +33,20 @@ REVERSE, EMPTY, BAD_PATH, NOT_ALIGNED = 1, 2, 4, 8
 # gwamd_window_segment
 SEGMENT_DTYPE = np.dtype([(n, np.uint32) for n in ("overlap", "window", "q_begin", "q_end", "t_begin", "t_end",
                                                    "flags", "reserved")])
+
+
+# gwamd_read_slice
+SLICE_DTYPE = np.dtype([("set", np.int32), ("read", np.uint32), ("begin", np.uint32), ("end", np.uint32),
+                        ("flags", np.uint32)])
+SLICE_REVERSE = 1
+
+
+class _WindowSlicesView(C.Structure):
+    """gwamd_window_slices_view."""
+    _fields_ = [("num_windows", C.c_int64), ("num_sequences", C.c_int64), ("dropped_by_cap", C.c_int64),
+                ("dropped_by_quality", C.c_int64), ("slices", C.c_void_p), ("window_counts", C.c_void_p),
+                ("window_target", C.c_void_p), ("window_index", C.c_void_p), ("sequence_overlap", C.c_void_p),
+                ("sequence_t_begin", C.c_void_p), ("sequence_t_end", C.c_void_p)]
 
 
 class _WindowsView(C.Structure):
@@ -55,6 +76,18 @@ def _declare(L):
     L.gwamd_windows_get.argtypes = [vp, P(_WindowsView)]
     L.gwamd_windows_free.restype = None
     L.gwamd_windows_free.argtypes = [vp]
+    L.gwamd_build_window_slices.restype = i32
+    L.gwamd_build_window_slices.argtypes = [vp, i32, vp, i32, C.c_char_p, i32, vp, i64, vp, i64, i32, i32, P(vp)]
+    L.gwamd_window_slices_get.restype = i32
+    L.gwamd_window_slices_get.argtypes = [vp, P(_WindowSlicesView)]
+    L.gwamd_window_slices_free.restype = None
+    L.gwamd_window_slices_free.argtypes = [vp]
+    L.gwamd_trim_consensus.restype = i32
+    L.gwamd_trim_consensus.argtypes = [vp, i32, i32, P(i32), P(i32)]
+    L.gwamd_poa_add_poa_group_resident.restype = i32
+    L.gwamd_poa_add_poa_group_resident.argtypes = [vp, vp, i32, vp, i32, P(i32)]
+    L.gwamd_internal_poa_download_inputs.restype = i32
+    L.gwamd_internal_poa_download_inputs.argtypes = [vp, vp, vp]
 
 
 def _take_segments(L, p, n):
@@ -169,19 +202,14 @@ def build_windows(targets, queries, overlaps, segments, window_length, max_seque
         v = _WindowsView()
         _check(L.gwamd_windows_get(h, C.byref(v)))
 
-        def array(address, count, dtype):
-            if not count:
-                return np.zeros(0, dtype)
-            return np.frombuffer(C.string_at(address, count * np.dtype(dtype).itemsize), dtype)
-
         bases = C.string_at(v.bases, v.num_bases).decode("latin-1") if v.num_bases else ""
-        off = array(v.sequence_offsets, v.num_sequences + 1, np.int64)
-        counts = array(v.window_counts, v.num_windows, np.int32)
-        target = array(v.window_target, v.num_windows, np.uint32)
-        index = array(v.window_index, v.num_windows, np.uint32)
-        overlap = array(v.sequence_overlap, v.num_sequences, np.int32)
-        t_begin = array(v.sequence_t_begin, v.num_sequences, np.int32)
-        t_end = array(v.sequence_t_end, v.num_sequences, np.int32)
+        off = _array(v.sequence_offsets, v.num_sequences + 1, np.int64)
+        counts = _array(v.window_counts, v.num_windows, np.int32)
+        target = _array(v.window_target, v.num_windows, np.uint32)
+        index = _array(v.window_index, v.num_windows, np.uint32)
+        overlap = _array(v.sequence_overlap, v.num_sequences, np.int32)
+        t_begin = _array(v.sequence_t_begin, v.num_sequences, np.int32)
+        t_end = _array(v.sequence_t_end, v.num_sequences, np.int32)
         windows, s = [], 0
         for i in range(v.num_windows):
             c = int(counts[i])
@@ -195,9 +223,114 @@ def build_windows(targets, queries, overlaps, segments, window_length, max_seque
         L.gwamd_windows_free(h)
 
 
+def _array(address, count, dtype):
+    if not count:
+        return np.zeros(0, dtype)
+    return np.frombuffer(C.string_at(address, count * np.dtype(dtype).itemsize), dtype)
+
+
+def _lengths_offsets(reads):
+    offs = (C.c_int64 * (len(reads) + 1))()
+    for i, r in enumerate(reads):
+        offs[i + 1] = offs[i] + (r if isinstance(r, int) else len(r))
+    return offs
+
+
+def build_window_slices(targets, queries, overlaps, segments, window_length, max_sequences_per_window=100,
+                        query_qualities=None, quality_threshold=10.0):
+    """(windows, dropped_by_cap, dropped_by_quality): the grouping of
+    build_windows without the bases.  Each window is a dict of "target",
+    "window", "overlap", "t_begin", "t_end" as build_windows gives them and
+    "slices": per sequence (set, read, begin, end, flags) with set 0 the targets
+    (the backbone, first) and set 1 the queries, flags & SLICE_REVERSE for a
+    reverse-complemented one.  targets / queries: the reads or just their
+    lengths.
+
+    query_qualities: one quality string (Phred + 33) per query.  A segment that
+    passes the keep rule is then dropped, before the cap, when the mean of
+    quality - 33 over its query range is below quality_threshold (racon's
+    rule).  The threshold counts in tenths, round(10 * quality_threshold), and
+    the test is the integer one: 10 * sum < tenths * length, so a mean equal to
+    the threshold keeps the segment.  Host only."""
+    L = load_library()
+    to, qo = _lengths_offsets(targets), _lengths_offsets(queries)
+    quals = None
+    if query_qualities is not None:
+        if len(query_qualities) != len(queries):
+            raise ValueError("%d quality strings for %d queries" % (len(query_qualities), len(queries)))
+        for i, q in enumerate(query_qualities):
+            if len(q) != qo[i + 1] - qo[i]:
+                raise ValueError("query %d has %d quality characters for %d bases" % (i, len(q), qo[i + 1] - qo[i]))
+        quals, _ = _pack(query_qualities)
+    arr = _overlap_array(overlaps)
+    segs = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+    h = C.c_void_p()
+    _check(L.gwamd_build_window_slices(to, len(targets), qo, len(queries), quals,
+                                       int(round(10 * float(quality_threshold))), arr, len(overlaps),
+                                       segs.ctypes.data_as(C.c_void_p), len(segs), int(window_length),
+                                       int(max_sequences_per_window), C.byref(h)))
+    try:
+        v = _WindowSlicesView()
+        _check(L.gwamd_window_slices_get(h, C.byref(v)))
+        slices = _array(v.slices, v.num_sequences, SLICE_DTYPE)
+        counts = _array(v.window_counts, v.num_windows, np.int32)
+        target = _array(v.window_target, v.num_windows, np.uint32)
+        index = _array(v.window_index, v.num_windows, np.uint32)
+        overlap = _array(v.sequence_overlap, v.num_sequences, np.int32)
+        t_begin = _array(v.sequence_t_begin, v.num_sequences, np.int32)
+        t_end = _array(v.sequence_t_end, v.num_sequences, np.int32)
+        slices = slices.tolist()  # tuples of ints
+        windows, s = [], 0
+        for i in range(v.num_windows):
+            c = int(counts[i])
+            windows.append({"target": int(target[i]), "window": int(index[i]), "slices": slices[s:s + c],
+                            "overlap": overlap[s:s + c].tolist(), "t_begin": t_begin[s:s + c].tolist(),
+                            "t_end": t_end[s:s + c].tolist()})
+            s += c
+        return windows, int(v.dropped_by_cap), int(v.dropped_by_quality)
+    finally:
+        L.gwamd_window_slices_free(h)
+
+
+def trim_consensus(consensus, coverage, num_sequences):
+    """racon's trimming of a window's consensus by coverage (window.cpp): with
+    average = (num_sequences - 1) // 2, num_sequences counting the backbone, the
+    consensus from the first to the last index whose coverage is at least
+    average, both included.  When no index qualifies, or the first is not before
+    the last, the consensus comes back whole (racon warns there).  Host only."""
+    L = load_library()
+    if len(coverage) != len(consensus):
+        raise ValueError("one coverage value per consensus base expected")
+    cov = np.ascontiguousarray(list(coverage) + [0], dtype=np.uint16)
+    b, e = C.c_int32(), C.c_int32()
+    _check(L.gwamd_trim_consensus(cov.ctypes.data_as(C.c_void_p), len(consensus), int(num_sequences), C.byref(b),
+                                  C.byref(e)))
+    return consensus[b.value:e.value]
+
+
+_COMPLEMENT = {ord("A"): "T", ord("T"): "A", ord("C"): "G", ord("G"): "C"}
+
+
+def _slice_text(sets, sl):
+    """The bases of a slice, cut from the host strings."""
+    text = sets[sl[0]][sl[1]][sl[2]:sl[3]]
+    return text[::-1].translate(_COMPLEMENT) if sl[4] & SLICE_REVERSE else text
+
+
+def _slice_weights(qualities, sl):
+    """The weights of a slice: quality - 33 per base, 1 without qualities."""
+    if qualities[sl[0]] is None:
+        return [1] * (sl[3] - sl[2])
+    q = qualities[sl[0]][sl[1]][sl[2]:sl[3]]
+    q = q.encode("latin-1") if isinstance(q, str) else bytes(q)
+    w = [c - 33 for c in q]
+    return w[::-1] if sl[4] & SLICE_REVERSE else w
+
+
 def polish(targets, queries, overlaps, window_length=500, max_sequences_per_window=100, banded=True,
            band_width=256, scores=(8, -6, -8), num_alignment_engines=1, device_id=0, max_gpu_mem=None,
-           return_windows=False):
+           return_windows=False, device_windows=False, query_qualities=None, target_qualities=None,
+           quality_threshold=10.0, trim=False):
     """Polished targets from targets, reads and overlaps (query = read, target =
     target): the overlaps are aligned and cut on the GPU
     (window_segments_resident), grouped into windows (build_windows) and run
@@ -207,68 +340,116 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
     batch may take (default: half of the device's free memory); windows beyond
     what it holds at once are processed in rounds.
 
+    device_windows: the windows are named as slices of the two resident read
+    sets (build_window_slices) and added with add_poa_group_resident, so the
+    POA batch's input is written on the device; the reads stay resident until
+    the POA is done.  Same result as the default route.  query_qualities /
+    target_qualities: one quality string (Phred + 33) per read; either implies
+    device_windows, and the POA then weighs every base of that side with
+    quality - 33 (a side without qualities weighs 1).  With query_qualities a
+    segment whose mean quality is below quality_threshold is dropped
+    (build_window_slices).  trim: every consensus is cut to racon's coverage
+    rule (trim_consensus) before it is joined.
+
     Returns (polished, stats); stats counts "windows", "backbone_by_rule"
-    (fewer than three sequences), "backbone_by_status", "dropped_by_cap" and
-    carries the "max_sequence_size" the POA batch was made for.  With
-    return_windows the windows and each one's consensus (None for a backbone by
-    rule) and status are appended to the result."""
+    (fewer than three sequences), "backbone_by_status", "dropped_by_cap",
+    "dropped_by_quality", "trimmed_bases" and carries the "max_sequence_size"
+    the POA batch was made for.  With return_windows the windows and each one's
+    consensus (None for a backbone by rule; as the POA gave it, untrimmed) and
+    status are appended to the result; on the device route a window also
+    carries its "slices" and "weights", and its "sequences" are cut from the
+    host strings."""
     from .cudapoa import CudaPoaBatch
     import torch
 
     targets = [t[1] if isinstance(t, tuple) else t for t in targets]
     queries = [q[1] if isinstance(q, tuple) else q for q in queries]
+    resident = bool(device_windows) or query_qualities is not None or target_qualities is not None
     with torch.cuda.device(device_id):
-        q_reads = DeviceReads(queries, device_id=device_id)
-        t_reads = DeviceReads(targets, device_id=device_id)
+        q_reads = DeviceReads(queries, device_id=device_id, qualities=query_qualities)
         try:
+            t_reads = DeviceReads(targets, device_id=device_id, qualities=target_qualities)
+        except Exception:
+            q_reads.close()
+            raise
+    try:
+        with torch.cuda.device(device_id):
             segments = window_segments_resident(overlaps, q_reads, t_reads, window_length, num_alignment_engines)
-        finally:
+        by_quality = 0
+        if resident:
+            windows, dropped, by_quality = build_window_slices(
+                targets, queries, overlaps, segments, window_length, max_sequences_per_window,
+                query_qualities=query_qualities, quality_threshold=quality_threshold)
+            backbone = [_slice_text((targets, queries), w["slices"][0]) for w in windows]
+            lengths = [[sl[3] - sl[2] for sl in w["slices"]] for w in windows]
+            if return_windows:
+                for w in windows:
+                    w["sequences"] = [_slice_text((targets, queries), sl) for sl in w["slices"]]
+                    w["weights"] = [_slice_weights((target_qualities, query_qualities), sl) for sl in w["slices"]]
+        else:
             q_reads.close()
             t_reads.close()
-    windows, dropped = build_windows(targets, queries, overlaps, segments, window_length, max_sequences_per_window)
-    stats = {"windows": len(windows), "backbone_by_rule": 0, "backbone_by_status": 0, "dropped_by_cap": dropped}
-    todo = [i for i, w in enumerate(windows) if len(w["sequences"]) >= 3]
-    stats["backbone_by_rule"] = len(windows) - len(todo)
-    longest = max([len(s) for i in todo for s in windows[i]["sequences"]] + [1])
-    # a sequence must be shorter than the batch's limit; sizes in steps of 64
-    max_sequence_size = (longest + 1 + 63) // 64 * 64
-    stats["max_sequence_size"] = max_sequence_size
-    consensus = [None] * len(windows)
-    status = [None] * len(windows)
-    if todo:
-        if max_gpu_mem is None:
-            max_gpu_mem = int(0.5 * torch.cuda.mem_get_info(device_id)[0])
-        batch = CudaPoaBatch(max_sequences_per_window, max_sequence_size, int(max_gpu_mem), device_id=device_id,
-                             gap_score=scores[2], mismatch_score=scores[1], match_score=scores[0],
-                             cuda_banded_alignment=banded, alignment_band_width=band_width)
-        held = []
+            windows, dropped = build_windows(targets, queries, overlaps, segments, window_length,
+                                             max_sequences_per_window)
+            backbone = [w["sequences"][0] for w in windows]
+            lengths = [[len(s) for s in w["sequences"]] for w in windows]
+        stats = {"windows": len(windows), "backbone_by_rule": 0, "backbone_by_status": 0, "dropped_by_cap": dropped,
+                 "dropped_by_quality": by_quality, "trimmed_bases": 0}
+        todo = [i for i, n in enumerate(lengths) if len(n) >= 3]
+        stats["backbone_by_rule"] = len(windows) - len(todo)
+        longest = max([n for i in todo for n in lengths[i]] + [1])
+        # a sequence must be shorter than the batch's limit; sizes in steps of 64
+        max_sequence_size = (longest + 1 + 63) // 64 * 64
+        stats["max_sequence_size"] = max_sequence_size
+        consensus = [None] * len(windows)
+        coverage = [None] * len(windows)
+        status = [None] * len(windows)
+        if todo:
+            if max_gpu_mem is None:
+                max_gpu_mem = int(0.5 * torch.cuda.mem_get_info(device_id)[0])
+            batch = CudaPoaBatch(max_sequences_per_window, max_sequence_size, int(max_gpu_mem), device_id=device_id,
+                                 gap_score=scores[2], mismatch_score=scores[1], match_score=scores[0],
+                                 cuda_banded_alignment=banded, alignment_band_width=band_width)
+            held = []
 
-        def flush():
-            if not held:
-                return
-            batch.generate_poa()
-            cons, _, st = batch.get_consensus()
-            for j, i in enumerate(held):
-                consensus[i], status[i] = cons[j], st[j]
-            batch.reset()
-            del held[:]
+            def add(i):
+                if resident:
+                    return batch.add_poa_group_resident([t_reads, q_reads], windows[i]["slices"])[0]
+                return batch.add_poa_group(windows[i]["sequences"])[0]
 
-        for i in todo:
-            st, _ = batch.add_poa_group(windows[i]["sequences"])
-            if st == 1:  # exceeded_maximum_poas: process what the batch holds, then add again
-                flush()
-                st, _ = batch.add_poa_group(windows[i]["sequences"])
-            if st != 0:
-                status[i] = st
-                continue
-            held.append(i)
-        flush()
+            def flush():
+                if not held:
+                    return
+                batch.generate_poa()
+                cons, cov, st = batch.get_consensus()
+                for j, i in enumerate(held):
+                    consensus[i], coverage[i], status[i] = cons[j], cov[j], st[j]
+                batch.reset()
+                del held[:]
+
+            for i in todo:
+                st = add(i)
+                if st == 1:  # exceeded_maximum_poas: process what the batch holds, then add again
+                    flush()
+                    st = add(i)
+                if st != 0:
+                    status[i] = st
+                    continue
+                held.append(i)
+            flush()
+            del batch
+    finally:
+        q_reads.close()
+        t_reads.close()
     polished = ["" for _ in targets]
     for i, w in enumerate(windows):
-        text = w["sequences"][0]
+        text = backbone[i]
         if consensus[i] is not None and status[i] == 0:
             text = consensus[i]
-        elif len(w["sequences"]) >= 3:
+            if trim:
+                text = trim_consensus(text, coverage[i], len(lengths[i]))
+                stats["trimmed_bases"] += len(consensus[i]) - len(text)
+        elif len(lengths[i]) >= 3:
             stats["backbone_by_status"] += 1
         polished[w["target"]] += text
     if return_windows:

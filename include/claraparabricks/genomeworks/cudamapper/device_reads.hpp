@@ -32,6 +32,16 @@ public:
     /// Throws std::invalid_argument for a read of 2^31 bases or more.
     static std::unique_ptr<DeviceReads> create(DefaultDeviceAllocator allocator, const io::FastaParser& parser,
                                                hipStream_t stream = 0);
+    /// The same with the parser's quality strings (FastaParser::get_quality_by_id)
+    /// in a second device array of the bases' layout, for
+    /// cudapolish::add_poa_group_resident's base weights.  Throws
+    /// std::invalid_argument unless every record has one quality character in
+    /// 33..126 per base (a FASTA record has none).
+    struct with_qualities_t
+    {
+    };
+    static std::unique_ptr<DeviceReads> create(DefaultDeviceAllocator allocator, const io::FastaParser& parser,
+                                               with_qualities_t, hipStream_t stream = 0);
     ~DeviceReads();
     DeviceReads(const DeviceReads&) = delete;
     DeviceReads& operator=(const DeviceReads&) = delete;
@@ -40,6 +50,7 @@ public:
     std::int64_t number_of_basepairs() const;
     /// The device the reads are on.
     std::int32_t device_id() const;
+    bool has_qualities() const;
 
     struct Impl;
     const Impl& impl() const { return *impl_; }

@@ -9,8 +9,14 @@
 // insertion (2) ONLY THE TARGET (alignment_impl.cpp:94-103), the opposite of
 // SAM's I / D.  The semantics of a record are in include/gwamd_polish.h.
 //
-// Not done here: quality weights, racon's coverage trimming of consensus ends,
-// positional (sub-graph) alignment of a segment within its window.
+// add_poa_group_resident adds a window to a cudapoa batch as slices of reads
+// that are already on the device (cudamapper::DeviceReads), with base qualities
+// as weights when the reads carry them; the grouping into slices, racon's
+// mean-quality filter and its coverage trimming are in the C ABI
+// (gwamd_build_window_slices, gwamd_trim_consensus, include/gwamd_polish.h).
+//
+// Not done here: positional (sub-graph) alignment of a segment within its
+// window, a command-line polisher.
 #pragma once
 
 #include <claraparabricks/genomeworks/cudaaligner/cudaaligner.hpp>
@@ -103,6 +109,38 @@ struct Windows
 Windows build_windows(const io::FastaParser& targets, const io::FastaParser& queries,
                       const std::vector<cudamapper::Overlap>& overlaps, const std::vector<WindowSegment>& segments,
                       int32_t window_length, int32_t max_sequences_per_window = 100);
+
+/// gwamd_read_slice: bases [begin, end) of read `read` of sets[set],
+/// reverse-complemented (A<->T, C<->G, every position) when flags & reverse
+struct ReadSlice
+{
+    enum Flags : uint32_t
+    {
+        reverse = 1
+    };
+    int32_t set;
+    uint32_t read;
+    uint32_t begin;
+    uint32_t end;
+    uint32_t flags;
+};
+
+/// Batch::add_poa_group for sequences that are slices of reads resident on the
+/// batch's device: the same group status, per_seq_status, capacity and window
+/// order as adding the same sequences from the host, and no base crosses the
+/// bus.  generate_poa() writes the bases into the batch's input on the device
+/// and, as base weights, quality - 33 of a set created with qualities
+/// (reversed, not complemented, for a reverse slice) and 1 of a set without.
+/// Host-added and resident groups may be mixed in one batch.  `batch` comes
+/// from cudapoa::create_batch.  The read sets must outlive the batch's use of
+/// them: until Batch::reset() or the batch's destruction after the last
+/// generate_poa() that uses them has completed.  Throws std::invalid_argument,
+/// before any device call and with the batch unchanged, for a null set, a set
+/// index or read id out of range, begin > end or end beyond the read, and a
+/// set on another device than the batch.
+cudapoa::StatusType add_poa_group_resident(cudapoa::Batch& batch, std::vector<cudapoa::StatusType>& per_seq_status,
+                                           const std::vector<const cudamapper::DeviceReads*>& sets,
+                                           const std::vector<ReadSlice>& slices);
 
 } // namespace cudapolish
 } // namespace genomeworks

@@ -33,6 +33,14 @@ public:
     virtual number_of_reads_t get_num_seqences() const = 0;
     /// Record by index; throws std::out_of_range for an index beyond the last record.
     virtual const FastaSequence& get_sequence_by_id(read_id_t sequence_id) const = 0;
+    /// The quality string of a FASTQ record, one character per base (this
+    /// build's addition; the reference's parser drops it).  Empty for a FASTA
+    /// record and for a parser that keeps none.
+    virtual const std::string& get_quality_by_id(read_id_t /*sequence_id*/) const
+    {
+        static const std::string none;
+        return none;
+    }
 };
 
 /// Parses a FASTA (or FASTQ) file.  Throws std::invalid_argument for a missing or empty file.
@@ -42,6 +50,10 @@ std::unique_ptr<FastaParser> create_kseq_fasta_parser(const std::string& fasta_f
 
 /// In-memory parser over records already read (this build's addition; used by the C ABI).
 std::unique_ptr<FastaParser> create_fasta_parser_from_sequences(std::vector<FastaSequence> records);
+/// The same with one quality string per record (empty: none).  Throws
+/// std::invalid_argument unless there are as many quality strings as records.
+std::unique_ptr<FastaParser> create_fasta_parser_from_sequences(std::vector<FastaSequence> records,
+                                                                std::vector<std::string> qualities);
 
 } // namespace io
 } // namespace genomeworks

@@ -103,6 +103,11 @@ int32_t gwamd_format_paf(const char* query_names, const int64_t* query_name_offs
  * sequences in parser order (shuffled with std::mt19937(0) when shuffle != 0). */
 int32_t gwamd_read_fasta(const char* path, uint32_t min_sequence_length, int32_t shuffle, gwamd_text_list** names,
                          gwamd_text_list** sequences);
+/* The same, and the records' quality strings: one per record, of its sequence's length for a
+ * FASTQ record and empty for a FASTA record. */
+int32_t gwamd_read_fasta_with_qualities(const char* path, uint32_t min_sequence_length, int32_t shuffle,
+                                        gwamd_text_list** names, gwamd_text_list** sequences,
+                                        gwamd_text_list** qualities);
 /* A list holding copies of n texts (e.g. CIGARs from another aligner run for gwamd_format_paf). */
 int32_t gwamd_text_list_create(const char* const* texts, const int64_t* lengths, int32_t n, gwamd_text_list** out);
 /* Entry i of a list (text and length, not NUL terminated beyond length). */
@@ -355,6 +360,17 @@ typedef struct gwamd_device_reads gwamd_device_reads;
 /* DeviceReads::create(allocator, parser, stream) (device_reads.hpp) on device_id */
 int32_t gwamd_device_reads_create(const char* bases, const int64_t* offsets, int32_t num_reads, int32_t device_id,
                                   struct gwamd_device_allocator* allocator_or_null, gwamd_device_reads** out);
+/* The same with the reads' quality characters in a second device array of the same layout:
+ * qualities[offsets[i], offsets[i + 1]) belongs to read i, one character per base (Phred + 33).
+ * GWAMD_E_INVALID_ARGUMENT, before any device call, also for a character outside 33..126 and
+ * NULL qualities with a base to describe.  gwamd_poa_add_poa_group_resident (gwamd_polish.h)
+ * turns them into base weights; every other entry treats the handle as one without. */
+int32_t gwamd_device_reads_create_with_qualities(const char* bases, const char* qualities, const int64_t* offsets,
+                                                 int32_t num_reads, int32_t device_id,
+                                                 struct gwamd_device_allocator* allocator_or_null,
+                                                 gwamd_device_reads** out);
+/* 1 when the handle carries qualities, 0 when not */
+int32_t gwamd_device_reads_has_qualities(const gwamd_device_reads* reads);
 void gwamd_device_reads_free(gwamd_device_reads* reads);
 /* number of reads, of bases, and the device; a NULL output is skipped */
 int32_t gwamd_device_reads_info(const gwamd_device_reads* reads, int64_t* num_reads, int64_t* num_bases,

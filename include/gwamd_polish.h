@@ -32,6 +32,8 @@
 #ifndef GWAMD_POLISH_H
 #define GWAMD_POLISH_H
 
+#include "gwamd_cudapoa.h"
+
 #include "gwamd_cudamapper.h"
 
 #ifdef __cplusplus
@@ -116,6 +118,88 @@ int32_t gwamd_build_windows(const char* target_bases, const int64_t* target_offs
 /* Pointers into the handle, valid until gwamd_windows_free. */
 int32_t gwamd_windows_get(const gwamd_windows* windows, gwamd_windows_view* view);
 void gwamd_windows_free(gwamd_windows* windows);
+
+/* ---- windows as slices of resident reads ---------------------------------------
+ *
+ * A sequence of a POA group named, not copied: bases [begin, end) of read `read` of the set
+ * sets[set], reverse-complemented (A<->T, C<->G, every other byte kept, every position) when
+ * bit 0 of flags is set. */
+#define GWAMD_SLICE_REVERSE 1u
+
+typedef struct gwamd_read_slice
+{
+    int32_t set; /* index into the sets of the call */
+    uint32_t read;
+    uint32_t begin;
+    uint32_t end;
+    uint32_t flags;
+} gwamd_read_slice;
+
+/* gwamd_poa_add_poa_group for sequences that are slices of reads resident on the batch's
+ * device: no base crosses the bus.  The bookkeeping is that of gwamd_poa_add_poa_group, so the
+ * returned group status, per_seq_status (n entries), the batch's capacity and the window order
+ * are those of adding the same sequences from the host.  gwamd_poa_upload / _generate_poa then
+ * writes the bases on the device into the batch's input and, as base weights, quality - 33 of a
+ * set that carries qualities (gwamd_device_reads_create_with_qualities; reversed, not
+ * complemented, for a reverse slice) and the constant 1, cudapoa's default, of a set that does
+ * not.  Host-added and resident groups may be mixed in one batch.
+ *
+ * The read sets must outlive the batch's use of them: until gwamd_poa_reset or
+ * gwamd_poa_destroy_batch after the last gwamd_poa_generate_poa that uses them has completed.
+ *
+ * GWAMD_E_INVALID_ARGUMENT, before any device call and with the batch unchanged: a NULL batch,
+ * sets array or set, NULL slices or per_seq_status with n > 0, n < 0, a set index outside
+ * [0, num_sets), a read id outside its set, begin > end or end beyond the read's length (from
+ * the handle's host copy of the offsets), a set on another device than the batch. */
+int32_t gwamd_poa_add_poa_group_resident(gwamd_poa_batch* batch, const gwamd_device_reads* const* sets,
+                                         int32_t num_sets, const gwamd_read_slice* slices, int32_t n,
+                                         int32_t* per_seq_status);
+
+/* Test hook: the batch's packed bases and weights as gwamd_poa_upload left them on the device,
+ * num_bases + 16 bytes each (the 16 bytes after the last base are zero); returns that count,
+ * and only that with both outputs NULL. */
+int32_t gwamd_internal_poa_download_inputs(gwamd_poa_batch* batch, uint8_t* seqs_out, int8_t* wts_out);
+
+/* The grouping of gwamd_build_windows without the bases (host only): the same windows, keep
+ * rule, order, cap and dropped_by_cap, each sequence a slice of set 0 (the targets: backbones)
+ * or set 1 (the queries).  With query_qualities_or_null (one character per query base, at the
+ * base's offset) a segment that passes the keep rule is dropped, before the cap is looked at,
+ * when the mean of quality - 33 over [q_begin, q_end) is below quality_threshold_tenths / 10
+ * (racon's rule), decided in integers: sum * 10 < quality_threshold_tenths * (q_end - q_begin).
+ * A mean equal to the threshold keeps the segment. */
+typedef struct gwamd_window_slices gwamd_window_slices;
+
+typedef struct gwamd_window_slices_view
+{
+    int64_t num_windows;
+    int64_t num_sequences;
+    int64_t dropped_by_cap;
+    int64_t dropped_by_quality;
+    const gwamd_read_slice* slices;  /* num_sequences, window after window, backbone first */
+    const int32_t* window_counts;    /* as in gwamd_windows_view */
+    const uint32_t* window_target;
+    const uint32_t* window_index;
+    const int32_t* sequence_overlap;
+    const int32_t* sequence_t_begin;
+    const int32_t* sequence_t_end;
+} gwamd_window_slices_view;
+
+int32_t gwamd_build_window_slices(const int64_t* target_offsets, int32_t num_targets, const int64_t* query_offsets,
+                                  int32_t num_queries, const char* query_qualities_or_null,
+                                  int32_t quality_threshold_tenths, const gwamd_overlap* overlaps, int64_t n,
+                                  const gwamd_window_segment* segments, int64_t num_segments, int32_t window_length,
+                                  int32_t max_sequences_per_window, gwamd_window_slices** out);
+/* Pointers into the handle, valid until gwamd_window_slices_free. */
+int32_t gwamd_window_slices_get(const gwamd_window_slices* windows, gwamd_window_slices_view* view);
+void gwamd_window_slices_free(gwamd_window_slices* windows);
+
+/* racon's trimming of a window's consensus by coverage (window.cpp): with average =
+ * (num_sequences - 1) / 2 (integer division; num_sequences counts the backbone), *begin is the
+ * first index with coverage >= average and *past_the_end one past the last such index: the
+ * trimmed consensus is consensus[*begin, *past_the_end).  When no index qualifies, or the first
+ * is not before the last, the consensus is kept whole (0, length), where racon warns. */
+int32_t gwamd_trim_consensus(const uint16_t* coverage, int32_t length, int32_t num_sequences, int32_t* begin,
+                             int32_t* past_the_end);
 
 /* Test hook: gwamd_window_segments on paths laid out as the aligner leaves them on the device,
  * end -> start, path i at paths[i * stride, i * stride + path_lengths[i]), stride a positive

@@ -10,12 +10,13 @@ compute runs in hand-written HIP kernels for gfx950; there is no CPU fallback.
 from ._lib import load_library, library_path  # noqa: F401
 from .cudamapper import (Index, match_anchors, get_overlaps, match_overlaps, post_process_overlaps,  # noqa: F401
                          rescue_overlap_ends, extend_overlap_by_sequence_similarity, DeviceReads,
-                         group_reads_into_indices, generate_batches_of_indices, IndexHostCopy)
+                         group_reads_into_indices, generate_batches_of_indices, IndexHostCopy, read_paf)
 from .cudapolish import (window_segments, window_segments_host, window_segments_resident,  # noqa: F401
+                         window_segments_cigar, window_segments_cigar_host, cigar_ops,
                          build_windows, build_window_slices, trim_consensus, polish)
 
 __all__ = ["load_library", "library_path", "Index", "match_anchors", "get_overlaps", "match_overlaps",
            "post_process_overlaps", "rescue_overlap_ends", "extend_overlap_by_sequence_similarity",
            "DeviceReads", "group_reads_into_indices", "generate_batches_of_indices",
            "IndexHostCopy", "window_segments", "window_segments_host", "window_segments_resident",
-           "build_windows", "build_window_slices", "trim_consensus", "polish"]
+           "window_segments_cigar", "window_segments_cigar_host", "cigar_ops", "read_paf", "build_windows", "build_window_slices", "trim_consensus", "polish"]

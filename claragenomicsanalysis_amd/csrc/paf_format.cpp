@@ -2,21 +2,177 @@
 // cudamapper/src/cudamapper_utils.cpp:30-112), and the parts of the C ABI
 // (include/gwamd_cudamapper.h) that only move text: gwamd_format_paf,
 // gwamd_read_fasta and the gwamd_text_list a call hands its texts back in.
+// The way back (include/gwamd_polish.h, cudapolish/windows.hpp): CIGAR text
+// as packed ops (gwamd_cigar_ops) and PAF text as overlaps and their ops
+// (gwamd_read_paf), for the cut from CIGAR runs.
 #include <claraparabricks/genomeworks/cudamapper/overlap_alignment.hpp>
+#include <claraparabricks/genomeworks/cudapolish/windows.hpp>
 #include <claraparabricks/genomeworks/io/fasta_parser.hpp>
 
+#include "../../include/gwamd_polish.h"
 #include "mapper_capi.hpp"
 
 #include <algorithm>
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
+#include <iterator>
 #include <mutex>
+#include <unordered_map>
 
 namespace gm = gwamd::mapper;
 
+// what gwamd_read_paf read
+struct gwamd_paf
+{
+    std::vector<gwamd_overlap> overlaps;
+    std::vector<uint32_t> ops;
+    std::vector<int64_t> op_offsets{0};
+};
+
 namespace
 {
+
+// The ops of CIGAR text, appended to out
+void parse_cigar(const char* text, size_t length, std::vector<uint32_t>& out)
+{
+    static const char letters[] = "MIDNSHP=X"; // BAM numbering
+    size_t i                    = 0;
+    while (i < length)
+    {
+        uint64_t value = 0;
+        size_t digits  = 0;
+        for (; i < length && text[i] >= '0' && text[i] <= '9'; i++, digits++)
+        {
+            value = value * 10 + uint64_t(text[i] - '0');
+            if (value >= (uint64_t(1) << 28))
+                throw std::invalid_argument("CIGAR: a length of 2^28 or more");
+        }
+        if (i == length)
+            throw std::invalid_argument("CIGAR: digits at the end");
+        const void* at = std::memchr(letters, text[i], sizeof(letters) - 1);
+        if (!at)
+            throw std::invalid_argument("CIGAR: unknown letter at character " + std::to_string(i));
+        if (digits == 0)
+            throw std::invalid_argument("CIGAR: a letter without a number at character " + std::to_string(i));
+        out.push_back(uint32_t(value << 4) | uint32_t(static_cast<const char*>(at) - letters));
+        i++;
+    }
+}
+
+using NameIds = std::unordered_map<std::string, uint32_t>;
+
+// a column that is a number below 2^32 and nothing else
+uint32_t paf_number(const std::string& column, const char* what)
+{
+    uint64_t value = 0;
+    if (column.empty())
+        throw std::invalid_argument(std::string(what) + " is empty");
+    for (char c : column)
+    {
+        if (c < '0' || c > '9')
+            throw std::invalid_argument(std::string(what) + " is not a number: " + column);
+        value = value * 10 + uint64_t(c - '0');
+        if (value >= (uint64_t(1) << 32))
+            throw std::invalid_argument(std::string(what) + " is 2^32 or more");
+    }
+    return uint32_t(value);
+}
+
+void parse_paf_line(const std::string& line, const NameIds& query_ids, const NameIds& target_ids, int32_t kmer_size,
+                    gwamd_paf& out)
+{
+    std::vector<std::string> columns;
+    for (size_t at = 0;;)
+    {
+        const size_t tab = line.find('\t', at);
+        columns.push_back(line.substr(at, tab == std::string::npos ? tab : tab - at));
+        if (tab == std::string::npos)
+            break;
+        at = tab + 1;
+    }
+    if (columns.size() < 12)
+        throw std::invalid_argument("fewer than 12 columns");
+    const auto query = query_ids.find(columns[0]), target = target_ids.find(columns[5]);
+    if (query == query_ids.end())
+        throw std::invalid_argument("unknown query name " + columns[0]);
+    if (target == target_ids.end())
+        throw std::invalid_argument("unknown target name " + columns[5]);
+    if (columns[4] != "+" && columns[4] != "-")
+        throw std::invalid_argument("the strand is neither + nor -");
+    gwamd_overlap o{};
+    o.query_read_id  = query->second;
+    o.target_read_id = target->second;
+    o.query_start    = paf_number(columns[2], "query start");
+    o.query_end      = paf_number(columns[3], "query end");
+    o.target_start   = paf_number(columns[7], "target start");
+    o.target_end     = paf_number(columns[8], "target end");
+    if (o.query_start > o.query_end || o.target_start > o.target_end)
+        throw std::invalid_argument("start > end");
+    if (o.query_end > paf_number(columns[1], "query length") || o.target_end > paf_number(columns[6], "target length"))
+        throw std::invalid_argument("an end beyond its read's length");
+    o.relative_strand  = static_cast<unsigned char>(columns[4][0]);
+    o.num_residues     = paf_number(columns[9], "column 10") / uint32_t(kmer_size);
+    o.overlap_complete = 0;
+    out.overlaps.push_back(o);
+    for (size_t c = 12; c < columns.size(); c++)
+        if (columns[c].compare(0, 5, "cg:Z:") == 0)
+        {
+            parse_cigar(columns[c].data() + 5, columns[c].size() - 5, out.ops);
+            break;
+        }
+    out.op_offsets.push_back(int64_t(out.ops.size()));
+}
+
+std::unique_ptr<gwamd_paf> parse_paf(const char* text, size_t length, const NameIds& query_ids,
+                                     const NameIds& target_ids, int32_t kmer_size)
+{
+    if (kmer_size < 1)
+        throw std::invalid_argument("kmer_size must be at least 1");
+    auto out       = std::make_unique<gwamd_paf>();
+    int64_t number = 0;
+    for (size_t at = 0; at < length;)
+    {
+        const void* nl   = std::memchr(text + at, '\n', length - at);
+        const size_t end = nl ? size_t(static_cast<const char*>(nl) - text) : length;
+        std::string line(text + at, end - at);
+        at = end + 1;
+        number++;
+        if (!line.empty() && line.back() == '\r')
+            line.pop_back();
+        if (line.empty())
+            continue;
+        try
+        {
+            parse_paf_line(line, query_ids, target_ids, kmer_size, *out);
+        }
+        catch (const std::invalid_argument& e)
+        {
+            throw std::invalid_argument("PAF line " + std::to_string(number) + ": " + e.what());
+        }
+    }
+    return out;
+}
+
+NameIds name_ids(const char* names, const int64_t* offsets, int32_t n, const char* what)
+{
+    gm::check_offsets(offsets, n, what);
+    if (n > 0 && offsets[n] > 0 && !names)
+        throw std::invalid_argument(std::string(what) + " is NULL");
+    NameIds ids;
+    for (int32_t i = 0; i < n; i++)
+        ids.emplace(std::string(names + offsets[i], size_t(offsets[i + 1] - offsets[i])), uint32_t(i));
+    return ids;
+}
+
+NameIds name_ids(const claraparabricks::genomeworks::io::FastaParser& parser)
+{
+    NameIds ids;
+    for (uint32_t i = 0; i < uint32_t(parser.get_num_seqences()); i++)
+        ids.emplace(parser.get_sequence_by_id(i).name, i);
+    return ids;
+}
 
 // qname, qlen, tname, tlen: the name and the length of a read by its id
 template <typename QueryName, typename QueryLen, typename TargetName, typename TargetLen>
@@ -84,12 +240,109 @@ void print_paf(const std::vector<Overlap>& overlaps, const std::vector<std::stri
 }
 
 } // namespace cudamapper
+
+namespace cudapolish
+{
+
+std::vector<uint32_t> cigar_ops(const std::string& text)
+{
+    std::vector<uint32_t> ops;
+    parse_cigar(text.data(), text.size(), ops);
+    return ops;
+}
+
+PafOverlaps read_paf(const std::string& text, const io::FastaParser& query_parser,
+                     const io::FastaParser& target_parser, int32_t kmer_size)
+{
+    const std::unique_ptr<gwamd_paf> paf =
+        parse_paf(text.data(), text.size(), name_ids(query_parser), name_ids(target_parser), kmer_size);
+    PafOverlaps out;
+    for (size_t i = 0; i < paf->overlaps.size(); i++)
+    {
+        out.overlaps.push_back(gm::overlap_as<cudamapper::Overlap>(paf->overlaps[i]));
+        out.cigars.emplace_back(paf->ops.begin() + paf->op_offsets[i], paf->ops.begin() + paf->op_offsets[i + 1]);
+    }
+    return out;
+}
+
+} // namespace cudapolish
 } // namespace genomeworks
 } // namespace claraparabricks
 
 // ---- C ABI ------------------------------------------------------------------
 
 extern "C" {
+
+int32_t gwamd_cigar_ops(const char* text, int64_t text_length, uint32_t* out_or_null, int64_t capacity,
+                        int64_t* num_ops)
+{
+    if (num_ops)
+        *num_ops = 0;
+    return gm::guarded_map([&] {
+        if (!num_ops)
+            throw std::invalid_argument("num_ops is NULL");
+        if (text_length < 0 || (text_length > 0 && !text))
+            throw std::invalid_argument("CIGAR: negative length or NULL text");
+        std::vector<uint32_t> ops;
+        parse_cigar(text, size_t(text_length), ops);
+        *num_ops = int64_t(ops.size());
+        if (out_or_null)
+        {
+            if (capacity < int64_t(ops.size()))
+                throw std::invalid_argument("CIGAR: " + std::to_string(ops.size()) + " ops for a capacity of " +
+                                            std::to_string(capacity));
+            std::copy(ops.begin(), ops.end(), out_or_null);
+        }
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_read_paf(const char* path_or_null, const char* text_or_null, int64_t text_length,
+                       const char* query_names, const int64_t* query_name_offsets, int32_t num_queries,
+                       const char* target_names, const int64_t* target_name_offsets, int32_t num_targets,
+                       int32_t kmer_size, gwamd_paf** handle_out)
+{
+    if (handle_out)
+        *handle_out = nullptr;
+    return gm::guarded_map([&] {
+        if (!handle_out)
+            throw std::invalid_argument("handle_out is NULL");
+        if ((path_or_null != nullptr) == (text_or_null != nullptr))
+            throw std::invalid_argument("read_paf: one of path and text expected");
+        if (text_or_null && text_length < 0)
+            throw std::invalid_argument("read_paf: negative text_length");
+        const NameIds query_ids  = name_ids(query_names, query_name_offsets, num_queries, "query names");
+        const NameIds target_ids = name_ids(target_names, target_name_offsets, num_targets, "target names");
+        std::string file;
+        if (path_or_null)
+        {
+            std::ifstream in(path_or_null, std::ios::binary);
+            if (!in)
+                throw std::runtime_error(std::string("read_paf: cannot open ") + path_or_null);
+            file.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+        }
+        *handle_out = parse_paf(path_or_null ? file.data() : text_or_null,
+                                path_or_null ? file.size() : size_t(text_length), query_ids, target_ids, kmer_size)
+                          .release();
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_paf_get(const gwamd_paf* paf, gwamd_paf_view* view)
+{
+    return gm::guarded_map([&] {
+        if (!paf || !view)
+            throw std::invalid_argument("paf or view is NULL");
+        view->num_overlaps = int64_t(paf->overlaps.size());
+        view->num_ops      = int64_t(paf->ops.size());
+        view->overlaps     = paf->overlaps.data();
+        view->ops          = paf->ops.data();
+        view->op_offsets   = paf->op_offsets.data();
+        return int32_t(0);
+    });
+}
+
+void gwamd_paf_free(gwamd_paf* paf) { delete paf; }
 
 int32_t gwamd_format_paf(const char* query_names, const int64_t* query_name_offsets, const int64_t* query_lengths,
                          int32_t num_queries, const char* target_names, const int64_t* target_name_offsets,

@@ -27,9 +27,7 @@
 //
 // k = t / w is a multiplication by a reciprocal the host prepares (w is the
 // same for every state of a launch).
-#include "polish_windows.hpp"
-
-#include <hip/hip_runtime.h>
+#include "polish_cut.hpp"
 
 namespace gwamd
 {
@@ -38,10 +36,8 @@ namespace polish
 namespace
 {
 
-constexpr uint32_t kThreads      = kCutWaves * 64;
-constexpr uint32_t kOverlapWords = sizeof(OverlapRecord) / sizeof(uint32_t);
-constexpr uint32_t kRecordWords  = sizeof(gwamd_window_segment) / sizeof(uint32_t);
-static_assert(kRecordWords == 8 && kCutTileStates == 64 * 16, "eight words per record, 16 states per lane");
+constexpr uint32_t kThreads = kCutWaves * 64;
+static_assert(kCutTileStates == 64 * 16, "16 states per lane");
 
 struct CutArgs
 {
@@ -58,51 +54,8 @@ struct CutArgs
     uint32_t* records;
     uint32_t* status;
     uint32_t n;
-    // n / w == (hi + ((n - hi) >> sh1)) >> sh2 with hi = mulhi(n, magic), for every 32-bit n
-    uint32_t magic, sh1, sh2;
+    WindowDivisor w;
 };
-
-__device__ inline uint32_t uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-__device__ inline int64_t uniform(int64_t v)
-{
-    return int64_t((uint64_t(uniform(uint32_t(uint64_t(v) >> 32))) << 32) | uniform(uint32_t(v)));
-}
-
-__device__ inline uint32_t window_of(uint32_t t, const CutArgs& a)
-{
-    const uint32_t hi = __umulhi(t, a.magic);
-    return (hi + ((t - hi) >> a.sh1)) >> a.sh2;
-}
-
-// a match or mismatch state: its window and positions
-struct Mark
-{
-    uint32_t k, q, t;
-};
-
-// The two words a state defines in its window's record (words 2..5: q_begin,
-// q_end, t_begin, t_end).  first_of_path: the state opens its window's run in
-// path order; of a Reverse overlap that state has the largest t.
-__device__ inline void store_mark(uint32_t* record0, uint32_t k0, const Mark& m, bool first_of_path, bool reverse)
-{
-    uint32_t* r = record0 + size_t(m.k - k0) * kRecordWords;
-    if (first_of_path)
-    {
-        r[2] = m.q;
-        if (reverse)
-            r[5] = m.t + 1;
-        else
-            r[4] = m.t;
-    }
-    else
-    {
-        r[3] = m.q + 1;
-        if (reverse)
-            r[4] = m.t;
-        else
-            r[5] = m.t + 1;
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void window_segments_kernel(const CutArgs a)
 {
@@ -117,7 +70,7 @@ __global__ __launch_bounds__(kThreads) void window_segments_kernel(const CutArgs
     const uint32_t te       = uniform(overlap[5]);
     const bool reverse      = (uniform(overlap[6]) & 0xff) == '-';
     const uint32_t span_t = te - ts, span_q = qe - qs; // the host has checked start <= end
-    const uint32_t k0     = window_of(ts, a);
+    const uint32_t k0     = window_of(ts, a.w);
     uint32_t* record0     = a.records + size_t(uniform(a.record_base[o])) * kRecordWords;
     const bool backwards  = a.end_to_start != 0;
 
@@ -204,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void window_segments_kernel(const CutArgs
                         Mark m;
                         m.t = reverse ? te - 1 - u : ts + u;
                         m.q = qs + v;
-                        m.k = window_of(m.t, a);
+                        m.k = window_of(m.t, a.w);
                         if (!have_mine)
                             mine_first = m;
                         else if (m.k != mine.k)
@@ -292,15 +245,7 @@ void launch_window_cut(const PathSource& source, const OverlapRecord* d_overlaps
     a.records      = reinterpret_cast<uint32_t*>(d_records);
     a.status       = d_status;
     a.n            = uint32_t(n);
-    // Granlund and Montgomery, division of a 32-bit n by the invariant w:
-    // l = ceil(log2 w), magic = floor(2^32 (2^l - w) / w) + 1
-    const uint32_t w = uint32_t(window_length);
-    uint32_t l       = 0;
-    while ((uint64_t(1) << l) < w)
-        l++;
-    a.magic = uint32_t(((uint64_t(1) << 32) * ((uint64_t(1) << l) - w)) / w + 1);
-    a.sh1   = l < 1 ? l : 1;
-    a.sh2   = l < 1 ? 0 : l - 1;
+    a.w            = window_divisor(uint32_t(window_length));
     const unsigned blocks = unsigned((n + kCutWaves - 1) / kCutWaves);
     window_segments_kernel<<<blocks, kThreads, 0, stream>>>(a);
     GWAMD_HIP_CHECK(hipGetLastError());

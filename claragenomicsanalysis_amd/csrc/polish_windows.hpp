@@ -1,5 +1,6 @@
 // Internal declarations of cudapolish's window cut (polish_windows.hip: the
-// kernel and its launch; polish_windows_host.cpp: the checks, the record
+// kernel on state paths and its launch; polish_cigar.hip: the kernel on CIGAR
+// runs and its launch; polish_windows_host.cpp: the checks, the record
 // layout, the host walk, the one cut launch, the cut on the aligner's device
 // paths through the engines of overlap_engines.hpp, the grouping and the C ABI).
 #pragma once
@@ -51,6 +52,36 @@ void launch_window_cut(const PathSource& source, const OverlapRecord* d_overlaps
                        gwamd_window_segment* d_records, uint32_t* d_status, int64_t n, int32_t window_length,
                        hipStream_t stream);
 
+constexpr int kCigarTileOps           = 64; // CIGAR ops a wave covers in one step: a lane one op
+constexpr uint32_t kCigarOwnCrossings = 2;  // window boundaries inside a match run its own lane walks
+
+// Where the CIGAR kernel (polish_cigar.hip) finds the ops of overlap i of a
+// launch: words [offsets[i], offsets[i + 1]) of ops, each length << 4 | op in
+// BAM numbering, normalised to this project's convention and to path order
+// (normalised_op).  num_ops is the allocation in words.
+struct CigarSource
+{
+    const uint32_t* ops    = nullptr; // device
+    int64_t num_ops        = 0;
+    const int64_t* offsets = nullptr; // device, n + 1 entries
+};
+
+// launch_window_cut for CIGAR runs in place of states: the same records, status and stream order
+void launch_window_cut_cigar(const CigarSource& source, const OverlapRecord* d_overlaps, const uint32_t* d_record_base,
+                             gwamd_window_segment* d_records, uint32_t* d_status, int64_t n, int32_t window_length,
+                             hipStream_t stream);
+
+// Op j of the `count` ops of an overlap as the walks take it: a SAM CIGAR
+// (GWAMD_CIGAR_SAM) has I and D exchanged and, for a '-' overlap, its order reversed.
+inline uint32_t normalised_op(const uint32_t* ops, int64_t count, int64_t j, bool sam, bool reverse)
+{
+    if (!sam)
+        return ops[j];
+    const uint32_t op   = ops[reverse ? count - 1 - j : j];
+    const uint32_t code = op & 15;
+    return code == 1 || code == 2 ? op ^ 3 : op;
+}
+
 // The layout of a call's records: counts per overlap and their exclusive sum
 struct RecordLayout
 {
@@ -71,6 +102,11 @@ void complete_records(gwamd_window_segment* records, uint32_t count, uint32_t in
 // The records of one overlap from its states (start -> end), on the host
 void walk_on_host(gwamd_window_segment* records, uint32_t count, uint32_t index, const OverlapRecord& overlap,
                   const int8_t* states, int64_t num_states, int32_t window_length);
+
+// The records of one overlap from its CIGAR ops in either convention, on the
+// host: a walk over runs and the windows they cross, never over bases
+void walk_cigar_on_host(gwamd_window_segment* records, uint32_t count, uint32_t index, const OverlapRecord& overlap,
+                        const uint32_t* ops, int64_t num_ops, bool sam, int32_t window_length);
 
 // The checked overlaps aligned on resident reads by num_alignment_engines
 // engines (overlap_engines.hpp) and cut on each aligner's stream from its

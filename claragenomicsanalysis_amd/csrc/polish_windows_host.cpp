@@ -2,9 +2,10 @@
 // claraparabricks/genomeworks/cudapolish/windows.hpp): the argument checks, the
 // layout of the records, the walk of one path on the host, the completion of
 // the records the kernel leaves (polish_windows.hip), the one launch of the
-// cut (cut_launch) for paths from the host and for the aligner's device paths
-// (window_segments_resident, on the engines of overlap_engines.hpp), the
-// grouping into cudapoa groups and the C ABI.  Every argument is checked here, before any
+// cut (cut_launch) for paths from the host, for the aligner's device paths
+// (window_segments_resident, on the engines of overlap_engines.hpp) and for
+// CIGAR ops (cut_cigars, polish_cigar.hip; walk_cigar_on_host), the grouping
+// into cudapoa groups and the C ABI.  Every argument is checked here, before any
 // device call, so that the kernel is never given an overlap with start > end or
 // a record range it does not own.
 //
@@ -153,6 +154,63 @@ void walk_on_host(gwamd_window_segment* records, uint32_t count, uint32_t index,
     complete_records(records, count, index, overlap, window_length, fits ? 0 : GWAMD_SEGMENT_BAD_PATH);
 }
 
+void walk_cigar_on_host(gwamd_window_segment* records, uint32_t count, uint32_t index, const OverlapRecord& overlap,
+                        const uint32_t* ops, int64_t num_ops, bool sam, int32_t window_length)
+{
+    const int64_t w      = window_length;
+    const int64_t span_t = int64_t(overlap.target_end) - int64_t(overlap.target_start);
+    const int64_t span_q = int64_t(overlap.query_end) - int64_t(overlap.query_start);
+    const bool reverse   = overlap.relative_strand == '-';
+    const int64_t k0     = overlap.target_start / w;
+    std::memset(static_cast<void*>(records), 0, size_t(count) * sizeof(gwamd_window_segment));
+    int64_t u = 0, v = 0; // at most num_ops * 2^28: no wrap
+    bool fits = true;
+    int64_t open = -1; // the window of the last match state
+    for (int64_t j = 0; j < num_ops && fits; j++)
+    {
+        const uint32_t op    = normalised_op(ops, num_ops, j, sam, reverse);
+        const uint32_t code  = op & 15;
+        const int64_t length = op >> 4;
+        const bool match     = code == 0 || code == 7 || code == 8;
+        if (!match && code != 1 && code != 2)
+            fits = false;
+        else if (match && length > 0)
+        {
+            if (u + length > span_t || v + length > span_q)
+                fits = false;
+            else
+            {
+                // the run's first and last target position, and the windows between them in path order
+                const int64_t t0 = reverse ? int64_t(overlap.target_end) - 1 - u : int64_t(overlap.target_start) + u;
+                const int64_t t1 = reverse ? t0 - (length - 1) : t0 + (length - 1);
+                const int64_t q0 = int64_t(overlap.query_start) + v;
+                const int64_t step = reverse ? -1 : 1;
+                for (int64_t k = t0 / w; k != t1 / w + step; k += step)
+                {
+                    const int64_t lo = std::max(std::min(t0, t1), k * w);
+                    const int64_t hi = std::min(std::max(t0, t1), (k + 1) * w - 1);
+                    gwamd_window_segment& r = records[k - k0];
+                    if (k != open)
+                    {
+                        open      = k;
+                        r.q_begin = uint32_t(q0 + (reverse ? t0 - hi : lo - t0));
+                        (reverse ? r.t_end : r.t_begin) = uint32_t(reverse ? hi + 1 : lo);
+                    }
+                    r.q_end = uint32_t(q0 + (reverse ? t0 - lo : hi - t0) + 1);
+                    (reverse ? r.t_begin : r.t_end) = uint32_t(reverse ? lo : hi + 1);
+                }
+            }
+        }
+        if (fits)
+        {
+            u += code != 2 ? length : 0;
+            v += code != 1 ? length : 0;
+        }
+    }
+    fits = fits && u == span_t && v == span_q;
+    complete_records(records, count, index, overlap, window_length, fits ? 0 : GWAMD_SEGMENT_BAD_PATH);
+}
+
 namespace
 {
 
@@ -208,12 +266,29 @@ struct CutRecords
     std::vector<uint32_t> status;
 };
 
+// the kernel of a source: on state paths or on CIGAR ops
+inline void launch_cut(const PathSource& source, const OverlapRecord* d_overlaps, const uint32_t* d_record_base,
+                       gwamd_window_segment* d_records, uint32_t* d_status, int64_t n, int32_t window_length,
+                       hipStream_t stream)
+{
+    launch_window_cut(source, d_overlaps, d_record_base, d_records, d_status, n, window_length, stream);
+}
+
+inline void launch_cut(const CigarSource& source, const OverlapRecord* d_overlaps, const uint32_t* d_record_base,
+                       gwamd_window_segment* d_records, uint32_t* d_status, int64_t n, int32_t window_length,
+                       hipStream_t stream)
+{
+    launch_window_cut_cigar(source, d_overlaps, d_record_base, d_records, d_status, n, window_length, stream);
+}
+
 // The one launch of the cut: n > 0 checked overlaps in host memory whose paths
-// `source` names on the device.  The overlaps and the record bases go up, the
-// records are zeroed, the kernel runs on stream, records and status come back
-// and complete_records writes the rest; the records of overlap i carry
-// index[i] (null: i).  Returns after the stream has been synchronized.
-CutRecords cut_launch(const PathSource& source, const OverlapRecord* overlaps, int64_t n, const int32_t* index,
+// or CIGAR ops `source` names on the device.  The overlaps and the record
+// bases go up, the records are zeroed, the kernel runs on stream, records and
+// status come back and complete_records writes the rest; the records of
+// overlap i carry index[i] (null: i).  Returns after the stream has been
+// synchronized.
+template <typename Source>
+CutRecords cut_launch(const Source& source, const OverlapRecord* overlaps, int64_t n, const int32_t* index,
                       int32_t window_length, const Budget& budget, hipStream_t stream)
 {
     CutRecords out;
@@ -228,8 +303,7 @@ CutRecords cut_launch(const PathSource& source, const OverlapRecord* overlaps, i
     gm::DevBuf<uint32_t> d_status(size_t(n), budget);
     gm::DevBuf<gwamd_window_segment> d_records(std::max<size_t>(out.records.size(), 1), budget);
     GWAMD_HIP_CHECK(hipMemsetAsync(d_records.data(), 0, d_records.size() * sizeof(gwamd_window_segment), stream));
-    launch_window_cut(source, d_overlaps.data(), d_base.data(), d_records.data(), d_status.data(), n, window_length,
-                      stream);
+    launch_cut(source, d_overlaps.data(), d_base.data(), d_records.data(), d_status.data(), n, window_length, stream);
     if (!out.records.empty())
         GWAMD_HIP_CHECK(hipMemcpyAsync(out.records.data(), d_records.data(),
                                        out.records.size() * sizeof(gwamd_window_segment), hipMemcpyDeviceToHost,
@@ -306,6 +380,61 @@ void check_states(const std::vector<OverlapRecord>& overlaps, const int8_t* stat
     }
     if (n > 0 && state_offsets[n] > 0 && !states)
         throw std::invalid_argument("states is NULL");
+}
+
+bool is_sam(int32_t convention)
+{
+    if (convention != GWAMD_CIGAR_GENOMEWORKS && convention != GWAMD_CIGAR_SAM)
+        throw std::invalid_argument("convention must be GWAMD_CIGAR_GENOMEWORKS or GWAMD_CIGAR_SAM, got " +
+                                    std::to_string(convention));
+    return convention == GWAMD_CIGAR_SAM;
+}
+
+void check_cigars(int64_t n, const uint32_t* ops, const int64_t* op_offsets)
+{
+    if (n > 0 && !op_offsets)
+        throw std::invalid_argument("op_offsets is NULL");
+    for (int64_t i = 0; i < n; i++)
+        if (op_offsets[i] < 0 || op_offsets[i] > op_offsets[i + 1])
+            throw std::invalid_argument("op_offsets must be non-decreasing");
+    if (n > 0 && op_offsets[n] > op_offsets[0] && !ops)
+        throw std::invalid_argument("ops is NULL");
+}
+
+// The cut of checked overlaps from their CIGAR ops in host memory: the ops
+// [op_offsets[0], op_offsets[n]) go up as they are, or normalised in one pass
+// when they are SAM's; no run is expanded.
+void cut_cigars(const std::vector<OverlapRecord>& overlaps, const uint32_t* ops, const int64_t* op_offsets, bool sam,
+                int32_t window_length, const Budget& budget, std::vector<gwamd_window_segment>& out)
+{
+    const size_t n      = overlaps.size();
+    const int64_t first = op_offsets[0], total = op_offsets[n] - first;
+    std::vector<int64_t> offsets(n + 1);
+    for (size_t i = 0; i <= n; i++)
+        offsets[i] = op_offsets[i] - first;
+    std::vector<uint32_t> normalised;
+    if (sam)
+    {
+        normalised.resize(size_t(total));
+        for (size_t i = 0; i < n; i++)
+        {
+            const int64_t count = offsets[i + 1] - offsets[i];
+            for (int64_t j = 0; j < count; j++)
+                normalised[size_t(offsets[i] + j)] = normalised_op(ops + first + offsets[i], count, j, true,
+                                                                   overlaps[i].relative_strand == '-');
+        }
+    }
+    gm::DevBuf<uint32_t> d_ops(size_t(std::max<int64_t>(total, 1)), budget);
+    gm::DevBuf<int64_t> d_offsets;
+    if (total > 0)
+        GWAMD_HIP_CHECK(hipMemcpyAsync(d_ops.data(), sam ? normalised.data() : ops + first,
+                                       size_t(total) * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
+    upload(d_offsets, offsets.data(), n + 1, budget, nullptr);
+    CigarSource source;
+    source.ops     = d_ops.data();
+    source.num_ops = total;
+    source.offsets = d_offsets.data();
+    out = cut_launch(source, overlaps.data(), int64_t(n), nullptr, window_length, budget, nullptr).records;
 }
 
 } // namespace
@@ -555,6 +684,42 @@ std::vector<WindowSegment> window_segments(DefaultDeviceAllocator /*allocator*/,
     return as_segments(out);
 }
 
+std::vector<WindowSegment> window_segments_cigar(DefaultDeviceAllocator allocator,
+                                                 const std::vector<cudamapper::Overlap>& overlaps,
+                                                 const std::vector<std::vector<uint32_t>>& cigars,
+                                                 int32_t window_length, CigarConvention convention)
+{
+    if (cigars.size() != overlaps.size())
+        throw std::invalid_argument("window_segments_cigar: one CIGAR per overlap expected");
+    const bool sam                               = gp::is_sam(int32_t(convention));
+    const std::vector<gm::OverlapRecord> records = as_records(overlaps);
+    std::vector<int64_t> offsets(cigars.size() + 1, 0);
+    for (size_t i = 0; i < cigars.size(); i++)
+        offsets[i + 1] = offsets[i] + int64_t(cigars[i].size());
+    std::vector<uint32_t> ops;
+    ops.reserve(size_t(offsets.back()));
+    for (const std::vector<uint32_t>& c : cigars)
+        ops.insert(ops.end(), c.begin(), c.end());
+    (void)gp::plan_records(records.data(), int64_t(records.size()), window_length);
+    std::vector<gwamd_window_segment> out;
+    if (!records.empty())
+        gp::cut_cigars(records, ops.data(), offsets.data(), sam, window_length, allocator.budget(), out);
+    return as_segments(out);
+}
+
+std::vector<WindowSegment> window_segments_cigar_host(const cudamapper::Overlap& overlap,
+                                                      const std::vector<uint32_t>& cigar, int32_t window_length,
+                                                      CigarConvention convention, uint32_t overlap_index)
+{
+    const bool sam                               = gp::is_sam(int32_t(convention));
+    const std::vector<gm::OverlapRecord> records = as_records({overlap});
+    const gp::RecordLayout layout                = gp::plan_records(records.data(), 1, window_length);
+    std::vector<gwamd_window_segment> out(static_cast<size_t>(layout.total()));
+    gp::walk_cigar_on_host(out.data(), uint32_t(out.size()), overlap_index, records[0], cigar.data(),
+                           int64_t(cigar.size()), sam, window_length);
+    return as_segments(out);
+}
+
 Windows build_windows(const io::FastaParser& targets, const io::FastaParser& queries,
                       const std::vector<cudamapper::Overlap>& overlaps, const std::vector<WindowSegment>& segments,
                       int32_t window_length, int32_t max_sequences_per_window)
@@ -639,6 +804,57 @@ int32_t gwamd_window_segments_host(const gwamd_overlap* overlap, const int8_t* s
         std::vector<gwamd_window_segment> result(static_cast<size_t>(layout.total()));
         gp::walk_on_host(result.data(), uint32_t(result.size()), overlap_index, records[0], states, num_states,
                          window_length);
+        gm::hand_over(result, out, num_out);
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_window_segments_cigar(const gwamd_overlap* overlaps, int64_t n, const uint32_t* ops,
+                                    const int64_t* op_offsets, int32_t convention, int32_t window_length,
+                                    int32_t device_id, gwamd_device_allocator* allocator_or_null,
+                                    gwamd_window_segment** out, int64_t* num_out)
+{
+    gp::clear_outputs(out, num_out);
+    return gm::guarded_map([&] {
+        if (!out || !num_out)
+            throw std::invalid_argument("out or num_out is NULL");
+        if (device_id < 0)
+            throw std::invalid_argument("device_id must not be negative");
+        const bool sam = gp::is_sam(convention);
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        gp::check_cigars(n, ops, op_offsets);
+        (void)gp::plan_records(records.data(), n, window_length);
+        if (n == 0)
+            return int32_t(0);
+        gwamd::host::ScopedDevice dev(device_id);
+        std::vector<gwamd_window_segment> result;
+        gp::cut_cigars(records, ops, op_offsets, sam, window_length,
+                       allocator_or_null ? allocator_or_null->alloc.budget() : nullptr, result);
+        gm::hand_over(result, out, num_out);
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_window_segments_cigar_host(const gwamd_overlap* overlap, const uint32_t* ops, int64_t num_ops,
+                                         int32_t convention, int32_t window_length, uint32_t overlap_index,
+                                         gwamd_window_segment** out, int64_t* num_out)
+{
+    gp::clear_outputs(out, num_out);
+    return gm::guarded_map([&] {
+        if (!out || !num_out)
+            throw std::invalid_argument("out or num_out is NULL");
+        if (!overlap)
+            throw std::invalid_argument("overlap is NULL");
+        const bool sam = gp::is_sam(convention);
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlap, 1, records);
+        if (num_ops < 0 || (num_ops > 0 && !ops))
+            throw std::invalid_argument("ops: negative count or NULL");
+        const gp::RecordLayout layout = gp::plan_records(records.data(), 1, window_length);
+        std::vector<gwamd_window_segment> result(static_cast<size_t>(layout.total()));
+        gp::walk_cigar_on_host(result.data(), uint32_t(result.size()), overlap_index, records[0], ops, num_ops, sam,
+                               window_length);
         gm::hand_over(result, out, num_out);
         return int32_t(0);
     });

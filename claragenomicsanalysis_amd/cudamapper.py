@@ -328,6 +328,20 @@ def format_paf(overlaps, cigars, query_reads, target_reads, kmer_size):
     return _take(L, h)[0]
 
 
+def read_paf(path_or_text, query_names, target_names, kmer_size=1):
+    """(overlaps, cigars) of a PAF file, or of PAF text (anything with a tab or
+    a newline in it), the way back from format_paf and the input of
+    cudapolish.polish(..., cigars=): one Overlap per non-empty line, its read
+    ids the indices of columns 1 and 6 in query_names / target_names,
+    num_residues column 10 // kmer_size, and per overlap the ops of its cg:Z:
+    tag as a np.uint32 array (cudapolish.cigar_ops; empty without the tag).
+    ValueError, with the line's number, for an unknown name, fewer than 12
+    columns, a strand other than + and -, start > end and an end beyond the
+    read's length in column 2 or 7."""
+    from .cudapolish import _read_paf
+    return _read_paf(path_or_text, query_names, target_names, kmer_size)
+
+
 def read_fasta(path, min_sequence_length=0, shuffle=True):
     """(name, sequence) records as io::create_kseq_fasta_parser holds them
     (kseqpp_fasta_parser.cpp:31-72): shorter records dropped, shuffled with

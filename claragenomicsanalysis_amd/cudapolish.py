@@ -7,6 +7,13 @@ overlaps on resident reads and cuts them where the aligner leaves its paths on
 the device, build_windows groups the pieces into POA windows, and polish runs
 targets + reads + overlaps -> polished targets end to end.
 
+Overlaps that already carry CIGARs (cudamapper.align_overlaps, cudamapper -a,
+minimap2 -c through cudamapper.read_paf) need no second alignment:
+window_segments_cigar cuts them from their runs on the GPU, in the
+"genomeworks" or the "sam" convention, without expanding a run to states, and
+polish(..., cigars=) takes that route.  cigar_ops turns CIGAR text into the
+packed ops (length << 4 | op, BAM numbering) the cut works on.
+
 Path states are AlignmentState values, start -> end: 0 match and 1 mismatch
 advance both sequences, 3 (deletion) advances ONLY THE QUERY and 2 (insertion)
 ONLY THE TARGET, the reference's convention and the opposite of SAM's I / D.
@@ -57,6 +64,12 @@ class _WindowsView(C.Structure):
                 ("sequence_overlap", C.c_void_p), ("sequence_t_begin", C.c_void_p), ("sequence_t_end", C.c_void_p)]
 
 
+class _PafView(C.Structure):
+    """gwamd_paf_view."""
+    _fields_ = [("num_overlaps", C.c_int64), ("num_ops", C.c_int64), ("overlaps", C.c_void_p), ("ops", C.c_void_p),
+                ("op_offsets", C.c_void_p)]
+
+
 def _declare(L):
     vp, i32, i64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32
     P = C.POINTER
@@ -66,6 +79,18 @@ def _declare(L):
     L.gwamd_window_segments_host.argtypes = [vp, vp, i64, i32, u32, P(vp), P(i64)]
     L.gwamd_window_segments_resident.restype = i32
     L.gwamd_window_segments_resident.argtypes = [vp, vp, vp, i32, i32, i32, P(vp), P(i64)]
+    L.gwamd_window_segments_cigar.restype = i32
+    L.gwamd_window_segments_cigar.argtypes = [vp, i64, vp, vp, i32, i32, i32, vp, P(vp), P(i64)]
+    L.gwamd_window_segments_cigar_host.restype = i32
+    L.gwamd_window_segments_cigar_host.argtypes = [vp, vp, i64, i32, i32, u32, P(vp), P(i64)]
+    L.gwamd_cigar_ops.restype = i32
+    L.gwamd_cigar_ops.argtypes = [C.c_char_p, i64, vp, i64, P(i64)]
+    L.gwamd_read_paf.restype = i32
+    L.gwamd_read_paf.argtypes = [C.c_char_p, C.c_char_p, i64, C.c_char_p, vp, i32, C.c_char_p, vp, i32, i32, P(vp)]
+    L.gwamd_paf_get.restype = i32
+    L.gwamd_paf_get.argtypes = [vp, P(_PafView)]
+    L.gwamd_paf_free.restype = None
+    L.gwamd_paf_free.argtypes = [vp]
     L.gwamd_window_segments_free.restype = None
     L.gwamd_window_segments_free.argtypes = [vp]
     L.gwamd_internal_window_segments_strided.restype = i32
@@ -165,6 +190,130 @@ def window_segments_resident(overlaps, query_reads, target_reads, window_length,
     _check(L.gwamd_window_segments_resident(*handles, arr, len(overlaps), int(window_length),
                                             int(num_alignment_engines), C.byref(p), C.byref(n)))
     return _take_segments(L, p, n)
+
+
+CIGAR_CONVENTIONS = {"genomeworks": 0, "sam": 1}  # GWAMD_CIGAR_*
+CIGAR_LETTERS = "MIDNSHP=X"  # BAM numbering; the cut takes M, I, D, = and X
+
+
+def cigar_ops(text):
+    """CIGAR text such as "12M3I4D5=1X" as a np.uint32 array of length << 4 |
+    op (M 0, I 1, D 2, = 7, X 8; lengths below 2^28).  ValueError for a letter
+    without a number, an unknown letter, a length of 2^28 or more and digits
+    at the end; "" gives no op."""
+    L = load_library()
+    data = text.encode() if isinstance(text, str) else bytes(text)
+    out = np.zeros(len(data) // 2 + 1, np.uint32)
+    n = C.c_int64()
+    _check(L.gwamd_cigar_ops(data, len(data), out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+    return out[:n.value]
+
+
+def _convention(name):
+    if name not in CIGAR_CONVENTIONS:
+        raise ValueError("convention must be one of %s, got %r" % (sorted(CIGAR_CONVENTIONS), name))
+    return CIGAR_CONVENTIONS[name]
+
+
+def _ops(cigar):
+    if isinstance(cigar, (str, bytes)):
+        return cigar_ops(cigar)
+    return np.ascontiguousarray(cigar, dtype=np.uint32)
+
+
+def _pack_cigars(cigars):
+    """(ops, offsets) of CIGARs given as text or as op arrays."""
+    if cigars and all(isinstance(c, str) for c in cigars):
+        # The texts joined are one CIGAR text whose ops are theirs in order, provided that none ends in
+        # digits: one call parses them all, and the letters counted up to each text's end are its ops.
+        data = "".join(cigars).encode()
+        buf = np.frombuffer(data, np.uint8)
+        ends = np.cumsum([len(c) for c in cigars])
+        letters = np.concatenate([[0], np.cumsum((buf < 48) | (buf > 57))])
+        last = buf[np.maximum(ends - 1, 0)] if len(buf) else np.zeros(len(ends), np.uint8)
+        ops = np.zeros(int(letters[-1]) + 1, np.uint32)
+        n = C.c_int64()
+        if not np.any((last >= 48) & (last <= 57) & (np.diff(ends, prepend=0) > 0)) and \
+                load_library().gwamd_cigar_ops(data, len(data), ops.ctypes.data_as(C.c_void_p), len(ops) - 1,
+                                               C.byref(n)) == 0 and n.value == len(ops) - 1:
+            offsets = np.zeros(len(cigars) + 1, np.int64)
+            offsets[1:] = letters[ends]
+            return ops, offsets
+        # a malformed text: parsed one by one below, which names it
+    arrays = [_ops(c) for c in cigars]
+    offsets = np.zeros(len(arrays) + 1, np.int64)
+    if arrays:
+        np.cumsum([len(a) for a in arrays], out=offsets[1:])
+    ops = np.concatenate(arrays + [np.zeros(1, np.uint32)])
+    return ops, offsets
+
+
+def window_segments_cigar(overlaps, cigars, window_length, convention="genomeworks", device_id=0, allocator=None):
+    """window_segments for overlaps that carry CIGARs: the records of the
+    state paths the CIGARs stand for, cut by one kernel launch over the runs
+    (no run is expanded, only the ops go up).
+
+    cigars[i]: the CIGAR of overlap i, as text or as ops (cigar_ops).
+    convention: "genomeworks" for what align_overlaps and cudamapper -a emit (I
+    advances only the target, D only the query; a '-' overlap runs along the
+    query and the reverse-complemented target region), "sam" for minimap2's
+    PAF and SAM (I only the query, D only the target; '-' runs along the target
+    and the reverse-complemented query region).  An op other than M, I, D, =
+    and X, and advances that are not the overlap's two spans, give BAD_PATH
+    records; ValueError as window_segments, and for an unknown convention."""
+    L = load_library()
+    if len(cigars) != len(overlaps):
+        raise ValueError("one CIGAR per overlap expected")
+    code = _convention(convention)
+    arr = _overlap_array(overlaps)
+    ops, offsets = _pack_cigars(cigars)
+    p, n = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_window_segments_cigar(arr, len(overlaps), ops.ctypes.data_as(C.c_void_p),
+                                         offsets.ctypes.data_as(C.c_void_p), code, int(window_length),
+                                         int(device_id), allocator._handle if allocator is not None else None,
+                                         C.byref(p), C.byref(n)))
+    return _take_segments(L, p, n)
+
+
+def window_segments_cigar_host(overlap, cigar, window_length, convention="genomeworks", overlap_index=0):
+    """The same walk over the runs of one overlap on the host, without a GPU."""
+    L = load_library()
+    code = _convention(convention)
+    arr = _overlap_array([overlap])
+    ops = np.concatenate([_ops(cigar), np.zeros(1, np.uint32)])
+    p, n = C.c_void_p(), C.c_int64()
+    _check(L.gwamd_window_segments_cigar_host(arr, ops.ctypes.data_as(C.c_void_p), len(ops) - 1, code,
+                                              int(window_length), int(overlap_index), C.byref(p), C.byref(n)))
+    return _take_segments(L, p, n)
+
+
+def _read_paf(path_or_text, query_names, target_names, kmer_size):
+    """cudamapper.read_paf: (overlaps, cigars) over gwamd_read_paf."""
+    import os
+
+    from .cudamapper import Overlap
+    L = load_library()
+    qn, qno = _pack(query_names)
+    tn, tno = _pack(target_names)
+    text = path_or_text.encode() if isinstance(path_or_text, str) else bytes(path_or_text)
+    # PAF text has tabs or is empty; anything else names a file
+    is_text = not text or b"\t" in text or b"\n" in text
+    if isinstance(path_or_text, os.PathLike):
+        text, is_text = os.fsencode(path_or_text), False
+    h = C.c_void_p()
+    _check(L.gwamd_read_paf(None if is_text else text, text if is_text else None, len(text) if is_text else 0,
+                            qn, qno, len(query_names), tn, tno, len(target_names), int(kmer_size), C.byref(h)))
+    try:
+        v = _PafView()
+        _check(L.gwamd_paf_get(h, C.byref(v)))
+        raw = _array(v.overlaps, v.num_overlaps * C.sizeof(Overlap), np.uint8).tobytes()
+        overlaps = [Overlap.from_buffer_copy(raw, i * C.sizeof(Overlap)) for i in range(v.num_overlaps)]
+        ops = _array(v.ops, v.num_ops, np.uint32)
+        offsets = _array(v.op_offsets, v.num_overlaps + 1, np.int64)
+        cigars = [ops[offsets[i]:offsets[i + 1]].copy() for i in range(v.num_overlaps)]
+        return overlaps, cigars
+    finally:
+        L.gwamd_paf_free(h)
 
 
 def _window_segments_strided(overlaps, paths, path_lengths, stride, window_length):
@@ -330,7 +479,7 @@ def _slice_weights(qualities, sl):
 def polish(targets, queries, overlaps, window_length=500, max_sequences_per_window=100, banded=True,
            band_width=256, scores=(8, -6, -8), num_alignment_engines=1, device_id=0, max_gpu_mem=None,
            return_windows=False, device_windows=False, query_qualities=None, target_qualities=None,
-           quality_threshold=10.0, trim=False):
+           quality_threshold=10.0, trim=False, cigars=None, cigar_convention="genomeworks"):
     """Polished targets from targets, reads and overlaps (query = read, target =
     target): the overlaps are aligned and cut on the GPU
     (window_segments_resident), grouped into windows (build_windows) and run
@@ -351,6 +500,12 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
     (build_window_slices).  trim: every consensus is cut to racon's coverage
     rule (trim_consensus) before it is joined.
 
+    cigars: one CIGAR per overlap (text or ops, in cigar_convention; what
+    cudamapper.align_overlaps, cudamapper -a or cudamapper.read_paf give),
+    ValueError for another count.  The segments then come from
+    window_segments_cigar: the overlaps are not aligned again and no aligner
+    is created; everything after the segments is the same.
+
     Returns (polished, stats); stats counts "windows", "backbone_by_rule"
     (fewer than three sequences), "backbone_by_status", "dropped_by_cap",
     "dropped_by_quality", "trimmed_bases" and carries the "max_sequence_size"
@@ -365,6 +520,10 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
     targets = [t[1] if isinstance(t, tuple) else t for t in targets]
     queries = [q[1] if isinstance(q, tuple) else q for q in queries]
     resident = bool(device_windows) or query_qualities is not None or target_qualities is not None
+    if cigars is not None:
+        if len(cigars) != len(overlaps):
+            raise ValueError("%d CIGARs for %d overlaps" % (len(cigars), len(overlaps)))
+        _convention(cigar_convention)
     with torch.cuda.device(device_id):
         q_reads = DeviceReads(queries, device_id=device_id, qualities=query_qualities)
         try:
@@ -374,7 +533,10 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
             raise
     try:
         with torch.cuda.device(device_id):
-            segments = window_segments_resident(overlaps, q_reads, t_reads, window_length, num_alignment_engines)
+            if cigars is not None:
+                segments = window_segments_cigar(overlaps, cigars, window_length, cigar_convention, device_id)
+            else:
+                segments = window_segments_resident(overlaps, q_reads, t_reads, window_length, num_alignment_engines)
         by_quality = 0
         if resident:
             windows, dropped, by_quality = build_window_slices(

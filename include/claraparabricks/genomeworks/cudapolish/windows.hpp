@@ -9,6 +9,10 @@
 // insertion (2) ONLY THE TARGET (alignment_impl.cpp:94-103), the opposite of
 // SAM's I / D.  The semantics of a record are in include/gwamd_polish.h.
 //
+// Overlaps that already carry CIGARs (cudamapper -a, align_overlaps, minimap2
+// -c) are cut from their runs by window_segments_cigar, without an alignment
+// and without expanding a run; read_paf reads them from PAF text.
+//
 // add_poa_group_resident adds a window to a cudapoa batch as slices of reads
 // that are already on the device (cudamapper::DeviceReads), with base qualities
 // as weights when the reads carry them; the grouping into slices, racon's
@@ -27,6 +31,7 @@
 #include <claraparabricks/genomeworks/utils/allocator.hpp>
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace claraparabricks
@@ -76,6 +81,49 @@ std::vector<WindowSegment> window_segments(DefaultDeviceAllocator allocator,
                                            const cudamapper::DeviceReads& query_reads,
                                            const cudamapper::DeviceReads& target_reads, int32_t window_length,
                                            int32_t num_alignment_engines);
+
+/// What I and D mean in a CIGAR and how a Reverse overlap is laid out
+/// (GWAMD_CIGAR_*, include/gwamd_polish.h)
+enum class CigarConvention : int32_t
+{
+    genomeworks = 0, ///< align_overlaps, cudamapper -a: I advances only the target, D only the query;
+                     ///< Reverse: query forward, target region reverse-complemented
+    sam         = 1  ///< minimap2 PAF, SAM: I advances only the query, D only the target;
+                     ///< Reverse: target forward, query region reverse-complemented
+};
+
+/// CIGAR text such as 12M3I4D5=1X as words length << 4 | op (BAM numbering).
+/// Throws std::invalid_argument for a letter without a number, an unknown
+/// letter, a length of 2^28 or more and digits at the end.
+std::vector<uint32_t> cigar_ops(const std::string& text);
+
+/// window_segments for overlaps that carry CIGARs (cigars[i]: the ops of
+/// overlap i): the records of the state paths the CIGARs stand for, cut by one
+/// kernel launch over the runs, none of them expanded.  An op other than M, I,
+/// D, = and X, and advances that are not the overlap's two spans, make the
+/// overlap's records bad_path.
+std::vector<WindowSegment> window_segments_cigar(DefaultDeviceAllocator allocator,
+                                                 const std::vector<cudamapper::Overlap>& overlaps,
+                                                 const std::vector<std::vector<uint32_t>>& cigars,
+                                                 int32_t window_length,
+                                                 CigarConvention convention = CigarConvention::genomeworks);
+
+/// The same walk over the runs of one overlap on the host
+std::vector<WindowSegment> window_segments_cigar_host(const cudamapper::Overlap& overlap,
+                                                      const std::vector<uint32_t>& cigar, int32_t window_length,
+                                                      CigarConvention convention = CigarConvention::genomeworks,
+                                                      uint32_t overlap_index                                    = 0);
+
+/// Overlaps and the ops of their cg:Z: tags (none for a line without one) read
+/// from PAF text, as gwamd_read_paf reads it: read ids by name among the
+/// parsers' reads, num_residues = column 10 / kmer_size.
+struct PafOverlaps
+{
+    std::vector<cudamapper::Overlap> overlaps;
+    std::vector<std::vector<uint32_t>> cigars;
+};
+PafOverlaps read_paf(const std::string& text, const io::FastaParser& query_parser,
+                     const io::FastaParser& target_parser, int32_t kmer_size = 1);
 
 /// One cudapoa group per window of every target, in target then window order.
 struct Windows

@@ -85,6 +85,83 @@ int32_t gwamd_window_segments_resident(const gwamd_device_reads* query_reads, co
 
 void gwamd_window_segments_free(gwamd_window_segment* segments);
 
+/* ---- the cut from CIGAR runs ------------------------------------------------------
+ *
+ * A CIGAR is an array of 32-bit words length << 4 | op, op in BAM numbering: M 0, I 1, D 2,
+ * = 7, X 8; the length is below 2^28, and a length of 0 contributes nothing.  The records of
+ * an overlap and its CIGAR are those of the state path the CIGAR stands for: the CIGAR is
+ * normalised to GWAMD_CIGAR_GENOMEWORKS, every run of length n written as n states (M, = and
+ * X: 0 or 1, which the records do not tell apart; I: 2; D: 3) and the definition at the top of
+ * this file applied.  No entry point expands a run: the work is per run and per window
+ * boundary.  Any other op code (N, S, H, P, 9..15), of any length, makes the overlap a misfit
+ * (GWAMD_SEGMENT_BAD_PATH), as do advances that are not exactly the overlap's two spans,
+ * whatever they sum to (the sums do not wrap); the call does not fail.
+ *
+ * GWAMD_CIGAR_GENOMEWORKS: what gwamd_align_overlaps and cudamapper -a emit.  I advances only
+ * the target, D only the query; for a '-' overlap the ops run along the query forward and the
+ * reverse complement of the target region.
+ * GWAMD_CIGAR_SAM: minimap2's PAF and SAM.  I advances only the query, D only the target; for
+ * a '-' overlap the ops run along the target forward and the reverse complement of the query
+ * region (t = target_start + u, q = query_end - 1 - v).  Normalised by exchanging I and D
+ * and, for '-', reversing the order of the ops: the same records. */
+#define GWAMD_CIGAR_GENOMEWORKS 0
+#define GWAMD_CIGAR_SAM 1
+
+/* gwamd_window_segments for n overlaps whose CIGARs are ops[op_offsets[i], op_offsets[i + 1]):
+ * one kernel launch over the runs.  Errors, ownership and the checks of the overlaps,
+ * window_length, device_id and the outputs as there; besides, GWAMD_E_INVALID_ARGUMENT for a
+ * convention other than the two above, op_offsets that are negative or fall, and NULL ops with
+ * an op behind it.  Every argument is checked before any device call; n == 0 makes none. */
+int32_t gwamd_window_segments_cigar(const gwamd_overlap* overlaps, int64_t n, const uint32_t* ops,
+                                    const int64_t* op_offsets, int32_t convention, int32_t window_length,
+                                    int32_t device_id, struct gwamd_device_allocator* allocator_or_null,
+                                    gwamd_window_segment** out, int64_t* num_out);
+
+/* The same walk over runs for one overlap on the host; the records carry overlap_index. */
+int32_t gwamd_window_segments_cigar_host(const gwamd_overlap* overlap, const uint32_t* ops, int64_t num_ops,
+                                         int32_t convention, int32_t window_length, uint32_t overlap_index,
+                                         gwamd_window_segment** out, int64_t* num_out);
+
+/* CIGAR text such as 12M3I4D5=1X as ops: *num_ops receives their number, and with
+ * out_or_null they are written to out_or_null[0, *num_ops).  Every letter of MIDNSHP=X is
+ * taken (BAM numbering); empty text gives 0 ops.  GWAMD_E_INVALID_ARGUMENT: a letter without
+ * a number, an unknown letter, a length of 2^28 or more, digits at the end, NULL text with
+ * text_length > 0, NULL num_ops, and a capacity below the number of ops (which *num_ops then
+ * still holds). */
+int32_t gwamd_cigar_ops(const char* text, int64_t text_length, uint32_t* out_or_null, int64_t capacity,
+                        int64_t* num_ops);
+
+/* Overlaps and their CIGARs read from PAF text: the file path_or_null, or text_or_null of
+ * text_length bytes (exactly one of the two).  Every non-empty line is one overlap, in order.
+ * The read ids are the indices of columns 1 and 6 among the names (names[offsets[i],
+ * offsets[i + 1]), as gwamd_format_paf takes them; of two equal names the first), the
+ * positions come from columns 3-4 and 8-9, the strand from column 5, num_residues is column 10
+ * divided by kmer_size and overlap_complete 0.  The ops are those of the cg:Z: tag, wherever
+ * it stands among the tags; a line without one has none.
+ * GWAMD_E_INVALID_ARGUMENT, with the number of the line (from 1) in gwamd_last_error(): a
+ * name that is not among the names, fewer than 12 columns, a number that is not one, a strand
+ * other than + and -, start > end, an end beyond the length in column 2 or 7, a CIGAR
+ * gwamd_cigar_ops refuses; and kmer_size < 1, both or neither of path and text.  A file that
+ * cannot be read is GWAMD_E_RUNTIME. */
+typedef struct gwamd_paf gwamd_paf;
+
+typedef struct gwamd_paf_view
+{
+    int64_t num_overlaps;
+    int64_t num_ops;
+    const gwamd_overlap* overlaps;
+    const uint32_t* ops;       /* num_ops */
+    const int64_t* op_offsets; /* num_overlaps + 1 */
+} gwamd_paf_view;
+
+int32_t gwamd_read_paf(const char* path_or_null, const char* text_or_null, int64_t text_length,
+                       const char* query_names, const int64_t* query_name_offsets, int32_t num_queries,
+                       const char* target_names, const int64_t* target_name_offsets, int32_t num_targets,
+                       int32_t kmer_size, gwamd_paf** handle_out);
+/* Pointers into the handle, valid until gwamd_paf_free. */
+int32_t gwamd_paf_get(const gwamd_paf* paf, gwamd_paf_view* view);
+void gwamd_paf_free(gwamd_paf* paf);
+
 /* POA windows (host only).  Target r of length T has windows k = 0 .. ceil(T / w) - 1 with
  * backbone target[k w, min((k + 1) w, T)) as their first sequence.  A segment is kept when it has
  * no EMPTY, BAD_PATH or NOT_ALIGNED flag and (q_end - q_begin) * 50 >= w (racon's 2 % rule); kept

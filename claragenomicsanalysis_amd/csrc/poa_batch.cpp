@@ -898,11 +898,9 @@ int32_t max_sequence_size(const Batch* batch) { return static_cast<const PoaBatc
 namespace
 {
 
-claraparabricks::genomeworks::cudapoa::StatusType
-add_resident_checked(claraparabricks::genomeworks::cudapoa::PoaBatch& batch,
-                     std::vector<claraparabricks::genomeworks::cudapoa::StatusType>& per_seq_status,
-                     const std::vector<const gwamd::mapper::DeviceReads*>& sets, const gwamd_read_slice* slices,
-                     int32_t n)
+void check_resident_slices(const claraparabricks::genomeworks::cudapoa::PoaBatch& batch,
+                           const std::vector<const gwamd::mapper::DeviceReads*>& sets, const gwamd_read_slice* slices,
+                           int64_t n)
 {
     if (n < 0)
         throw std::invalid_argument("the number of slices must not be negative");
@@ -911,7 +909,7 @@ add_resident_checked(claraparabricks::genomeworks::cudapoa::PoaBatch& batch,
     for (size_t s = 0; s < sets.size(); s++)
         if (!sets[s])
             throw std::invalid_argument("set " + std::to_string(s) + " is NULL");
-    for (int32_t i = 0; i < n; i++)
+    for (int64_t i = 0; i < n; i++)
     {
         const gwamd_read_slice& sl = slices[i];
         const std::string which    = "slice " + std::to_string(i);
@@ -926,7 +924,57 @@ add_resident_checked(claraparabricks::genomeworks::cudapoa::PoaBatch& batch,
             throw std::invalid_argument(which + ": its reads are on device " + std::to_string(set.device_id) +
                                         ", the batch is on device " + std::to_string(batch.device_id()));
     }
+}
+
+claraparabricks::genomeworks::cudapoa::StatusType
+add_resident_checked(claraparabricks::genomeworks::cudapoa::PoaBatch& batch,
+                     std::vector<claraparabricks::genomeworks::cudapoa::StatusType>& per_seq_status,
+                     const std::vector<const gwamd::mapper::DeviceReads*>& sets, const gwamd_read_slice* slices,
+                     int32_t n)
+{
+    check_resident_slices(batch, sets, slices, n);
     return batch.add_poa_group_resident(per_seq_status, sets.data(), slices, n);
+}
+
+// Many groups in one call (gwamd_poa_add_poa_groups_resident): every slice is
+// checked before the first group is added; then group after group as the single
+// call adds it, up to the first that the batch has no room for.  Returns the
+// number of groups consumed.  group_status and per_seq_status (one entry per
+// slice) are written for those groups only.
+int32_t add_resident_groups_checked(claraparabricks::genomeworks::cudapoa::PoaBatch& batch,
+                                    const std::vector<const gwamd::mapper::DeviceReads*>& sets,
+                                    const gwamd_read_slice* slices, const int32_t* group_counts, int32_t num_groups,
+                                    int32_t* group_status, int32_t* per_seq_status)
+{
+    using claraparabricks::genomeworks::cudapoa::StatusType;
+    if (num_groups < 0)
+        throw std::invalid_argument("the number of groups must not be negative");
+    if (num_groups > 0 && (!group_counts || !group_status))
+        throw std::invalid_argument("group_counts or group_status is NULL");
+    int64_t total = 0;
+    for (int32_t g = 0; g < num_groups; g++)
+    {
+        if (group_counts[g] < 0)
+            throw std::invalid_argument("group " + std::to_string(g) + ": negative number of slices");
+        total += group_counts[g];
+    }
+    if (total > 0 && !per_seq_status)
+        throw std::invalid_argument("per_seq_status is NULL");
+    check_resident_slices(batch, sets, slices, total);
+    std::vector<StatusType> st;
+    int64_t at = 0;
+    for (int32_t g = 0; g < num_groups; g++)
+    {
+        const int32_t n     = group_counts[g];
+        const StatusType rc = batch.add_poa_group_resident(st, sets.data(), slices + at, n);
+        if (rc == StatusType::exceeded_maximum_poas)
+            return g;
+        group_status[g] = int32_t(rc);
+        for (size_t i = 0; i < size_t(n); i++)
+            per_seq_status[size_t(at) + i] = int32_t(i < st.size() ? st[i] : rc);
+        at += n;
+    }
+    return num_groups;
 }
 
 } // namespace
@@ -952,6 +1000,39 @@ cudapoa::StatusType add_poa_group_resident(cudapoa::Batch& batch, std::vector<cu
         reads[s] = sets[s] ? sets[s]->impl().reads.get() : nullptr;
     return add_resident_checked(*own, per_seq_status, reads,
                                 reinterpret_cast<const gwamd_read_slice*>(slices.data()), int32_t(slices.size()));
+}
+
+int32_t add_poa_groups_resident(cudapoa::Batch& batch, std::vector<cudapoa::StatusType>& group_status,
+                                std::vector<cudapoa::StatusType>& per_seq_status,
+                                const std::vector<const cudamapper::DeviceReads*>& sets,
+                                const std::vector<ReadSlice>& slices, const std::vector<int32_t>& group_counts)
+{
+    auto* own = dynamic_cast<cudapoa::PoaBatch*>(&batch);
+    if (!own)
+        throw std::invalid_argument("add_poa_groups_resident: the batch does not come from cudapoa::create_batch");
+    if (group_counts.size() > size_t(INT32_MAX))
+        throw std::invalid_argument("add_poa_groups_resident: too many groups for one call");
+    std::vector<const gwamd::mapper::DeviceReads*> reads(sets.size());
+    for (size_t s = 0; s < sets.size(); s++)
+        reads[s] = sets[s] ? sets[s]->impl().reads.get() : nullptr;
+    int64_t total = 0;
+    for (int32_t c : group_counts)
+        total += std::max(c, 0);
+    if (total > int64_t(slices.size()))
+        throw std::invalid_argument("add_poa_groups_resident: the groups count more slices than there are");
+    std::vector<int32_t> groups(group_counts.size() + 1), seqs(size_t(total) + 1);
+    const int32_t added =
+        add_resident_groups_checked(*own, reads, reinterpret_cast<const gwamd_read_slice*>(slices.data()),
+                                    group_counts.data(), int32_t(group_counts.size()), groups.data(), seqs.data());
+    group_status.clear();
+    per_seq_status.clear();
+    for (int32_t g = 0, at = 0; g < added; g++)
+    {
+        group_status.push_back(cudapoa::StatusType(groups[size_t(g)]));
+        for (int32_t i = 0; i < group_counts[size_t(g)]; i++, at++)
+            per_seq_status.push_back(cudapoa::StatusType(seqs[size_t(at)]));
+    }
+    return added;
 }
 
 } // namespace cudapolish
@@ -1115,6 +1196,31 @@ int32_t gwamd_poa_add_poa_group_resident(gwamd_poa_batch* batch, const gwamd_dev
         for (size_t i = st.size(); i < size_t(n); i++)
             per_seq_status[i] = int32_t(rc);
         return int32_t(rc);
+    });
+}
+
+int32_t gwamd_poa_add_poa_groups_resident(gwamd_poa_batch* batch, const gwamd_device_reads* const* sets,
+                                          int32_t num_sets, const gwamd_read_slice* slices,
+                                          const int32_t* group_counts, int32_t num_groups, int32_t* group_status,
+                                          int32_t* per_seq_status, int32_t* num_added)
+{
+    if (num_added)
+        *num_added = 0;
+    return guarded([&] {
+        if (!batch)
+            throw std::invalid_argument("batch is NULL");
+        if (!num_added)
+            throw std::invalid_argument("num_added is NULL");
+        if (num_sets < 0)
+            throw std::invalid_argument("num_sets must not be negative");
+        if (num_sets > 0 && !sets)
+            throw std::invalid_argument("sets is NULL");
+        std::vector<const gwamd::mapper::DeviceReads*> reads(static_cast<size_t>(num_sets));
+        for (int32_t s = 0; s < num_sets; s++)
+            reads[size_t(s)] = sets[s] ? sets[s]->reads.get() : nullptr;
+        *num_added = add_resident_groups_checked(*batch->impl, reads, slices, group_counts, num_groups, group_status,
+                                                 per_seq_status);
+        return int32_t(*num_added < num_groups ? cp::StatusType::exceeded_maximum_poas : cp::StatusType::success);
     });
 }
 

@@ -5,7 +5,8 @@
 // cut (cut_launch) for paths from the host, for the aligner's device paths
 // (window_segments_resident, on the engines of overlap_engines.hpp) and for
 // CIGAR ops (cut_cigars, polish_cigar.hip; walk_cigar_on_host), the grouping
-// into cudapoa groups and the C ABI.  Every argument is checked here, before any
+// into cudapoa groups on the host (group_slices) and on the device
+// (group_segments_on_device, slices_resident; polish_group.hip) and the C ABI.  Every argument is checked here, before any
 // device call, so that the kernel is never given an overlap with start > end or
 // a record range it does not own.
 //
@@ -20,9 +21,11 @@
 #include "mapper_capi.hpp"
 #include "mapper_reads.hpp"
 #include "overlap_engines.hpp"
+#include "polish_group.hpp"
 #include "polish_windows.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cstddef>
 #include <cstring>
 #include <memory>
@@ -38,14 +41,7 @@ static_assert(sizeof(gw::cudapolish::WindowSegment) == sizeof(gwamd_window_segme
               "a record is eight 32-bit words");
 static_assert(sizeof(gw::cudaaligner::AlignmentState) == 1, "states are bytes");
 
-struct gwamd_window_slices
-{
-    std::vector<gwamd_read_slice> slices;
-    std::vector<int32_t> window_counts;
-    std::vector<uint32_t> window_target, window_index;
-    std::vector<int32_t> sequence_overlap, sequence_t_begin, sequence_t_end;
-    int64_t dropped_by_cap = 0, dropped_by_quality = 0;
-};
+// (gwamd_window_slices, the handle of all three grouping routes: polish_group.hpp)
 
 // the slices with their bases copied out of the host's reads
 struct gwamd_windows
@@ -281,12 +277,32 @@ inline void launch_cut(const CigarSource& source, const OverlapRecord* d_overlap
     launch_window_cut_cigar(source, d_overlaps, d_record_base, d_records, d_status, n, window_length, stream);
 }
 
+// what the cut's kernel reads besides its source: held until the stream has been synchronized
+struct CutInputs
+{
+    gm::DevBuf<OverlapRecord> overlaps;
+    gm::DevBuf<uint32_t> base;
+};
+
 // The one launch of the cut: n > 0 checked overlaps in host memory whose paths
-// or CIGAR ops `source` names on the device.  The overlaps and the record
-// bases go up, the records are zeroed, the kernel runs on stream, records and
-// status come back and complete_records writes the rest; the records of
-// overlap i carry index[i] (null: i).  Returns after the stream has been
-// synchronized.
+// or CIGAR ops `source` names on the device.  The overlaps and base[0, n), the
+// index of each one's first record in d_records, go up and the kernel runs on
+// stream: it writes the records, which the caller has zeroed, and d_status[0, n).
+// Asynchronous; records and status stay on the device.
+template <typename Source>
+void cut_to_device(const Source& source, const OverlapRecord* overlaps, int64_t n, const uint32_t* base,
+                   gwamd_window_segment* d_records, uint32_t* d_status, int32_t window_length, const Budget& budget,
+                   hipStream_t stream, CutInputs& held)
+{
+    upload(held.overlaps, overlaps, size_t(n), budget, stream);
+    upload(held.base, base, size_t(n), budget, stream);
+    launch_cut(source, held.overlaps.data(), held.base.data(), d_records, d_status, n, window_length, stream);
+}
+
+// cut_to_device for a caller that wants the records on the host: they are
+// zeroed on the device, cut, and come back with the status, and
+// complete_records writes the rest; the records of overlap i carry index[i]
+// (null: i).  Returns after the stream has been synchronized.
 template <typename Source>
 CutRecords cut_launch(const Source& source, const OverlapRecord* overlaps, int64_t n, const int32_t* index,
                       int32_t window_length, const Budget& budget, hipStream_t stream)
@@ -296,14 +312,12 @@ CutRecords cut_launch(const Source& source, const OverlapRecord* overlaps, int64
     out.records.assign(size_t(out.layout.total()), gwamd_window_segment{});
     out.status.assign(size_t(n), 0);
     const std::vector<uint32_t>& base = out.layout.base;
-    gm::DevBuf<OverlapRecord> d_overlaps;
-    gm::DevBuf<uint32_t> d_base;
-    upload(d_overlaps, overlaps, size_t(n), budget, stream);
-    upload(d_base, base.data(), size_t(n), budget, stream);
+    CutInputs held;
     gm::DevBuf<uint32_t> d_status(size_t(n), budget);
     gm::DevBuf<gwamd_window_segment> d_records(std::max<size_t>(out.records.size(), 1), budget);
     GWAMD_HIP_CHECK(hipMemsetAsync(d_records.data(), 0, d_records.size() * sizeof(gwamd_window_segment), stream));
-    launch_cut(source, d_overlaps.data(), d_base.data(), d_records.data(), d_status.data(), n, window_length, stream);
+    cut_to_device(source, overlaps, n, base.data(), d_records.data(), d_status.data(), window_length, budget, stream,
+                  held);
     if (!out.records.empty())
         GWAMD_HIP_CHECK(hipMemcpyAsync(out.records.data(), d_records.data(),
                                        out.records.size() * sizeof(gwamd_window_segment), hipMemcpyDeviceToHost,
@@ -401,11 +415,18 @@ void check_cigars(int64_t n, const uint32_t* ops, const int64_t* op_offsets)
         throw std::invalid_argument("ops is NULL");
 }
 
-// The cut of checked overlaps from their CIGAR ops in host memory: the ops
-// [op_offsets[0], op_offsets[n]) go up as they are, or normalised in one pass
-// when they are SAM's; no run is expanded.
-void cut_cigars(const std::vector<OverlapRecord>& overlaps, const uint32_t* ops, const int64_t* op_offsets, bool sam,
-                int32_t window_length, const Budget& budget, std::vector<gwamd_window_segment>& out)
+// The CIGAR ops of checked overlaps on the device, and the source that names them
+struct DeviceCigars
+{
+    gm::DevBuf<uint32_t> ops;
+    gm::DevBuf<int64_t> offsets;
+    CigarSource source;
+};
+
+// The ops [op_offsets[0], op_offsets[n]) go up as they are, or normalised in
+// one pass when they are SAM's; no run is expanded.
+void upload_cigars(const std::vector<OverlapRecord>& overlaps, const uint32_t* ops, const int64_t* op_offsets, bool sam,
+                   const Budget& budget, DeviceCigars& up)
 {
     const size_t n      = overlaps.size();
     const int64_t first = op_offsets[0], total = op_offsets[n] - first;
@@ -424,17 +445,25 @@ void cut_cigars(const std::vector<OverlapRecord>& overlaps, const uint32_t* ops,
                                                                    overlaps[i].relative_strand == '-');
         }
     }
-    gm::DevBuf<uint32_t> d_ops(size_t(std::max<int64_t>(total, 1)), budget);
-    gm::DevBuf<int64_t> d_offsets;
+    up.ops.alloc(size_t(std::max<int64_t>(total, 1)), budget);
     if (total > 0)
-        GWAMD_HIP_CHECK(hipMemcpyAsync(d_ops.data(), sam ? normalised.data() : ops + first,
+        GWAMD_HIP_CHECK(hipMemcpyAsync(up.ops.data(), sam ? normalised.data() : ops + first,
                                        size_t(total) * sizeof(uint32_t), hipMemcpyHostToDevice, nullptr));
-    upload(d_offsets, offsets.data(), n + 1, budget, nullptr);
-    CigarSource source;
-    source.ops     = d_ops.data();
-    source.num_ops = total;
-    source.offsets = d_offsets.data();
-    out = cut_launch(source, overlaps.data(), int64_t(n), nullptr, window_length, budget, nullptr).records;
+    upload(up.offsets, offsets.data(), n + 1, budget, nullptr);
+    GWAMD_HIP_CHECK(hipStreamSynchronize(nullptr)); // the copies have read this function's arrays
+    up.source.ops     = up.ops.data();
+    up.source.num_ops = total;
+    up.source.offsets = up.offsets.data();
+}
+
+// The cut of checked overlaps from their CIGAR ops in host memory
+void cut_cigars(const std::vector<OverlapRecord>& overlaps, const uint32_t* ops, const int64_t* op_offsets, bool sam,
+                int32_t window_length, const Budget& budget, std::vector<gwamd_window_segment>& out)
+{
+    DeviceCigars up;
+    upload_cigars(overlaps, ops, op_offsets, sam, budget, up);
+    out = cut_launch(up.source, overlaps.data(), int64_t(overlaps.size()), nullptr, window_length, budget, nullptr)
+              .records;
 }
 
 } // namespace
@@ -491,6 +520,51 @@ namespace
 
 char complement(char c) { return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c; }
 
+// What the host and the device grouping ask of their scalar arguments
+void check_grouping(const gwamd_window_segment* segments, int64_t num_segments, int32_t window_length,
+                    int32_t max_sequences_per_window)
+{
+    if (window_length <= 0)
+        throw std::invalid_argument("window_length must be positive, got " + std::to_string(window_length));
+    if (max_sequences_per_window < 1)
+        throw std::invalid_argument("max_sequences_per_window must be at least 1");
+    if (num_segments < 0 || (num_segments > 0 && !segments))
+        throw std::invalid_argument("segments: bad count or NULL");
+}
+
+// first[r]: the global index of target r's first window; first[num_reads]: the number of windows
+std::vector<int64_t> first_windows(const gm::ReadSet& targets, int64_t w)
+{
+    std::vector<int64_t> first(size_t(targets.num_reads) + 1, 0);
+    for (int64_t r = 0; r < targets.num_reads; r++)
+        first[size_t(r) + 1] = first[size_t(r)] + (targets.offsets[r + 1] - targets.offsets[r] + w - 1) / w;
+    return first;
+}
+
+// Whether segment s counts, before the quality filter and the cap: it is not
+// flagged and passes the 2 % rule.  Throws std::invalid_argument for a segment
+// whose overlap index, read ids, window or (unless it is flagged) query range
+// are out of bounds.
+bool segment_counts(int64_t s, const gwamd_window_segment& seg, const std::vector<gm::OverlapRecord>& overlaps,
+                    const gm::ReadSet& targets, const gm::ReadSet& queries, const std::vector<int64_t>& first,
+                    int64_t w)
+{
+    const std::string which = "segment " + std::to_string(s);
+    if (seg.overlap >= overlaps.size())
+        throw std::invalid_argument(which + ": overlap index beyond the overlaps");
+    const gm::OverlapRecord& o = overlaps[seg.overlap];
+    if (int64_t(o.query_read_id) >= queries.num_reads || int64_t(o.target_read_id) >= targets.num_reads)
+        throw std::invalid_argument(which + ": read id of its overlap beyond the reads");
+    if (int64_t(seg.window) >= first[size_t(o.target_read_id) + 1] - first[o.target_read_id])
+        throw std::invalid_argument(which + ": window beyond the target's windows");
+    if (seg.flags & (GWAMD_SEGMENT_EMPTY | GWAMD_SEGMENT_BAD_PATH | GWAMD_SEGMENT_NOT_ALIGNED))
+        return false;
+    if (seg.q_begin > seg.q_end ||
+        int64_t(seg.q_end) > queries.offsets[o.query_read_id + 1] - queries.offsets[o.query_read_id])
+        throw std::invalid_argument(which + ": query range outside its read");
+    return (int64_t(seg.q_end) - int64_t(seg.q_begin)) * 50 >= w;
+}
+
 // The grouping: which slices of the targets (set 0) and queries (set 1) make
 // up which window.  Only offsets are looked at, and the queries' quality
 // characters when they are given (racon's mean-quality rule, gwamd_polish.h).
@@ -500,40 +574,21 @@ std::unique_ptr<gwamd_window_slices> group_slices(const gm::ReadSet& targets, co
                                                   const gwamd_window_segment* segments, int64_t num_segments,
                                                   int32_t window_length, int32_t max_sequences_per_window)
 {
-    if (window_length <= 0)
-        throw std::invalid_argument("window_length must be positive, got " + std::to_string(window_length));
-    if (max_sequences_per_window < 1)
-        throw std::invalid_argument("max_sequences_per_window must be at least 1");
-    if (num_segments < 0 || (num_segments > 0 && !segments))
-        throw std::invalid_argument("segments: bad count or NULL");
+    check_grouping(segments, num_segments, window_length, max_sequences_per_window);
     if (query_qualities && quality_threshold_tenths < 0)
         throw std::invalid_argument("quality_threshold_tenths must not be negative");
     const int64_t w = window_length;
     // the windows of every target, and the kept segments of each in the order given
-    std::vector<int64_t> first(size_t(targets.num_reads) + 1, 0);
-    for (int64_t r = 0; r < targets.num_reads; r++)
-        first[size_t(r) + 1] = first[size_t(r)] + (targets.offsets[r + 1] - targets.offsets[r] + w - 1) / w;
-    const int64_t num_windows = first[size_t(targets.num_reads)];
+    const std::vector<int64_t> first = first_windows(targets, w);
+    const int64_t num_windows        = first[size_t(targets.num_reads)];
     std::vector<std::vector<int64_t>> kept(static_cast<size_t>(num_windows));
     auto out = std::make_unique<gwamd_window_slices>();
     for (int64_t s = 0; s < num_segments; s++)
     {
         const gwamd_window_segment& seg = segments[s];
-        const std::string which         = "segment " + std::to_string(s);
-        if (seg.overlap >= overlaps.size())
-            throw std::invalid_argument(which + ": overlap index beyond the overlaps");
+        if (!segment_counts(s, seg, overlaps, targets, queries, first, w))
+            continue;
         const gm::OverlapRecord& o = overlaps[seg.overlap];
-        if (int64_t(o.query_read_id) >= queries.num_reads || int64_t(o.target_read_id) >= targets.num_reads)
-            throw std::invalid_argument(which + ": read id of its overlap beyond the reads");
-        if (int64_t(seg.window) >= first[size_t(o.target_read_id) + 1] - first[o.target_read_id])
-            throw std::invalid_argument(which + ": window beyond the target's windows");
-        if (seg.flags & (GWAMD_SEGMENT_EMPTY | GWAMD_SEGMENT_BAD_PATH | GWAMD_SEGMENT_NOT_ALIGNED))
-            continue;
-        if (seg.q_begin > seg.q_end ||
-            int64_t(seg.q_end) > queries.offsets[o.query_read_id + 1] - queries.offsets[o.query_read_id])
-            throw std::invalid_argument(which + ": query range outside its read");
-        if ((int64_t(seg.q_end) - int64_t(seg.q_begin)) * 50 < w)
-            continue;
         if (query_qualities)
         {
             const char* q = query_qualities + queries.offsets[o.query_read_id];
@@ -636,6 +691,197 @@ void cut_resident(const gm::DeviceReads& query, const gm::DeviceReads& target,
     gm::check_on_current_device(query, target);
     gp::window_segments_resident(query, target, records.data(), int32_t(records.size()), window_length,
                                  num_alignment_engines, out);
+}
+
+// ---- grouping on the device (polish_group.hip) ----------------------------------
+
+// first_windows as the kernels read it.  Throws std::invalid_argument for 2^31
+// windows or more, and when the windows and `records` records, each of which may
+// become a sequence, come to 2^31 or more.
+std::vector<uint32_t> device_first_windows(const gm::ReadSet& targets, int64_t w, int64_t records)
+{
+    const std::vector<int64_t> first = first_windows(targets, w);
+    if (first.back() >= (int64_t(1) << 31) || first.back() + records >= (int64_t(1) << 31))
+        throw std::invalid_argument("2^31 or more windows or sequences in one call");
+    return std::vector<uint32_t>(first.begin(), first.end());
+}
+
+// gwamd_build_window_slices_device after the checks of its pointers and read
+// sets: the rest of the checks, all of them before the first device call, then
+// the given segments go up and are grouped.
+std::unique_ptr<gwamd_window_slices> group_segments_on_device(
+    const gm::ReadSet& targets, const gm::ReadSet& queries, const gm::DeviceReads* query_reads,
+    int32_t quality_threshold_tenths, const std::vector<gm::OverlapRecord>& overlaps,
+    const gwamd_window_segment* segments, int64_t num_segments, int32_t window_length,
+    int32_t max_sequences_per_window, int32_t device_id, const gp::Budget& budget, int32_t repeats = 1,
+    double* seconds = nullptr)
+{
+    check_grouping(segments, num_segments, window_length, max_sequences_per_window);
+    if (quality_threshold_tenths < 0)
+        throw std::invalid_argument("quality_threshold_tenths must not be negative");
+    if (query_reads)
+    {
+        if (device_id >= 0 && query_reads->device_id != device_id)
+            throw std::invalid_argument("query_reads is on device " + std::to_string(query_reads->device_id) +
+                                        ", the call is for device " + std::to_string(device_id));
+        if (query_reads->num_reads() != queries.num_reads ||
+            !std::equal(query_reads->offsets.begin(), query_reads->offsets.end(), queries.offsets,
+                        [&](int64_t a, int64_t b) { return a == b - queries.offsets[0]; }))
+            throw std::invalid_argument("query_reads does not hold the reads of query_offsets");
+    }
+    const std::vector<uint32_t> first = device_first_windows(targets, window_length, num_segments);
+    {
+        const std::vector<int64_t> first64(first.begin(), first.end());
+        for (int64_t s = 0; s < num_segments; s++)
+            (void)segment_counts(s, segments[s], overlaps, targets, queries, first64, window_length);
+    }
+    auto out = std::make_unique<gwamd_window_slices>();
+    if (first.back() == 0)
+        return out;
+    if (device_id < 0) // the C++ entry: the current device
+    {
+        GWAMD_HIP_CHECK(hipGetDevice(&device_id));
+        if (query_reads && query_reads->device_id != device_id)
+            throw std::invalid_argument("query_reads is not on the current device");
+    }
+    gwamd::host::ScopedDevice dev(device_id);
+    const bool filter = query_reads && query_reads->has_qualities;
+    gm::DevBuf<gwamd_window_segment> d_records;
+    gm::DevBuf<gm::OverlapRecord> d_overlaps;
+    gm::DevBuf<int64_t> d_target_offsets;
+    gm::DevBuf<uint32_t> d_first;
+    gp::upload(d_records, segments, size_t(num_segments), budget, nullptr);
+    gp::upload(d_overlaps, overlaps.data(), overlaps.size(), budget, nullptr);
+    gp::upload(d_target_offsets, targets.offsets, size_t(targets.num_reads) + 1, budget, nullptr);
+    gp::upload(d_first, first.data(), first.size(), budget, nullptr);
+    gp::GroupInput in;
+    in.records                  = d_records.data();
+    in.num_records              = num_segments;
+    in.overlaps                 = d_overlaps.data();
+    in.num_overlaps             = int64_t(overlaps.size());
+    in.target_offsets           = d_target_offsets.data();
+    in.window_first             = d_first.data();
+    in.num_targets              = targets.num_reads;
+    in.num_windows              = int64_t(first.back());
+    in.query_offsets            = filter ? query_reads->d_offsets.data() : nullptr;
+    in.query_qualities          = filter ? query_reads->qualities() : nullptr;
+    in.quality_threshold_tenths = quality_threshold_tenths;
+    in.window_length            = window_length;
+    in.max_sequences_per_window = max_sequences_per_window;
+    // (repeats > 1, seconds: the measurement hook times each grouping of the records that are now resident)
+    GWAMD_HIP_CHECK(hipStreamSynchronize(nullptr));
+    for (int32_t r = 0; r < repeats; r++)
+    {
+        const auto begin = std::chrono::steady_clock::now();
+        gp::group_on_device(in, *out, budget, nullptr);
+        if (seconds)
+            seconds[r] = std::chrono::duration<double>(std::chrono::steady_clock::now() - begin).count();
+    }
+    return out;
+}
+
+// gwamd_window_slices_resident after the checks of its pointers: the rest of
+// the checks, then the cut (of the aligner's device paths, engine range by
+// engine range, or of the CIGAR ops) into one device array of records, laid out
+// by plan_records over all overlaps, and the grouping of that array.  No record
+// comes to the host.
+std::unique_ptr<gwamd_window_slices> slices_resident(const gm::DeviceReads& query, const gm::DeviceReads& target,
+                                                     const std::vector<gm::OverlapRecord>& overlaps,
+                                                     const uint32_t* ops, const int64_t* op_offsets,
+                                                     int32_t convention, int32_t window_length,
+                                                     int32_t max_sequences_per_window,
+                                                     int32_t quality_threshold_tenths, int32_t num_alignment_engines)
+{
+    namespace ga      = gwamd::aln;
+    const int32_t n   = int32_t(overlaps.size());
+    const bool cigars = op_offsets != nullptr;
+    const bool sam    = cigars && gp::is_sam(convention);
+    gm::check_overlaps(query, target, overlaps.data(), n);
+    if (cigars)
+        gp::check_cigars(n, ops, op_offsets);
+    else if (num_alignment_engines < 1)
+        throw std::invalid_argument("num_alignment_engines must be at least 1");
+    const gp::RecordLayout layout = gp::plan_records(overlaps.data(), n, window_length);
+    if (max_sequences_per_window < 1)
+        throw std::invalid_argument("max_sequences_per_window must be at least 1");
+    if (quality_threshold_tenths < 0)
+        throw std::invalid_argument("quality_threshold_tenths must not be negative");
+    const gm::ReadSet targets{nullptr, target.offsets.data(), target.num_reads()};
+    const std::vector<uint32_t> first = device_first_windows(targets, window_length, layout.total());
+    auto out                          = std::make_unique<gwamd_window_slices>();
+    if (first.back() == 0)
+        return out;
+    gm::check_on_current_device(query, target);
+
+    const gp::Budget budget; // the fused entry has no pool to count against
+    gm::DevBuf<gwamd_window_segment> d_records(std::max<size_t>(size_t(layout.total()), 1), budget);
+    gm::DevBuf<uint32_t> d_status(std::max<size_t>(size_t(n), 1), budget);
+    std::vector<uint32_t> slot(size_t(n), gp::kNotAligned); // overlap -> its word of d_status
+    GWAMD_HIP_CHECK(hipMemsetAsync(d_records.data(), 0, d_records.size() * sizeof(gwamd_window_segment), nullptr));
+    GWAMD_HIP_CHECK(hipStreamSynchronize(nullptr)); // the engines' streams do not wait for the null stream
+    if (n > 0 && cigars)
+    {
+        gp::DeviceCigars up;
+        gp::CutInputs held;
+        gp::upload_cigars(overlaps, ops, op_offsets, sam, budget, up);
+        gp::cut_to_device(up.source, overlaps.data(), n, layout.base.data(), d_records.data(), d_status.data(),
+                          window_length, budget, nullptr, held);
+        GWAMD_HIP_CHECK(hipStreamSynchronize(nullptr));
+        for (int32_t i = 0; i < n; i++)
+            slot[size_t(i)] = uint32_t(i);
+    }
+    else if (n > 0)
+    {
+        const ga::ResidentOverlaps pairs(overlaps.data(), n);
+        for (size_t k = 0; k < pairs.kept.size(); k++)
+            slot[size_t(pairs.kept[k])] = uint32_t(k);
+        // as window_segments_resident, but the records of the range stay on the
+        // device, at the places the layout of the whole call gives them
+        const ga::RangeFn cut = [&](claraparabricks::genomeworks::cudaaligner::Aligner& aligner, int32_t start,
+                                    int32_t end) {
+            const ga::DevicePaths p = ga::device_paths(aligner);
+            gp::PathSource source;
+            source.paths        = p.paths;
+            source.paths_bytes  = p.bytes;
+            source.stride       = p.max_path_length;
+            source.lengths      = p.lengths;
+            source.max_length   = p.max_path_length;
+            source.end_to_start = true;
+            std::vector<uint32_t> base(size_t(end - start));
+            for (int32_t k = 0; k < end - start; k++)
+                base[size_t(k)] = layout.base[size_t(pairs.kept[size_t(start + k)])];
+            gp::CutInputs held;
+            gp::cut_to_device(source, pairs.kept_records.data() + start, end - start, base.data(), d_records.data(),
+                              d_status.data() + start, window_length, budget, p.stream, held);
+            GWAMD_HIP_CHECK(hipStreamSynchronize(p.stream));
+        };
+        ga::run_engines(pairs.lengths, pairs.kept, num_alignment_engines, {pairs.add(query, target), cut, true});
+    }
+    gm::DevBuf<gm::OverlapRecord> d_overlaps;
+    gm::DevBuf<uint32_t> d_base, d_slot, d_first;
+    gp::upload(d_overlaps, overlaps.data(), size_t(n), budget, nullptr);
+    gp::upload(d_base, layout.base.data(), size_t(n) + 1, budget, nullptr);
+    gp::upload(d_slot, slot.data(), size_t(n), budget, nullptr);
+    gp::upload(d_first, first.data(), first.size(), budget, nullptr);
+    gp::GroupInput in;
+    in.records                  = d_records.data();
+    in.num_records              = layout.total();
+    in.overlaps                 = d_overlaps.data();
+    in.num_overlaps             = n;
+    in.record_base              = d_base.data();
+    in.status                   = d_status.data();
+    in.status_slot              = d_slot.data();
+    in.target_offsets           = target.d_offsets.data();
+    in.window_first             = d_first.data();
+    in.num_targets              = target.num_reads();
+    in.num_windows              = int64_t(first.back());
+    in.query_offsets            = query.has_qualities ? query.d_offsets.data() : nullptr;
+    in.query_qualities          = query.qualities();
+    in.quality_threshold_tenths = quality_threshold_tenths;
+    in.window_length            = window_length;
+    in.max_sequences_per_window = max_sequences_per_window;
+    gp::group_on_device(in, *out, budget, nullptr);
+    return out;
 }
 
 } // namespace
@@ -750,6 +996,71 @@ Windows build_windows(const io::FastaParser& targets, const io::FastaParser& que
         out.sequence.push_back(std::move(meta));
     }
     return out;
+}
+
+namespace
+{
+
+WindowSlices as_window_slices(gwamd_window_slices&& h)
+{
+    static_assert(sizeof(ReadSlice) == sizeof(gwamd_read_slice), "ReadSlice is gwamd_read_slice");
+    WindowSlices out;
+    out.slices.resize(h.slices.size());
+    if (!h.slices.empty())
+        std::memcpy(static_cast<void*>(out.slices.data()), h.slices.data(), h.slices.size() * sizeof(ReadSlice));
+    out.window_counts      = std::move(h.window_counts);
+    out.window_target      = std::move(h.window_target);
+    out.window_index       = std::move(h.window_index);
+    out.sequence_overlap   = std::move(h.sequence_overlap);
+    out.sequence_t_begin   = std::move(h.sequence_t_begin);
+    out.sequence_t_end     = std::move(h.sequence_t_end);
+    out.dropped_by_cap     = h.dropped_by_cap;
+    out.dropped_by_quality = h.dropped_by_quality;
+    return out;
+}
+
+} // namespace
+
+WindowSlices build_window_slices_device(DefaultDeviceAllocator allocator, const io::FastaParser& targets,
+                                        const io::FastaParser& queries,
+                                        const std::vector<cudamapper::Overlap>& overlaps,
+                                        const std::vector<WindowSegment>& segments, int32_t window_length,
+                                        int32_t max_sequences_per_window, const cudamapper::DeviceReads* query_reads,
+                                        int32_t quality_threshold_tenths)
+{
+    const gm::PackedReads t(targets), q(queries);
+    return as_window_slices(std::move(*group_segments_on_device(
+        t.view(), q.view(), query_reads ? query_reads->impl().reads.get() : nullptr, quality_threshold_tenths,
+        as_records(overlaps), reinterpret_cast<const gwamd_window_segment*>(segments.data()),
+        int64_t(segments.size()), window_length, max_sequences_per_window, -1, allocator.budget())));
+}
+
+WindowSlices window_slices_resident(const std::vector<cudamapper::Overlap>& overlaps,
+                                    const cudamapper::DeviceReads& query_reads,
+                                    const cudamapper::DeviceReads& target_reads, int32_t window_length,
+                                    int32_t max_sequences_per_window, int32_t quality_threshold_tenths,
+                                    int32_t num_alignment_engines, const std::vector<std::vector<uint32_t>>* cigars,
+                                    CigarConvention convention)
+{
+    if (overlaps.size() > size_t(INT32_MAX))
+        throw std::invalid_argument("too many overlaps for one call");
+    std::vector<int64_t> offsets;
+    std::vector<uint32_t> ops;
+    if (cigars)
+    {
+        if (cigars->size() != overlaps.size())
+            throw std::invalid_argument("window_slices_resident: one CIGAR per overlap expected");
+        offsets.assign(1, 0);
+        for (const std::vector<uint32_t>& c : *cigars)
+        {
+            ops.insert(ops.end(), c.begin(), c.end());
+            offsets.push_back(int64_t(ops.size()));
+        }
+    }
+    return as_window_slices(std::move(*slices_resident(
+        *query_reads.impl().reads, *target_reads.impl().reads, as_records(overlaps), ops.data(),
+        cigars ? offsets.data() : nullptr, int32_t(convention), window_length, max_sequences_per_window,
+        quality_threshold_tenths, num_alignment_engines)));
 }
 
 } // namespace cudapolish
@@ -982,6 +1293,86 @@ int32_t gwamd_build_window_slices(const int64_t* target_offsets, int32_t num_tar
         gp::check_cut_overlaps(overlaps, n, records);
         *out = group_slices(targets, queries, query_qualities_or_null, quality_threshold_tenths, records, segments,
                             num_segments, window_length, max_sequences_per_window)
+                   .release();
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_build_window_slices_device(const int64_t* target_offsets, int32_t num_targets,
+                                         const int64_t* query_offsets, int32_t num_queries,
+                                         const gwamd_device_reads* query_reads_or_null,
+                                         int32_t quality_threshold_tenths, const gwamd_overlap* overlaps, int64_t n,
+                                         const gwamd_window_segment* segments, int64_t num_segments,
+                                         int32_t window_length, int32_t max_sequences_per_window, int32_t device_id,
+                                         gwamd_device_allocator* allocator_or_null, gwamd_window_slices** out)
+{
+    if (out)
+        *out = nullptr;
+    return gm::guarded_map([&] {
+        if (!out)
+            throw std::invalid_argument("out is NULL");
+        if (device_id < 0)
+            throw std::invalid_argument("device_id must not be negative");
+        static const char somewhere = 0; // only offsets are read
+        const gm::ReadSet targets{&somewhere, target_offsets, num_targets};
+        const gm::ReadSet queries{&somewhere, query_offsets, num_queries};
+        gm::check_read_set("target", targets);
+        gm::check_read_set("query", queries);
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        *out = group_segments_on_device(targets, queries, query_reads_or_null ? query_reads_or_null->reads.get() : nullptr,
+                                        quality_threshold_tenths, records, segments, num_segments, window_length,
+                                        max_sequences_per_window, device_id,
+                                        allocator_or_null ? allocator_or_null->alloc.budget() : nullptr)
+                   .release();
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_internal_group_repeat(const int64_t* target_offsets, int32_t num_targets, const int64_t* query_offsets,
+                                    int32_t num_queries, const gwamd_device_reads* query_reads_or_null,
+                                    int32_t quality_threshold_tenths, const gwamd_overlap* overlaps, int64_t n,
+                                    const gwamd_window_segment* segments, int64_t num_segments, int32_t window_length,
+                                    int32_t max_sequences_per_window, int32_t device_id, int32_t repeats,
+                                    double* seconds)
+{
+    return gm::guarded_map([&] {
+        if (repeats < 1 || !seconds || device_id < 0)
+            throw std::invalid_argument("repeats below 1, NULL seconds or a negative device_id");
+        static const char somewhere = 0;
+        const gm::ReadSet targets{&somewhere, target_offsets, num_targets};
+        const gm::ReadSet queries{&somewhere, query_offsets, num_queries};
+        gm::check_read_set("target", targets);
+        gm::check_read_set("query", queries);
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        (void)group_segments_on_device(targets, queries, query_reads_or_null ? query_reads_or_null->reads.get() : nullptr,
+                                       quality_threshold_tenths, records, segments, num_segments, window_length,
+                                       max_sequences_per_window, device_id, nullptr, repeats, seconds);
+        return int32_t(0);
+    });
+}
+
+int32_t gwamd_window_slices_resident(const gwamd_device_reads* query_reads, const gwamd_device_reads* target_reads,
+                                     const gwamd_overlap* overlaps, int32_t n, const uint32_t* ops_or_null,
+                                     const int64_t* op_offsets_or_null, int32_t convention, int32_t window_length,
+                                     int32_t max_sequences_per_window, int32_t quality_threshold_tenths,
+                                     int32_t num_alignment_engines, gwamd_window_slices** out)
+{
+    if (out)
+        *out = nullptr;
+    return gm::guarded_map([&] {
+        if (!out)
+            throw std::invalid_argument("out is NULL");
+        if (!query_reads || !target_reads)
+            throw std::invalid_argument("query_reads or target_reads is NULL");
+        if (ops_or_null && !op_offsets_or_null)
+            throw std::invalid_argument("ops without op_offsets");
+        std::vector<gm::OverlapRecord> records;
+        gp::check_cut_overlaps(overlaps, n, records);
+        *out = slices_resident(*query_reads->reads, *target_reads->reads, records, ops_or_null, op_offsets_or_null,
+                               convention, window_length, max_sequences_per_window, quality_threshold_tenths,
+                               num_alignment_engines)
                    .release();
         return int32_t(0);
     });

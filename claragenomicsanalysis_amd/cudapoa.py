@@ -204,6 +204,46 @@ class CudaPoaBatch:
         self._resident_sets.extend(sets)
         return rc, list(seq_status)[:n]
 
+    def add_poa_groups_resident(self, sets, slices, counts):
+        """add_poa_group_resident for many groups in one call
+        (gwamd_poa_add_poa_groups_resident): group g is the next counts[g] of
+        slices (a SLICE_DTYPE array, or tuples).  Equivalent to adding them one
+        by one, in order, up to the first group the batch answers
+        exceeded_maximum_poas for.  Returns (num_added, group_status,
+        per_seq_status): the number of groups before that one, a status per
+        added group and the per-sequence statuses of each as a list.  Every
+        slice is checked first: ValueError leaves the batch unchanged."""
+        from .cudapolish import SLICE_DTYPE
+        handles = (C.c_void_p * max(len(sets), 1))()
+        for i, r in enumerate(sets):
+            if not getattr(r, "_handle", None):
+                raise ValueError("set %d is not an open DeviceReads" % i)
+            handles[i] = r._handle
+        if isinstance(slices, np.ndarray) and slices.dtype == SLICE_DTYPE:
+            arr = np.ascontiguousarray(slices)
+        else:
+            try:
+                arr = np.array([tuple(sl) for sl in slices], dtype=SLICE_DTYPE)
+            except OverflowError as e:
+                raise ValueError("a slice field is outside its 32-bit range: %s" % e)
+        groups = np.ascontiguousarray(counts, dtype=np.int32)
+        if groups.ndim != 1 or (len(groups) and int(groups.clip(min=0).sum()) > len(arr)):
+            raise ValueError("counts must be one-dimensional and count no more slices than there are")
+        if len(arr) == 0:
+            arr = np.zeros(1, SLICE_DTYPE)
+        group_status = np.zeros(max(len(groups), 1), np.int32)
+        seq_status = np.zeros(max(len(arr), 1), np.int32)
+        added = C.c_int32()
+        _check(self._lib.gwamd_poa_add_poa_groups_resident(
+            self._handle, handles, len(sets), arr.ctypes.data_as(C.c_void_p), groups.ctypes.data_as(C.c_void_p),
+            len(groups), group_status.ctypes.data_as(C.c_void_p), seq_status.ctypes.data_as(C.c_void_p),
+            C.byref(added)))
+        if added.value:
+            self._resident_sets.extend(sets)
+        ends = np.cumsum(groups[:added.value])
+        per_seq = [seq_status[e - c:e].tolist() for e, c in zip(ends.tolist(), groups[:added.value].tolist())]
+        return added.value, group_status[:added.value].tolist(), per_seq
+
     def _download_inputs(self):
         """Test hook: (bases, weights) of the batch's packed input as upload()
         left it on the device, the 16 bytes after the last base included."""

@@ -25,8 +25,14 @@ sent to the device a second time, and base qualities become POA weights on the
 device.  Segments of low mean quality are dropped as racon drops them, and
 trim_consensus is racon's coverage trimming of a window's consensus ends.
 
+With device_grouping the cut records stay on the device as well:
+window_slices_resident cuts and groups them there and returns the windows as a
+WindowSlices of flat numpy arrays, build_window_slices_device is that grouping
+alone on given segments, and CudaPoaBatch.add_poa_groups_resident adds many
+windows per call.
+
 Not done: positional (sub-graph) alignment of a segment within its window, a
-command-line polisher.
+native driver for the whole pipeline, a command-line polisher.
 """
 import ctypes as C
 
@@ -103,6 +109,13 @@ def _declare(L):
     L.gwamd_windows_free.argtypes = [vp]
     L.gwamd_build_window_slices.restype = i32
     L.gwamd_build_window_slices.argtypes = [vp, i32, vp, i32, C.c_char_p, i32, vp, i64, vp, i64, i32, i32, P(vp)]
+    L.gwamd_build_window_slices_device.restype = i32
+    L.gwamd_build_window_slices_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, i64, vp, i64, i32, i32, i32, vp,
+                                                   P(vp)]
+    L.gwamd_window_slices_resident.restype = i32
+    L.gwamd_window_slices_resident.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, P(vp)]
+    L.gwamd_poa_add_poa_groups_resident.restype = i32
+    L.gwamd_poa_add_poa_groups_resident.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, P(i32)]
     L.gwamd_window_slices_get.restype = i32
     L.gwamd_window_slices_get.argtypes = [vp, P(_WindowSlicesView)]
     L.gwamd_window_slices_free.restype = None
@@ -418,27 +431,113 @@ def build_window_slices(targets, queries, overlaps, segments, window_length, max
                                        int(round(10 * float(quality_threshold))), arr, len(overlaps),
                                        segs.ctypes.data_as(C.c_void_p), len(segs), int(window_length),
                                        int(max_sequences_per_window), C.byref(h)))
+    ws = _take_window_slices(L, h)
+    return ws.windows(), ws.dropped_by_cap, ws.dropped_by_quality
+
+
+class WindowSlices:
+    """The windows of every target as flat numpy arrays (gwamd_window_slices_view):
+    per sequence, window after window and the backbone first, `slices`
+    (SLICE_DTYPE; set 0 the targets, set 1 the queries), `overlap` (-1 for a
+    backbone), `t_begin` and `t_end` relative to the window's first base; per
+    window `counts` (its sequences), `target` and `index` (k); and the two
+    counters dropped_by_cap and dropped_by_quality."""
+
+    def __init__(self, slices, counts, target, index, overlap, t_begin, t_end, dropped_by_cap, dropped_by_quality):
+        self.slices, self.counts, self.target, self.index = slices, counts, target, index
+        self.overlap, self.t_begin, self.t_end = overlap, t_begin, t_end
+        self.dropped_by_cap, self.dropped_by_quality = int(dropped_by_cap), int(dropped_by_quality)
+
+    def __len__(self):
+        return len(self.counts)
+
+    def windows(self):
+        """The list of dicts build_window_slices returns."""
+        slices = self.slices.tolist()  # tuples of ints
+        windows, s = [], 0
+        for i in range(len(self.counts)):
+            c = int(self.counts[i])
+            windows.append({"target": int(self.target[i]), "window": int(self.index[i]), "slices": slices[s:s + c],
+                            "overlap": self.overlap[s:s + c].tolist(), "t_begin": self.t_begin[s:s + c].tolist(),
+                            "t_end": self.t_end[s:s + c].tolist()})
+            s += c
+        return windows
+
+
+def _take_window_slices(L, h):
+    """The arrays of a gwamd_window_slices handle, copied; the handle is freed."""
     try:
         v = _WindowSlicesView()
         _check(L.gwamd_window_slices_get(h, C.byref(v)))
-        slices = _array(v.slices, v.num_sequences, SLICE_DTYPE)
-        counts = _array(v.window_counts, v.num_windows, np.int32)
-        target = _array(v.window_target, v.num_windows, np.uint32)
-        index = _array(v.window_index, v.num_windows, np.uint32)
-        overlap = _array(v.sequence_overlap, v.num_sequences, np.int32)
-        t_begin = _array(v.sequence_t_begin, v.num_sequences, np.int32)
-        t_end = _array(v.sequence_t_end, v.num_sequences, np.int32)
-        slices = slices.tolist()  # tuples of ints
-        windows, s = [], 0
-        for i in range(v.num_windows):
-            c = int(counts[i])
-            windows.append({"target": int(target[i]), "window": int(index[i]), "slices": slices[s:s + c],
-                            "overlap": overlap[s:s + c].tolist(), "t_begin": t_begin[s:s + c].tolist(),
-                            "t_end": t_end[s:s + c].tolist()})
-            s += c
-        return windows, int(v.dropped_by_cap), int(v.dropped_by_quality)
+        return WindowSlices(_array(v.slices, v.num_sequences, SLICE_DTYPE),
+                            _array(v.window_counts, v.num_windows, np.int32),
+                            _array(v.window_target, v.num_windows, np.uint32),
+                            _array(v.window_index, v.num_windows, np.uint32),
+                            _array(v.sequence_overlap, v.num_sequences, np.int32),
+                            _array(v.sequence_t_begin, v.num_sequences, np.int32),
+                            _array(v.sequence_t_end, v.num_sequences, np.int32),
+                            v.dropped_by_cap, v.dropped_by_quality)
     finally:
         L.gwamd_window_slices_free(h)
+
+
+def build_window_slices_device(targets, queries, overlaps, segments, window_length, max_sequences_per_window=100,
+                               query_reads=None, quality_threshold=10.0, device_id=0, allocator=None):
+    """build_window_slices with the grouping done by kernels on device_id: the
+    segments go up, a WindowSlices comes back, equal to the host's in every
+    array and both counters.  query_reads: the queries as a DeviceReads; when
+    it carries qualities they are read where they are resident and racon's
+    mean-quality rule applies as in build_window_slices.  allocator: a
+    cudaaligner.DeviceAllocator whose pool the device arrays are counted
+    against during the call (RuntimeError when it is too small, with the pool
+    as it was).  ValueError, before any device call, for window_length <= 0,
+    max_sequences_per_window < 1, a negative threshold and a segment whose
+    overlap index, read id, window or query range is out of bounds."""
+    L = load_library()
+    to, qo = _lengths_offsets(targets), _lengths_offsets(queries)
+    handle = None
+    if query_reads is not None:
+        handle = getattr(query_reads, "_handle", None)
+        if not handle:
+            raise TypeError("query_reads must be an open DeviceReads")
+    arr = _overlap_array(overlaps)
+    segs = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+    h = C.c_void_p()
+    _check(L.gwamd_build_window_slices_device(to, len(targets), qo, len(queries), handle,
+                                              int(round(10 * float(quality_threshold))), arr, len(overlaps),
+                                              segs.ctypes.data_as(C.c_void_p), len(segs), int(window_length),
+                                              int(max_sequences_per_window), int(device_id),
+                                              allocator._handle if allocator is not None else None, C.byref(h)))
+    return _take_window_slices(L, h)
+
+
+def window_slices_resident(overlaps, query_reads, target_reads, window_length, max_sequences_per_window=100,
+                           quality_threshold=10.0, num_alignment_engines=1, cigars=None,
+                           cigar_convention="genomeworks"):
+    """Cut, then group, on the device: what build_window_slices makes of
+    window_segments_resident's records (of window_segments_cigar's with
+    cigars=, one CIGAR per overlap in cigar_convention), as a WindowSlices,
+    without a record on the host: only the overlaps (and the ops) go up and
+    only the grouped arrays come back.  The mean-quality rule applies when
+    query_reads carries qualities."""
+    L = load_library()
+    handles = _handles(query_reads, target_reads)
+    if not handles:
+        raise TypeError("query_reads and target_reads must be DeviceReads")
+    arr = _overlap_array(overlaps)
+    ops = offsets = None
+    code = 0
+    if cigars is not None:
+        if len(cigars) != len(overlaps):
+            raise ValueError("one CIGAR per overlap expected")
+        code = _convention(cigar_convention)
+        ops_array, offsets_array = _pack_cigars(cigars)
+        ops, offsets = ops_array.ctypes.data_as(C.c_void_p), offsets_array.ctypes.data_as(C.c_void_p)
+    h = C.c_void_p()
+    _check(L.gwamd_window_slices_resident(*handles, arr, len(overlaps), ops, offsets, code, int(window_length),
+                                          int(max_sequences_per_window), int(round(10 * float(quality_threshold))),
+                                          int(num_alignment_engines), C.byref(h)))
+    return _take_window_slices(L, h)
 
 
 def trim_consensus(consensus, coverage, num_sequences):
@@ -479,7 +578,7 @@ def _slice_weights(qualities, sl):
 def polish(targets, queries, overlaps, window_length=500, max_sequences_per_window=100, banded=True,
            band_width=256, scores=(8, -6, -8), num_alignment_engines=1, device_id=0, max_gpu_mem=None,
            return_windows=False, device_windows=False, query_qualities=None, target_qualities=None,
-           quality_threshold=10.0, trim=False, cigars=None, cigar_convention="genomeworks"):
+           quality_threshold=10.0, trim=False, cigars=None, cigar_convention="genomeworks", device_grouping=False):
     """Polished targets from targets, reads and overlaps (query = read, target =
     target): the overlaps are aligned and cut on the GPU
     (window_segments_resident), grouped into windows (build_windows) and run
@@ -506,6 +605,13 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
     window_segments_cigar: the overlaps are not aligned again and no aligner
     is created; everything after the segments is the same.
 
+    device_grouping: implies device_windows.  The cut records stay on the
+    device and are grouped there (window_slices_resident): only the grouped
+    arrays come back, the windows with at least three sequences are picked and
+    sized with numpy on the flat arrays and added with add_poa_groups_resident,
+    as many per call as the batch takes.  Per-window lists are built only for
+    return_windows.  Same result and stats as device_windows=True.
+
     Returns (polished, stats); stats counts "windows", "backbone_by_rule"
     (fewer than three sequences), "backbone_by_status", "dropped_by_cap",
     "dropped_by_quality", "trimmed_bases" and carries the "max_sequence_size"
@@ -519,7 +625,8 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
 
     targets = [t[1] if isinstance(t, tuple) else t for t in targets]
     queries = [q[1] if isinstance(q, tuple) else q for q in queries]
-    resident = bool(device_windows) or query_qualities is not None or target_qualities is not None
+    resident = bool(device_windows) or bool(device_grouping) or query_qualities is not None or \
+        target_qualities is not None
     if cigars is not None:
         if len(cigars) != len(overlaps):
             raise ValueError("%d CIGARs for %d overlaps" % (len(cigars), len(overlaps)))
@@ -533,12 +640,34 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
             raise
     try:
         with torch.cuda.device(device_id):
-            if cigars is not None:
+            if device_grouping:
+                grouped = window_slices_resident(overlaps, q_reads, t_reads, window_length, max_sequences_per_window,
+                                                 quality_threshold, num_alignment_engines, cigars, cigar_convention)
+            elif cigars is not None:
                 segments = window_segments_cigar(overlaps, cigars, window_length, cigar_convention, device_id)
             else:
                 segments = window_segments_resident(overlaps, q_reads, t_reads, window_length, num_alignment_engines)
         by_quality = 0
-        if resident:
+        if device_grouping:
+            # everything below works on the flat arrays; per-window lists only for return_windows
+            dropped, by_quality = grouped.dropped_by_cap, grouped.dropped_by_quality
+            first = np.concatenate([[0], np.cumsum(grouped.counts, dtype=np.int64)])
+            seq_len = grouped.slices["end"].astype(np.int64) - grouped.slices["begin"]
+            backbone = [_slice_text((targets, queries), sl) for sl in grouped.slices[first[:-1]].tolist()]
+            windows = None
+            if return_windows:
+                windows = grouped.windows()
+                for w in windows:
+                    w["sequences"] = [_slice_text((targets, queries), sl) for sl in w["slices"]]
+                    w["weights"] = [_slice_weights((target_qualities, query_qualities), sl) for sl in w["slices"]]
+            num_seqs, window_target = grouped.counts.tolist(), grouped.target.tolist()
+            todo = np.nonzero(grouped.counts >= 3)[0]
+            in_todo = np.repeat(grouped.counts >= 3, grouped.counts)
+            longest = max(int(seq_len[in_todo].max()), 1) if len(todo) else 1
+            todo_slices, todo_counts = grouped.slices[in_todo], grouped.counts[todo]
+            todo_first = np.concatenate([[0], np.cumsum(todo_counts, dtype=np.int64)])
+            todo = todo.tolist()
+        elif resident:
             windows, dropped, by_quality = build_window_slices(
                 targets, queries, overlaps, segments, window_length, max_sequences_per_window,
                 query_qualities=query_qualities, quality_threshold=quality_threshold)
@@ -555,17 +684,19 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
                                              max_sequences_per_window)
             backbone = [w["sequences"][0] for w in windows]
             lengths = [[len(s) for s in w["sequences"]] for w in windows]
-        stats = {"windows": len(windows), "backbone_by_rule": 0, "backbone_by_status": 0, "dropped_by_cap": dropped,
+        if not device_grouping:
+            num_seqs, window_target = [len(n) for n in lengths], [w["target"] for w in windows]
+            todo = [i for i, n in enumerate(num_seqs) if n >= 3]
+            longest = max([n for i in todo for n in lengths[i]] + [1])
+        stats = {"windows": len(num_seqs), "backbone_by_rule": 0, "backbone_by_status": 0, "dropped_by_cap": dropped,
                  "dropped_by_quality": by_quality, "trimmed_bases": 0}
-        todo = [i for i, n in enumerate(lengths) if len(n) >= 3]
-        stats["backbone_by_rule"] = len(windows) - len(todo)
-        longest = max([n for i in todo for n in lengths[i]] + [1])
+        stats["backbone_by_rule"] = len(num_seqs) - len(todo)
         # a sequence must be shorter than the batch's limit; sizes in steps of 64
         max_sequence_size = (longest + 1 + 63) // 64 * 64
         stats["max_sequence_size"] = max_sequence_size
-        consensus = [None] * len(windows)
-        coverage = [None] * len(windows)
-        status = [None] * len(windows)
+        consensus = [None] * len(num_seqs)
+        coverage = [None] * len(num_seqs)
+        status = [None] * len(num_seqs)
         if todo:
             if max_gpu_mem is None:
                 max_gpu_mem = int(0.5 * torch.cuda.mem_get_info(device_id)[0])
@@ -589,31 +720,53 @@ def polish(targets, queries, overlaps, window_length=500, max_sequences_per_wind
                 batch.reset()
                 del held[:]
 
-            for i in todo:
-                st = add(i)
-                if st == 1:  # exceeded_maximum_poas: process what the batch holds, then add again
-                    flush()
+            def add_many(at):
+                """As many of todo[at:] as the batch takes, in one call; the index of the first it did not take."""
+                added, group_status, _ = batch.add_poa_groups_resident([t_reads, q_reads],
+                                                                       todo_slices[todo_first[at]:], todo_counts[at:])
+                for i, st in zip(todo[at:at + added], group_status):
+                    if st != 0:
+                        status[i] = st
+                    else:
+                        held.append(i)
+                return at + added
+
+            if device_grouping:
+                at = 0
+                while at < len(todo):
+                    took = add_many(at)
+                    if took < len(todo):  # exceeded_maximum_poas
+                        if took == at and not held:  # an empty batch does not hold it either
+                            status[todo[took]] = 1
+                            took += 1
+                        flush()
+                    at = took
+            else:
+                for i in todo:
                     st = add(i)
-                if st != 0:
-                    status[i] = st
-                    continue
-                held.append(i)
+                    if st == 1:  # exceeded_maximum_poas: process what the batch holds, then add again
+                        flush()
+                        st = add(i)
+                    if st != 0:
+                        status[i] = st
+                        continue
+                    held.append(i)
             flush()
             del batch
     finally:
         q_reads.close()
         t_reads.close()
     polished = ["" for _ in targets]
-    for i, w in enumerate(windows):
+    for i, target in enumerate(window_target):
         text = backbone[i]
         if consensus[i] is not None and status[i] == 0:
             text = consensus[i]
             if trim:
-                text = trim_consensus(text, coverage[i], len(lengths[i]))
+                text = trim_consensus(text, coverage[i], num_seqs[i])
                 stats["trimmed_bases"] += len(consensus[i]) - len(text)
-        elif len(lengths[i]) >= 3:
+        elif num_seqs[i] >= 3:
             stats["backbone_by_status"] += 1
-        polished[w["target"]] += text
+        polished[target] += text
     if return_windows:
         return polished, stats, windows, consensus, status
     return polished, stats

@@ -19,8 +19,12 @@
 // mean-quality filter and its coverage trimming are in the C ABI
 // (gwamd_build_window_slices, gwamd_trim_consensus, include/gwamd_polish.h).
 //
+// window_slices_resident is the cut and the grouping in one call with the
+// records left on the device, build_window_slices_device the grouping alone on
+// given segments, add_poa_groups_resident many windows per call.
+//
 // Not done here: positional (sub-graph) alignment of a segment within its
-// window, a command-line polisher.
+// window, a native driver for the whole pipeline, a command-line polisher.
 #pragma once
 
 #include <claraparabricks/genomeworks/cudaaligner/cudaaligner.hpp>
@@ -189,6 +193,59 @@ struct ReadSlice
 cudapoa::StatusType add_poa_group_resident(cudapoa::Batch& batch, std::vector<cudapoa::StatusType>& per_seq_status,
                                            const std::vector<const cudamapper::DeviceReads*>& sets,
                                            const std::vector<ReadSlice>& slices);
+
+/// The windows of every target as slices of the targets (set 0: the backbone,
+/// first in its window) and the queries (set 1), window after window: the
+/// arrays of gwamd_window_slices_view (include/gwamd_polish.h)
+struct WindowSlices
+{
+    std::vector<ReadSlice> slices;         ///< per sequence
+    std::vector<int32_t> window_counts;    ///< sequences per window
+    std::vector<read_id_t> window_target;  ///< per window
+    std::vector<uint32_t> window_index;    ///< per window: k
+    std::vector<int32_t> sequence_overlap; ///< per sequence, -1 for a backbone
+    std::vector<int32_t> sequence_t_begin; ///< relative to the window's first base
+    std::vector<int32_t> sequence_t_end;
+    std::int64_t dropped_by_cap     = 0;
+    std::int64_t dropped_by_quality = 0;
+};
+
+/// The grouping of build_windows without the bases, done by kernels on the
+/// current device (gwamd_build_window_slices_device): `segments` go up, the
+/// arrays above come back.  With query_reads that carry qualities a segment
+/// whose mean quality - 33 is below quality_threshold_tenths / 10 is dropped
+/// before the cap is looked at (racon's rule), its characters read where they
+/// are resident.  Device arrays are counted against the allocator's pool.
+WindowSlices build_window_slices_device(DefaultDeviceAllocator allocator, const io::FastaParser& targets,
+                                        const io::FastaParser& queries,
+                                        const std::vector<cudamapper::Overlap>& overlaps,
+                                        const std::vector<WindowSegment>& segments, int32_t window_length,
+                                        int32_t max_sequences_per_window                  = 100,
+                                        const cudamapper::DeviceReads* query_reads        = nullptr,
+                                        int32_t quality_threshold_tenths                  = 100);
+
+/// Cut, then group, on the device (gwamd_window_slices_resident): the overlaps
+/// are aligned on the resident reads and cut from the aligners' device paths,
+/// or, with `cigars` (one per overlap, in `convention`), cut from their runs;
+/// the records stay on the device and only the arrays above come back.
+WindowSlices window_slices_resident(const std::vector<cudamapper::Overlap>& overlaps,
+                                    const cudamapper::DeviceReads& query_reads,
+                                    const cudamapper::DeviceReads& target_reads, int32_t window_length,
+                                    int32_t max_sequences_per_window = 100, int32_t quality_threshold_tenths = 100,
+                                    int32_t num_alignment_engines                    = 1,
+                                    const std::vector<std::vector<uint32_t>>* cigars = nullptr,
+                                    CigarConvention convention                       = CigarConvention::genomeworks);
+
+/// add_poa_group_resident for many groups in one call: group g is the next
+/// group_counts[g] of `slices`.  Equivalent to adding them one by one, in order,
+/// up to the first the batch answers exceeded_maximum_poas for; returns the
+/// number of groups before that one.  group_status receives one status per
+/// group added and per_seq_status one per slice of those groups.  Every slice is
+/// checked before the first group is added.
+int32_t add_poa_groups_resident(cudapoa::Batch& batch, std::vector<cudapoa::StatusType>& group_status,
+                                std::vector<cudapoa::StatusType>& per_seq_status,
+                                const std::vector<const cudamapper::DeviceReads*>& sets,
+                                const std::vector<ReadSlice>& slices, const std::vector<int32_t>& group_counts);
 
 } // namespace cudapolish
 } // namespace genomeworks

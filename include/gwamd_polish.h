@@ -232,6 +232,21 @@ int32_t gwamd_poa_add_poa_group_resident(gwamd_poa_batch* batch, const gwamd_dev
                                          int32_t num_sets, const gwamd_read_slice* slices, int32_t n,
                                          int32_t* per_seq_status);
 
+/* gwamd_poa_add_poa_group_resident for num_groups groups in one call: group g is the next
+ * group_counts[g] slices, and the call is equivalent to adding them one by one, in order.  It
+ * stops before the first group the single call would answer exceeded_maximum_poas (1) for: the
+ * batch is then as that call leaves it, *num_added counts the groups before it, and the caller
+ * runs the batch and goes on from there.  A group with any other status is consumed (counted in
+ * *num_added) and its status written to group_status[g]; per_seq_status has one entry per slice,
+ * as the single call fills it.  Entries of the groups that were not reached are not written.
+ * Every slice of every group is validated before the first group is added: an invalid one
+ * (above), a negative count, or a NULL array with something behind it is
+ * GWAMD_E_INVALID_ARGUMENT with the batch unchanged.  Returns 0, or 1 when it stopped early. */
+int32_t gwamd_poa_add_poa_groups_resident(gwamd_poa_batch* batch, const gwamd_device_reads* const* sets,
+                                          int32_t num_sets, const gwamd_read_slice* slices,
+                                          const int32_t* group_counts, int32_t num_groups, int32_t* group_status,
+                                          int32_t* per_seq_status, int32_t* num_added);
+
 /* Test hook: the batch's packed bases and weights as gwamd_poa_upload left them on the device,
  * num_bases + 16 bytes each (the 16 bytes after the last base are zero); returns that count,
  * and only that with both outputs NULL. */
@@ -266,6 +281,46 @@ int32_t gwamd_build_window_slices(const int64_t* target_offsets, int32_t num_tar
                                   int32_t quality_threshold_tenths, const gwamd_overlap* overlaps, int64_t n,
                                   const gwamd_window_segment* segments, int64_t num_segments, int32_t window_length,
                                   int32_t max_sequences_per_window, gwamd_window_slices** out);
+/* ---- the grouping on the device ---------------------------------------------------
+ *
+ * gwamd_build_window_slices with the work done by kernels on device_id: the given segments go
+ * up, are classified, sorted stably by window and written out as slices; the view of the handle
+ * equals gwamd_build_window_slices' in every array and both counters, and the same input gives
+ * the same bytes.  The quality filter applies exactly when query_reads_or_null is given and
+ * carries qualities (gwamd_device_reads_create_with_qualities): the characters are read where
+ * they are resident.  Device arrays are counted against allocator_or_null's pool for the
+ * duration of the call; an allocation the pool refuses is GWAMD_E_RUNTIME with the pool as it
+ * was.  GWAMD_E_INVALID_ARGUMENT, before any device call, for what gwamd_build_window_slices
+ * refuses and for a negative quality_threshold_tenths (with or without qualities), a negative
+ * device_id, a handle on another device than device_id or whose reads are not those of
+ * query_offsets, 2^31 or more windows, and windows plus segments (each of which may become a
+ * sequence) of 2^31 or more. */
+int32_t gwamd_build_window_slices_device(const int64_t* target_offsets, int32_t num_targets,
+                                         const int64_t* query_offsets, int32_t num_queries,
+                                         const gwamd_device_reads* query_reads_or_null,
+                                         int32_t quality_threshold_tenths, const gwamd_overlap* overlaps, int64_t n,
+                                         const gwamd_window_segment* segments, int64_t num_segments,
+                                         int32_t window_length, int32_t max_sequences_per_window, int32_t device_id,
+                                         struct gwamd_device_allocator* allocator_or_null, gwamd_window_slices** out);
+
+/* Cut, then group, without a record on the host: only the overlaps (and the ops) go up and only
+ * the grouped arrays come back.  With op_offsets_or_null NULL the overlaps are aligned on the
+ * resident reads and cut as gwamd_window_segments_resident cuts them (an overlap beyond the
+ * aligner's limits contributes nothing; num_alignment_engines engines); otherwise they are cut
+ * from ops[op_offsets[i], op_offsets[i + 1]) in `convention` as gwamd_window_segments_cigar cuts
+ * them, and num_alignment_engines is not looked at.  The records of the whole call lie in one
+ * device array and are grouped once; the view equals that of gwamd_build_window_slices on the
+ * records of the matching entry above, with the quality filter when query_reads carries
+ * qualities.  The reads are on the current device.  GWAMD_E_INVALID_ARGUMENT, before any device
+ * call: what those two entries refuse, an overlap that names a read or a position outside the
+ * two sets, max_sequences_per_window < 1, a negative threshold, ops without op_offsets, and the
+ * limits of gwamd_build_window_slices_device. */
+int32_t gwamd_window_slices_resident(const gwamd_device_reads* query_reads, const gwamd_device_reads* target_reads,
+                                     const gwamd_overlap* overlaps, int32_t n, const uint32_t* ops_or_null,
+                                     const int64_t* op_offsets_or_null, int32_t convention, int32_t window_length,
+                                     int32_t max_sequences_per_window, int32_t quality_threshold_tenths,
+                                     int32_t num_alignment_engines, gwamd_window_slices** out);
+
 /* Pointers into the handle, valid until gwamd_window_slices_free. */
 int32_t gwamd_window_slices_get(const gwamd_window_slices* windows, gwamd_window_slices_view* view);
 void gwamd_window_slices_free(gwamd_window_slices* windows);
@@ -277,6 +332,17 @@ void gwamd_window_slices_free(gwamd_window_slices* windows);
  * is not before the last, the consensus is kept whole (0, length), where racon warns. */
 int32_t gwamd_trim_consensus(const uint16_t* coverage, int32_t length, int32_t num_sequences, int32_t* begin,
                              int32_t* past_the_end);
+
+/* Measurement hook (scripts/polish_group_bench.py): the arguments and checks of
+ * gwamd_build_window_slices_device without a pool; the segments go up once and the records, then
+ * resident, are grouped `repeats` times, each timed from the first launch to the grouped arrays'
+ * arrival in host memory: seconds[0, repeats).  (When no target has a window nothing is timed.) */
+int32_t gwamd_internal_group_repeat(const int64_t* target_offsets, int32_t num_targets, const int64_t* query_offsets,
+                                    int32_t num_queries, const gwamd_device_reads* query_reads_or_null,
+                                    int32_t quality_threshold_tenths, const gwamd_overlap* overlaps, int64_t n,
+                                    const gwamd_window_segment* segments, int64_t num_segments, int32_t window_length,
+                                    int32_t max_sequences_per_window, int32_t device_id, int32_t repeats,
+                                    double* seconds);
 
 /* Test hook: gwamd_window_segments on paths laid out as the aligner leaves them on the device,
  * end -> start, path i at paths[i * stride, i * stride + path_lengths[i]), stride a positive
